@@ -2,8 +2,14 @@
 """Benchmark of the matching hot path (coarse correlation + dual-softmax mutual-NN assignment
 -> window crop -> fine correlation + soft-argmax) on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, runs W warm-up steps, times ONE region of exactly K steps and prints the line (`value`,
+`ms_per_step`); --dump-outputs DIR first writes what the last timed step computed as DIR/<name>.npy.  Everything else
+it measures or checks runs with --full only: the region repeated with its spread, verification against the CPU
+oracle, per-kernel event timings and rooflines, the secondary lines (not with --quick), the CPU baseline (not with
+--skip-cpu).
 
 One step = one pass of the path over one batch of synthetic feature maps that are already
 resident in HBM.  Default workload = BASELINE.json configs[1]: one 640x480 pair, C=256 coarse
@@ -386,6 +392,28 @@ def verify(pair, nverify=2):
     nontrivial = int((rconf[ri] < 0.999).sum())
     return {"ok": bool(ok), "samples_checked": nv, "matches": len(gk), "oracle_matches": len(rk), "mconf_err": conf_err,
             "mconf_below_0.999": nontrivial, "fine_err_px": fine_err}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, pair, m):
+    """--dump-outputs: what the step of `pair` last computed, as a caller of the path receives it - the coarse match list
+    (b_ids, i_ids, j_ids, mconf, mkpts0_c, mkpts1_c) and the fine keypoints (mkpts0_f, mkpts1_f: [M,3] = x, y, std) - as
+    out_dir/<name>.npy.  Ids go out as float64 (exact), the rest as float32.  Above DUMP_LIMIT_BYTES a fixed, seeded
+    sample of the M rows is written, the same rows of every array, and their indices as sample_rows.npy."""
+    buf, k0, k1 = pair.last
+    arrays = {k: v.cpu().numpy() for k, v in buf.sliced(m).items()}
+    arrays["mkpts0_f"], arrays["mkpts1_f"] = k0[:m].cpu().numpy(), k1[:m].cpu().numpy()
+    arrays = {k: v.astype(np.float64 if k.endswith("_ids") else np.float32) for k, v in arrays.items()}
+    row_bytes = sum(v[:1].nbytes for v in arrays.values())
+    if m * row_bytes > DUMP_LIMIT_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(m, DUMP_LIMIT_BYTES // (row_bytes + 8), replace=False))
+        arrays = {k: v[rows] for k, v in arrays.items()}
+        arrays["sample_rows"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
 
 
 def cpu_model():
@@ -784,11 +812,20 @@ def main():
                     help="storage of the fine maps: nchw = the reference's contiguous [N,Cf,Hf,Wf]; nhwc = channels-last")
     ap.add_argument("--fine-path", default="maps", choices=["windows", "maps"],
                     help="windows = window crop -> fine kernel; maps = crop + fine from the maps in one call (fm_fine_match_maps)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the timed region repeated with its spread, verification against "
+                         "the CPU oracle, per-kernel event timings and rooflines, the secondary lines (unless --quick) and "
+                         "the CPU baseline (unless --skip-cpu).  Without it one region of exactly --steps steps is timed")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last timed step computed (its match list and fine "
+                         "keypoints, the arrays a caller receives) as DIR/<name>.npy in float32 / float64")
     ap.add_argument("--reps", type=int, default=0,
-                    help="repetitions of the timed K-step region (0 = enough for >= 120 ms of GPU work, at least 3)")
+                    help="with --full: repetitions of the timed K-step region (0 = enough for >= 1.2 s of GPU work, at "
+                         "least 3)")
     ap.add_argument("--no-graph", action="store_true", help="launch eagerly instead of replaying hipGraphs")
-    ap.add_argument("--skip-cpu", action="store_true")
-    ap.add_argument("--quick", action="store_true", help="skip the secondary lines (other workloads and data, module API)")
+    ap.add_argument("--skip-cpu", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--quick", action="store_true",
+                    help="with --full: skip the secondary lines (other workloads and data, module API)")
     ap.add_argument("--batch", type=int, default=0,
                     help="diagnostic: pairs per launch (overrides the workload's batch; the JSON line is then not the metric's config)")
     ap.add_argument("--stages", default="all", choices=["all", "coarse", "fine"],
@@ -806,6 +843,8 @@ def main():
                     help="test hook: run the launcher / rank protocol with a CPU stand-in for the HIP step (no GPU needed; "
                          "the JSON line is marked as a stub and carries no measurement)")
     a = ap.parse_args()
+    if a.reps and not a.full:
+        ap.error("--reps repeats the timed region: it needs --full (a plain run times exactly --steps steps)")
 
     # `python bench.py --gpus N` (N > 1) without a launcher: this process becomes the launcher of N ranks.  Decided
     # before any GPU call of this process (torch is imported, nothing is initialised).
@@ -885,11 +924,12 @@ def main():
     for i in range(a.warmup):
         run(i)
     barrier()
-    # A short --steps alone is a sample of a millisecond: the timed K-step region (barrier + synchronise on both
-    # sides, as the contract says) is repeated R times and the MEDIAN repetition is reported, with the spread.
-    # R from a probe of the step time: >= 1.2 s of GPU work in total (long enough for a once-per-second utilisation
-    # sampler outside this process to see the GPU busy), at least 3, at most 2000 repetitions.
-    reps = a.reps
+    # A plain run times ONE region of exactly K steps (barrier + synchronise on both sides, as the contract says).
+    # --full: a short --steps alone is a sample of a millisecond, so the region is repeated R times and the MEDIAN
+    # repetition is reported, with the spread.  R from a probe of the step time: >= 1.2 s of GPU work in total (long
+    # enough for a once-per-second utilisation sampler outside this process to see the GPU busy), at least 3, at most
+    # 2000 repetitions.
+    reps = a.reps if a.full else 1
     if reps <= 0:
         tp = time.perf_counter()
         nprobe = max(8, min(a.steps, 64))
@@ -912,6 +952,9 @@ def main():
         for p in pairs:
             ms.append(p.last[0].read_count())
         assert min(ms) > 0, "a timed step produced no matches"
+        if a.dump_outputs and rank == 0:
+            last = (a.steps - 1) % npairs          # run(i) of the timed region's last step
+            dump_outputs(a.dump_outputs, pairs[last], ms[last])
 
         if grouped:
             # cfg#4's exchange: the match lists of the last step of EVERY resident input set, packed as 24-byte
@@ -926,7 +969,7 @@ def main():
             gather_ms, gathered = timed_gather(rec, world, torch.cuda.synchronize, coll_dev)
 
         tk = ver = None
-        if rank == 0:
+        if rank == 0 and a.full:
             pairs[0].stages = "all"
             pairs[0].step()
             torch.cuda.synchronize()
@@ -948,33 +991,17 @@ def main():
 
     pairs_per_step = wl["n"]
     value = world * a.steps * pairs_per_step / dt
-    flops = 2.0 * wl["n"] * pairs[0].l * pairs[0].l * wl["c"]          # one GEMM per pair
-    # the whole correlation: max pass + the sum kernels (+ the dense kernel's float16 planes when that path runs);
-    # k_prep_split (the quantisation the product needs) is priced beside it
-    t_corr = tk["max"] + tk["sparse"] + tk["planes"] + tk["dense"]
-    ach = flops / (t_corr * 1e-3) / 1e12
-    ach_max = flops / (tk["max"] * 1e-3) / 1e12
     m_avg = float(np.mean(ms)) / wl["n"]
-    ww, cf = a.window * a.window, wl["cf"]
-    crop_bytes = 2.0 * m_avg * wl["n"] * ww * cf * 4 * 2      # both images: read + write
-    fine_bytes = 2.0 * m_avg * wl["n"] * ww * cf * 4 + 2.0 * m_avg * wl["n"] * 12
-    traffic, traffic_src = committed_traffic(a.workload)
-    copy_gbs = copy_rate(crop_bytes, dev)
     maps_path = pairs[0].fine_path == "maps"
     # (the common path's five: prep, max pass, thresholds, screening, assignment)
     launches = 5 + (2 if pairs[0].dense and not pairs[0].flat else 0) + \
         ((2 if a.layout == "nchw" and not pairs[0].fuse_maps else 1) if maps_path else (3 if a.layout == "nhwc" else 2))
-    map_bytes = 2.0 * wl["n"] * cf * 4 * sh0["hf"] * sh0["wf"]           # both fine maps
     out = {
         "metric": ("image-pairs/sec at 640x480 (coarse corr + dual-softmax mutual-NN + fine window refinement)"
                    if a.workload == "cfg2" else f"image-pairs/sec ({a.workload})")
                   + ("" if a.stages == "all" else f" [DIAGNOSTIC: {a.stages} stage only]"),
         "value": round(value, 2), "unit": "image-pairs/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
         "ms_per_step": round(dt / a.steps * 1e3, 4),
-        "ms_per_step_spread": {"repetitions": reps, "min": round(min(dts) / a.steps * 1e3, 4),
-                               "max": round(max(dts) / a.steps * 1e3, 4), "timed_regions_total_s": round(t_region, 3),
-                               "note": "the K-step region (barrier + synchronise on both sides) repeated; value and "
-                                       "ms_per_step are the median repetition"},
         "higher_is_better": True, "scaling": "weak",
         "vs_baseline": None,
         "dtype": "i8 screening + f32 exact",
@@ -988,36 +1015,54 @@ def main():
                    "concurrent_streams": nstreams, "matches_per_pair": round(m_avg, 1),
                    "launches_per_step": launches, "pair_block": [pair_lo, pair_hi],
                    "host_enqueue_ms_per_step": round(1e3 * t_enq / a.steps, 4)},
-        "verified": (ver["ok"] if ver else None), "verification": ver,
+    }
+    if a.full:
+        flops = 2.0 * wl["n"] * pairs[0].l * pairs[0].l * wl["c"]          # one GEMM per pair
+        # the whole correlation: max pass + the sum kernels (+ the dense kernel's float16 planes when that path runs);
+        # k_prep_split (the quantisation the product needs) is priced beside it
+        t_corr = tk["max"] + tk["sparse"] + tk["planes"] + tk["dense"]
+        ach = flops / (t_corr * 1e-3) / 1e12
+        ach_max = flops / (tk["max"] * 1e-3) / 1e12
+        ww, cf = a.window * a.window, wl["cf"]
+        crop_bytes = 2.0 * m_avg * wl["n"] * ww * cf * 4 * 2      # both images: read + write
+        fine_bytes = 2.0 * m_avg * wl["n"] * ww * cf * 4 + 2.0 * m_avg * wl["n"] * 12
+        traffic, traffic_src = committed_traffic(a.workload)
+        copy_gbs = copy_rate(crop_bytes, dev)
+        map_bytes = 2.0 * wl["n"] * cf * 4 * sh0["hf"] * sh0["wf"]           # both fine maps
+        out["ms_per_step_spread"] = {"repetitions": reps, "min": round(min(dts) / a.steps * 1e3, 4),
+                                     "max": round(max(dts) / a.steps * 1e3, 4), "timed_regions_total_s": round(t_region, 3),
+                                     "note": "the K-step region (barrier + synchronise on both sides) repeated; value and "
+                                             "ms_per_step are the median repetition"}
+        out["verified"], out["verification"] = (ver["ok"] if ver else None), ver
         # The coarse correlation = every launch that works on the L x S product: the int8 max pass (the one dense
         # sweep) and the sparse sum kernel (re-executes the live units, exact float32 dots for the significant entries)
         # (+ float16 planes and the dense sum kernel under FM_MODE_DENSE).  Priced against the int8 MFMA peak, the
         # matrix-core type the dominant kernel runs on.
-        "roofline": {"bound": "mfma",
-                     "kernel": "coarse correlation: k_max_i8<256> + k_thresh + k_screen_rows<256>"
-                               + (" + k_prep_f16 + k_dense<256>" if pairs[0].dense else "")
-                               + " (every launch on the L x S product; v_mfma_i32_32x32x32_i8)",
-                     "achieved": round(ach, 2), "peak": PEAK_I8_DENSE_TOPS, "unit": "TFLOP/s",
-                     "frac": round(ach / PEAK_I8_DENSE_TOPS, 4),
-                     "frac_of_f16_peak": round(ach / PEAK_F16_DENSE_TFLOPS, 4),
-                     "traffic": traffic, "traffic_source": traffic_src,
-                     "avg_ms": round(t_corr, 5), "algorithmic_flop": flops,
-                     "note": "algorithmic 2*L*S*C flop of the ONE product per pair over the summed event-timed launch "
-                             "durations of the correlation kernels; `peak` is the dense int8 MFMA peak (2x the f16/bf16 "
-                             "figure the north star names: frac_of_f16_peak)",
-                     "max_pass": {"kernel": "k_max_i8<256>", "avg_ms": round(tk["max"], 5), "achieved": round(ach_max, 2),
-                                  "frac": round(ach_max / PEAK_I8_DENSE_TOPS, 4),
-                                  "frac_of_f16_peak": round(ach_max / PEAK_F16_DENSE_TFLOPS, 4)},
-                     "sparse_sum_avg_ms": round(tk["sparse"], 5), "dense_sum_avg_ms": round(tk["dense"], 5),
-                     "f16_planes_avg_ms": round(tk["planes"], 5),
-                     "with_quantisation": {"k_prep_split_avg_ms": round(tk["prep"], 5),
-                                           "frac": round(flops / ((t_corr + tk["prep"]) * 1e-3) / 1e12 / PEAK_I8_DENSE_TOPS, 4)},
-                     "coarse_stage": {"avg_ms": round(tk["coarse"], 5),
-                                      "what": "one fm_coarse_match call (all launches with their in-stream gaps, one stream)"
-                                              + ("; the assignment launch also carries the channels-last copy of image 1's "
-                                                 "fine map (fm_coarse_match_maps)" if pairs[0].fuse_maps else ""),
-                                      "assignment_and_gaps_ms": round(tk["coarse"] - t_corr - tk["prep"], 5)}},
-        "roofline_aux": ({
+        out["roofline"] = {"bound": "mfma",
+                           "kernel": "coarse correlation: k_max_i8<256> + k_thresh + k_screen_rows<256>"
+                                     + (" + k_prep_f16 + k_dense<256>" if pairs[0].dense else "")
+                                     + " (every launch on the L x S product; v_mfma_i32_32x32x32_i8)",
+                           "achieved": round(ach, 2), "peak": PEAK_I8_DENSE_TOPS, "unit": "TFLOP/s",
+                           "frac": round(ach / PEAK_I8_DENSE_TOPS, 4),
+                           "frac_of_f16_peak": round(ach / PEAK_F16_DENSE_TFLOPS, 4),
+                           "traffic": traffic, "traffic_source": traffic_src,
+                           "avg_ms": round(t_corr, 5), "algorithmic_flop": flops,
+                           "note": "algorithmic 2*L*S*C flop of the ONE product per pair over the summed event-timed launch "
+                                   "durations of the correlation kernels; `peak` is the dense int8 MFMA peak (2x the f16/bf16 "
+                                   "figure the north star names: frac_of_f16_peak)",
+                           "max_pass": {"kernel": "k_max_i8<256>", "avg_ms": round(tk["max"], 5), "achieved": round(ach_max, 2),
+                                        "frac": round(ach_max / PEAK_I8_DENSE_TOPS, 4),
+                                        "frac_of_f16_peak": round(ach_max / PEAK_F16_DENSE_TFLOPS, 4)},
+                           "sparse_sum_avg_ms": round(tk["sparse"], 5), "dense_sum_avg_ms": round(tk["dense"], 5),
+                           "f16_planes_avg_ms": round(tk["planes"], 5),
+                           "with_quantisation": {"k_prep_split_avg_ms": round(tk["prep"], 5),
+                                                 "frac": round(flops / ((t_corr + tk["prep"]) * 1e-3) / 1e12 / PEAK_I8_DENSE_TOPS, 4)},
+                           "coarse_stage": {"avg_ms": round(tk["coarse"], 5),
+                                            "what": "one fm_coarse_match call (all launches with their in-stream gaps, one stream)"
+                                                    + ("; the assignment launch also carries the channels-last copy of image 1's "
+                                                       "fine map (fm_coarse_match_maps)" if pairs[0].fuse_maps else ""),
+                                            "assignment_and_gaps_ms": round(tk["coarse"] - t_corr - tk["prep"], 5)}}
+        out["roofline_aux"] = ({
             "fine_from_maps": {"bound": "hbm",
                                "kernel": ("k_nchw_to_nhwc64 (image 1) + " if a.layout == "nchw" else "") + f"k_fine_maps<{a.window}> (window crop + fine stage, no window tensors)",
                                # SURVEY 8(d) fine-kernel bytes ONLY: the window bytes of both images read once + 12 bytes
@@ -1044,8 +1089,7 @@ def main():
                            "unit": "GB/s", "frac": round(fine_bytes / (tk["fine"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
                            "avg_ms": round(tk["fine"], 5), "algorithmic_bytes": fine_bytes}}) | {
             "plain_copy": {"what": "torch device-to-device copy moving as many bytes as the window crop",
-                           "achieved": round(copy_gbs, 1), "unit": "GB/s", "frac": round(copy_gbs / HBM_PEAK_GBS, 4)}},
-    }
+                           "achieved": round(copy_gbs, 1), "unit": "GB/s", "frac": round(copy_gbs / HBM_PEAK_GBS, 4)}}
     out["config"]["fine_maps_layout"] = a.layout
     out["config"]["fine_path"] = ("fm_fine_match_maps (crop + fine from the maps)" if maps_path
                                   else "window crop -> fm_fine_match")
@@ -1055,14 +1099,14 @@ def main():
         # what the collective backend saw: the world size torch.distributed reports and one device identity per rank
         out["distributed"] = {"backend": backend + (" (RCCL)" if backend == "nccl" else ""),
                               "world_size": dist.get_world_size(), "device_uuids": rank_devices}
-    if world == 1 and not a.quick and a.stages == "all":
+    if a.full and world == 1 and not a.quick and a.stages == "all":
         out["extra"] = extras(a, wl, dev, streams, flops)
         # the headline is measured on 'peaky' descriptors (every conf is 1.0, one significant entry per row);
         # the same step on data with textureless cells and missing partners stands next to it
         for key, name in (("mixed_data", "value_on_mixed"), ("borderline_data", "value_on_borderline")):
             v = out["extra"].get(key, {})
             out["config"][name] = v.get("value") if isinstance(v, dict) else None
-    if not a.skip_cpu and world == 1:
+    if a.full and not a.skip_cpu and world == 1:
         out["cpu_baseline"] = cpu_baseline(wl, a.window, 1)
     print(json.dumps(out))
     if grouped:

@@ -73,11 +73,13 @@ def test_match_records_from_the_hip_path_go_through_rccl_all_gathers():
 def test_bench_under_a_launcher_environment_prints_the_distributed_block():
     """`bench.py --gpus 1` with torchrun's environment (WORLD_SIZE = 1): the RCCL group is initialised with device_id, the
     match lists of the timed steps go through both all-gathers, and the JSON line names backend, world size and the
-    device.  A child process (the test process keeps its own GPU state); --quick --skip-cpu: seconds."""
+    device.  A child process (the test process keeps its own GPU state); --full for the verification, --quick
+    --skip-cpu: seconds."""
     env = dict(os.environ, RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()),
                HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "40", "--warmup", "8",
-                        "--quick", "--skip-cpu", "--pairs", "4"], env=env, capture_output=True, text=True, timeout=900)
+                        "--full", "--quick", "--skip-cpu", "--pairs", "4"], env=env, capture_output=True, text=True,
+                       timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -96,7 +98,8 @@ def test_two_ranks_on_one_gpu_run_the_hip_step_and_gather_over_gloo():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "24", "--warmup", "4",
-                        "--quick", "--skip-cpu", "--pairs", "4"], env=env, capture_output=True, text=True, timeout=900)
+                        "--full", "--quick", "--skip-cpu", "--pairs", "4"], env=env, capture_output=True, text=True,
+                       timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]

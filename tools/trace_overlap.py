@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Concurrency of the kernels of a multi-stream bench run from a rocprofv3 --kernel-trace CSV:
 
-    rocprofv3 --kernel-trace --output-format csv -d gpurun_out/trace -- python3 bench.py --quick --skip-cpu --steps 600 --reps 2
-    python tools/trace_overlap.py gpurun_out/trace
+    rocprofv3 --kernel-trace --output-format csv -d prof_trace -- python3 bench.py --full --quick --skip-cpu --steps 600 --reps 2
+    python tools/trace_overlap.py prof_trace
 
 per kernel: launches, mean duration; per queue: mean gap between consecutive kernels; how many kernels run at once
 (time-weighted) over the densest part of the trace."""

@@ -87,6 +87,11 @@ SIGNATURES = {
     "fm_fine_transformer_start": (_i, [_p, _p, _i, _p, _i, _i, _p, _p, _p, _p, _i, _p, _p]),
     "fm_epipolar_errors": (_i, [_p, _p, _i, _p, _p, _i, _i, _p, _p, _p, _f, _p, _p, _p, _p]),
     "fm_fine_match": (_i, [_p, _p, _i, _p, _i, _i, _p, _p, _p, _p, _f, _p, _p, _p]),
+    "fm_fine_match_backward_workspace_bytes": (C.c_size_t, [_i, _i]),
+    "fm_fine_match_backward": (_i, [_p, _p, _i, _p, _i, _i, _p, _p, _f, _p, _p, _p, C.c_size_t, _p, _p, _p, _p, _p]),
+    "fm_gather_windows_backward_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i]),
+    "fm_gather_windows_backward": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, C.c_size_t, _p,
+                                        _p]),
     "fm_fine_maps_scratch_bytes": (C.c_size_t, [_i, _i, _i, _i, _i, _i, _i]),
     "fm_fine_maps_scratch_bytes_dtype": (C.c_size_t, [_i, _i, _i, _i, _i, _i, _i, _i]),
     "fm_fine_match_maps_dtype": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _i, _p, _p,

@@ -195,9 +195,14 @@ class FinePreprocess(nn.Module):
                     win0 = ops.gather_merge_windows(feat_f0, packed, ctx0, b_ids, i_ids, W, stride, hw0_c[0], hw0_c[1])
                     win1 = ops.gather_merge_windows(feat_f1, packed, ctx1, b_ids, j_ids, W, stride, hw1_c[0], hw1_c[1])
             return win0, win1
-        with torch.no_grad():
-            win0 = ops.gather_windows(feat_f0, b_ids, i_ids, W, stride, hw0_c[1], cells=cells0, h_c=hw0_c[0])
-            win1 = ops.gather_windows(feat_f1, b_ids, j_ids, W, stride, hw1_c[1], cells=cells1, h_c=hw1_c[0])
+        if torch.is_grad_enabled() and (self.training or feat_f0.requires_grad or feat_f1.requires_grad):
+            # the crop with its HIP backward (fm_gather_windows_backward): the fine loss reaches the fine maps
+            win0 = ops.gather_windows_grad(feat_f0, b_ids, i_ids, W, stride, hw0_c[1], hw0_c[0], cells=cells0)
+            win1 = ops.gather_windows_grad(feat_f1, b_ids, j_ids, W, stride, hw1_c[1], hw1_c[0], cells=cells1)
+        else:
+            with torch.no_grad():
+                win0 = ops.gather_windows(feat_f0, b_ids, i_ids, W, stride, hw0_c[1], cells=cells0, h_c=hw0_c[0])
+                win1 = ops.gather_windows(feat_f1, b_ids, j_ids, W, stride, hw1_c[1], cells=cells1, h_c=hw1_c[0])
         if self.cat_c_feat:      # training (autograd through the two Linear layers) or shapes outside the fused kernel
             feat_c_win = self.down_proj(torch.cat([feat_c0[b_ids, i_ids], feat_c1[b_ids, j_ids]], 0))
             feat_cf_win = self.merge_feat(torch.cat([
@@ -227,8 +232,10 @@ class FineMatching(nn.Module):
             cache[id(lin)] = hit
         return hit[1]
 
-    @torch.no_grad()
     def forward(self, feat_f0, feat_f1, data):
+        """In training mode, or when feat_f0 / feat_f1 require grad (under grad mode), the outputs carry the HIP
+        backward (ops.fine_match_grad): the gradient of mkpts*_f reaches the windows and mix_feat_0 / mix_feat_1.
+        Otherwise the plain kernel call, as under no_grad."""
         M, WW, C = feat_f0.shape
         W = int(math.sqrt(WW))
         scale = data['hw0_i'][0] / data['hw0_f'][0]
@@ -239,6 +246,11 @@ class FineMatching(nn.Module):
             data.update({'expec_f': torch.empty(0, 3, device=feat_f0.device),
                          'mkpts0_f': data['mkpts0_c'], 'mkpts1_f': data['mkpts1_c']})
             return
-        k0, k1 = ops.fine_match(feat_f0, feat_f1, self._mix(self.mix_feat_0), self._mix(self.mix_feat_1),
-                                data['mkpts0_c'], data['mkpts1_c'], scale)
+        if torch.is_grad_enabled() and (self.training or feat_f0.requires_grad or feat_f1.requires_grad):
+            mix = [torch.cat([lin.weight.view(-1), lin.bias]) for lin in (self.mix_feat_0, self.mix_feat_1)]
+            k0, k1 = ops.fine_match_grad(feat_f0, feat_f1, mix[0], mix[1], data['mkpts0_c'], data['mkpts1_c'], scale)
+        else:
+            with torch.no_grad():
+                k0, k1 = ops.fine_match(feat_f0, feat_f1, self._mix(self.mix_feat_0), self._mix(self.mix_feat_1),
+                                        data['mkpts0_c'], data['mkpts1_c'], scale)
         data.update({"mkpts0_f": k0, "mkpts1_f": k1})

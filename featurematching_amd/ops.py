@@ -643,6 +643,108 @@ def fine_match(win0: torch.Tensor, win1: torch.Tensor, mix0: torch.Tensor, mix1:
     return out0, out1
 
 
+def _aligned_workspace(nbytes: int, device):
+    """(buffer, 256-byte aligned address) of at least nbytes of device memory"""
+    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
+    return ws, C.c_void_p(ws.data_ptr() + (-ws.data_ptr()) % 256)
+
+
+class _FineMatch(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, win0, win1, mix0, mix1, mkpts0_c, mkpts1_c, scale_f):
+        w0, w1 = _f32c(win0, "win0"), _f32c(win1, "win1")
+        m0, m1 = _f32c(mix0, "mix0"), _f32c(mix1, "mix1")
+        k0, k1 = fine_match(w0, w1, m0, m1, mkpts0_c, mkpts1_c, scale_f)
+        ctx.save_for_backward(w0, w1, m0, m1)
+        ctx.scale_f = float(scale_f)
+        ctx.dtypes = (win0.dtype, win1.dtype, mix0.dtype, mix1.dtype)
+        return k0, k1
+
+    @staticmethod
+    def backward(ctx, g0, g1):
+        w0, w1, m0, m1 = ctx.saved_tensors
+        lib = _lib.load()
+        m_max, ww, cf = w0.shape
+        dev = w0.device
+        g0 = torch.zeros(m_max, 3, dtype=torch.float32, device=dev) if g0 is None else _f32c(g0, "grad")
+        g1 = torch.zeros(m_max, 3, dtype=torch.float32, device=dev) if g1 is None else _f32c(g1, "grad")
+        d_w0, d_w1 = torch.zeros_like(w0), torch.zeros_like(w1)
+        d_m0, d_m1 = torch.zeros_like(m0), torch.zeros_like(m1)
+        if m_max > 0:
+            need = int(lib.fm_fine_match_backward_workspace_bytes(m_max, ww))
+            ws, wsp = _aligned_workspace(need, dev)
+            _lib.check(lib.fm_fine_match_backward(_ptr(w0), _ptr(w1), m_max, None, ww, cf, _ptr(m0), _ptr(m1), ctx.scale_f,
+                                                  _ptr(g0), _ptr(g1), wsp, need, _ptr(d_w0), _ptr(d_w1), _ptr(d_m0),
+                                                  _ptr(d_m1), _stream(dev)), "fm_fine_match_backward")
+            d_w0._keep = (ws, g0, g1)
+        t0, t1, t2, t3 = ctx.dtypes
+        return d_w0.to(t0), d_w1.to(t1), d_m0.to(t2), d_m1.to(t3), g0[:, :2], g1[:, :2], None
+
+
+def fine_match_grad(win0: torch.Tensor, win1: torch.Tensor, mix0: torch.Tensor, mix1: torch.Tensor,
+                    mkpts0_c: torch.Tensor, mkpts1_c: torch.Tensor, scale_f: float):
+    """fine_match as a differentiable function of the windows, the position-mix parameters mix0 / mix1 ([WW+1] =
+    weight, bias) and the coarse keypoints: the forward is fine_match itself, the backward fm_fine_match_backward
+    (HIP, deterministic).  Cf = 64, WW in {25, 49}."""
+    return _FineMatch.apply(win0, win1, mix0, mix1, mkpts0_c, mkpts1_c, scale_f)
+
+
+def _crop_layout(feat_f: torch.Tensor) -> int:
+    """the layout gather_windows reads a map in: 0 = NCHW (also for any other strides: it copies), 1 = channels-last"""
+    if feat_f.is_contiguous():
+        return 0
+    return 1 if feat_f.is_contiguous(memory_format=torch.channels_last) else 0
+
+
+def gather_windows_backward(d_win: torch.Tensor, b_ids: torch.Tensor, ids: torch.Tensor, shape, w: int, stride: int,
+                            w_c: int, h_c: int, pad: int = 2, layout: int = 0) -> torch.Tensor:
+    """The adjoint of gather_windows (fm_gather_windows_backward): d_feat float32 of the logical shape [N, Cf, Hf, Wf]
+    (stored channels-last for layout 1), the sum of d_win over every (match, window position) that read each pixel, in
+    a fixed order (bitwise reproducible)."""
+    lib = _lib.load()
+    n, cf, hf, wf = shape
+    dev = d_win.device
+    mf = torch.channels_last if layout == 1 else torch.contiguous_format
+    d_feat = torch.empty(n, cf, hf, wf, dtype=torch.float32, device=dev, memory_format=mf)
+    m_max = int(b_ids.shape[0])
+    if m_max == 0:
+        return d_feat.zero_()
+    g = _f32c(d_win, "d_win")
+    b64 = lambda t: t.to(torch.int64).contiguous()
+    bb, ii = b64(b_ids), b64(ids)
+    need = int(lib.fm_gather_windows_backward_workspace_bytes(n, int(h_c), int(w_c), m_max))
+    ws, wsp = _aligned_workspace(need, dev)
+    _lib.check(lib.fm_gather_windows_backward(_ptr(g), _ptr(bb), _ptr(ii), None, m_max, n, cf, hf, wf, layout, w, stride,
+                                              pad, int(h_c), int(w_c), wsp, need, _ptr(d_feat), _stream(dev)),
+               "fm_gather_windows_backward")
+    d_feat._keep = (ws, g, bb, ii)
+    return d_feat
+
+
+class _GatherWindows(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, feat_f, b_ids, ids, w, stride, w_c, h_c, pad, cells):
+        out = gather_windows(feat_f, b_ids, ids, w, stride, w_c, pad=pad, cells=cells, h_c=h_c)
+        ctx.save_for_backward(b_ids, ids)
+        ctx.args = (tuple(feat_f.shape), w, stride, w_c, h_c, pad, _crop_layout(feat_f), feat_f.dtype)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad):
+        b_ids, ids = ctx.saved_tensors
+        shape, w, stride, w_c, h_c, pad, layout, dtype = ctx.args
+        d = gather_windows_backward(grad, b_ids, ids, shape, w, stride, w_c, h_c, pad, layout)
+        return d.to(dtype), None, None, None, None, None, None, None, None
+
+
+def gather_windows_grad(feat_f: torch.Tensor, b_ids: torch.Tensor, ids: torch.Tensor, w: int, stride: int, w_c: int,
+                        h_c: int, pad: int = 2, cells=None) -> torch.Tensor:
+    """gather_windows as a differentiable function of the fine map: the forward is gather_windows itself, the backward
+    fm_gather_windows_backward (HIP; the gradient is cast to the map's dtype, in the map's layout).  h_c = rows of the
+    coarse grid (the backward's CSR of matches per cell)."""
+    return _GatherWindows.apply(feat_f, b_ids, ids, w, stride, w_c, h_c, pad, cells)
+
+
 def _map_layout(t: torch.Tensor):
     """(tensor, layout) of a logical [N,Cf,Hf,Wf] fine map: 0 = NCHW-contiguous, 1 = channels-last storage.  float32,
     float16 and bfloat16 maps are taken as they are (fm_fine_match_maps_dtype: no up-cast pass)."""

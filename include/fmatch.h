@@ -327,6 +327,47 @@ int fm_fine_match(const float* win0, const float* win1, int m_max, const int32_t
                   float* out0, float* out1, void* stream);
 
 /*
+ * Training surface of the fine stage (the gradient of fine_matching_new.py:50-79 and of the crop,
+ * fine_preprocess.py:43-50).  float32 arithmetic, no float atomics: both calls are bitwise reproducible.
+ *
+ *   fm_fine_match_backward : the gradient of fm_fine_match.  d_out0 / d_out1 [dev] float32 [m_max, 3] = dL/d out0 /
+ *                            out1.  Per direction (0 shown; 1 swaps the windows), t = 1/sqrt(64), g = d_out0[m],
+ *                            Wh = W/2, (gx, gy) = the normalised kornia grid, h = the forward's heat map (recomputed
+ *                            with the forward's arithmetic), co / var its expectation and variance:
+ *                              dvar_k = g[2] / (2 sqrt(var_k)) if var_k >= 1e-10 else 0,  dco_k = g[k] Wh scale_f - 2 co_k dvar_k
+ *                              ds[r] = h[r] (dh[r] - sum h dh),  dh = dco_x gx + dco_y gy + dvar_x gx^2 + dvar_y gy^2
+ *                              dq = t sum_r ds[r] win1[r,:];  d_win1[r,:] += t ds[r] q;  d_win0[r,:] += mix0[r] dq
+ *                              d_mix0[r] = sum_m dq . win0[r,:],  d_mix0[WW] = sum_m sum_c dq
+ *                            Outputs d_win0 / d_win1 [m_max, WW, Cf], d_mix0 / d_mix1 [WW+1] (weights, then bias), all
+ *                            float32 [dev].  Rows at or beyond min(*d_count, m_max) (d_count may be NULL) get zero
+ *                            gradients.  d_mix is reduced from per-match partials in a fixed order.  workspace:
+ *                            fm_fine_match_backward_workspace_bytes(m_max, WW) bytes [dev], 256-byte aligned.
+ *                            Cf = 64, WW in {25, 49} (else FM_E_UNSUPPORTED); m_max = 0: returns at once, nothing written.
+ *   fm_gather_windows_backward : the adjoint of fm_gather_windows.  d_win [dev] float32 [m_max, W*W, Cf]; b_ids / ids as
+ *                            in the crop; h_c, w_c = the coarse grid.  d_feat [dev] float32 [N, Cf, Hf, Wf] in `layout`
+ *                            (0 = NCHW, 1 = channels-last): EVERY element is written, pixel (y, x) of sample b gets the
+ *                            sum of d_win over every (match, window position) that read it, 0 where no window reads.
+ *                            Window positions in the padding contribute nothing; rows whose (b, id) lies outside
+ *                            [0, N) x [0, h_c*w_c) read nothing and are skipped.  Gather form (a CSR of matches per
+ *                            (b, cell) in the workspace; each pixel sums its covering cells in row-major order and each
+ *                            cell's matches in ascending index).  workspace: fm_gather_windows_backward_workspace_bytes
+ *                            bytes [dev], 256-byte aligned.  Any Cf <= 512, W <= 15 (else FM_E_UNSUPPORTED); m_max = 0:
+ *                            returns at once, d_feat untouched.
+ * Statuses: FM_E_NULL (a required pointer is NULL; d_count may be NULL), FM_E_SHAPE (m_max < 0, non-positive sizes),
+ * FM_E_UNSUPPORTED, FM_E_WORKSPACE (too small or misaligned), or a hipError_t.  The *_workspace_bytes functions return 0
+ * for invalid sizes.
+ */
+size_t fm_fine_match_backward_workspace_bytes(int m_max, int WW);
+int fm_fine_match_backward(const float* win0, const float* win1, int m_max, const int32_t* d_count, int WW, int Cf,
+                           const float* mix0, const float* mix1, float scale_f, const float* d_out0, const float* d_out1,
+                           void* workspace, size_t workspace_bytes, float* d_win0, float* d_win1, float* d_mix0,
+                           float* d_mix1, void* stream);
+size_t fm_gather_windows_backward_workspace_bytes(int N, int h_c, int w_c, int m_max);
+int fm_gather_windows_backward(const float* d_win, const int64_t* b_ids, const int64_t* ids, const int32_t* d_count,
+                               int m_max, int N, int Cf, int Hf, int Wf, int layout, int W, int stride, int pad, int h_c,
+                               int w_c, void* workspace, size_t workspace_bytes, float* d_feat, void* stream);
+
+/*
  * Window crop + fine stage in one call, straight from the fine maps (fine_preprocess.py:43-50 with the plain
  * windows, then fine_matching_new.py:50-79): for callers without fine-level context layers between the two.  The
  * window tensors never exist: with channels-last maps (layout 1: [N,Hf,Wf,64] storage - a window row is W*256

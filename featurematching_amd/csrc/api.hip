@@ -75,22 +75,27 @@ CoarseWs coarse_layout(int N, int L, int S, int C, int slots, bool alone) {
   const size_t nblk = (rows * slots + 255) / 256;
   size_t o = 0;
   auto take = [&](size_t bytes) { size_t at = o; o = align256(o + bytes); return at; };
+  auto since = [&](size_t at) { return Span{at, o - at}; };      // what was taken from `at` on
   // ---- the common path ----
-  w.zero_begin = o;
   w.cand_count = take(rows * 4);
   w.ccand_count = take(cols * 4);
   w.cand_count_b = take(rows * 4);
   w.ccand_count_b = take(cols * 4);
   w.dense_cnt = take((size_t)N * 4);
+  w.counters[0] = since(w.cand_count);
   w.cell0 = take(rows * 4);
   w.cell1 = take(cols * 4);
   w.ties0 = take((kTieCap + 1) * 4);
   w.ties1 = take((kTieCap + 1) * 4);
+  w.reassign[0] = since(w.cell0);
   w.rowmax_u = take(rows * 4);
   w.colmax_u = take(cols * 4);
   w.blocktot = take(nblk * 4);
+  w.reassign[1] = since(w.blocktot);
   w.scalars = take(sizeof(Scalars));
-  w.zero_end = o;
+  w.reassign[2] = Span{w.scalars, sizeof(Scalars::flags)};     // (dense_units stays: the dense kernels read it)
+  w.counters[1] = Span{w.scalars, sizeof(Scalars)};
+  w.prep_zero = since(w.cand_count);
   w.q0 = take(rows * C); w.q1 = take(cols * C);
   w.sigimg = take((size_t)N * 2 * 4);
   w.imgstat = take((size_t)N * 8 * 4);
@@ -155,29 +160,79 @@ static bool valid_slots(int s) { return s >= 4 && s <= 64 && (s & (s - 1)) == 0;
 constexpr int kKnownModes = FM_MODE_DENSE | FM_MODE_EXACT_SCREENING | FM_MODE_NO_CELL_MAPS | FM_MODE_EXACT_STEP | FM_MODE_STATS |
                             FM_MODE_FLAT | FM_MODE_ALONE;
 
-static bool needs_dense_region(int mode, bool want_conf) {
-  return want_conf || (mode & (FM_MODE_DENSE | FM_MODE_EXACT_SCREENING | FM_MODE_STATS | FM_MODE_FLAT)) != 0;
+static int check_coarse_shape(int N, int L, int S, int C, int cand_slots) {
+  if (N <= 0 || L <= 0 || S <= 0) return FM_E_SHAPE;
+  if (!valid_channels(C) || !valid_slots(cand_slots)) return FM_E_UNSUPPORTED;
+  return FM_OK;
+}
+
+// The checks of an entry point that works on a coarse workspace (its pointers, then the shape), then the layout.
+static int checked_layout(bool have_ptrs, int N, int L, int S, int C, int cand_slots, CoarseWs* w) {
+  if (!have_ptrs) return FM_E_NULL;
+  if (const int bad = check_coarse_shape(N, L, S, C, cand_slots)) return bad;
+  *w = coarse_layout(N, L, S, C, cand_slots);
+  return FM_OK;
+}
+
+// Everything a coarse call decides from its mode bits, from whether the dense conf_matrix is wanted and from its
+// candidate slots: which launches coarse_match_impl enqueues, with which switches, and how much workspace they need.
+struct CoarsePlan {
+  bool alone;          // FM_MODE_ALONE: launch geometry only
+  bool exact_step;     // prep finds the images' largest |x| first (one small kernel) and the int8 step from them
+  bool flat;           // prep writes every sample's float16 planes and k_stab stands in for the screening kernel
+  bool allow_dead;     // dead-row certificates: only when nobody reads every row's denominator
+  bool prep_f16;       // the float16 planes of the flagged samples; f16_force 1: of every sample, 2: hi planes of the
+  int f16_force;       // other samples too (the conf sweep alone wants them)
+  bool dense;          // the dense sum kernel redoes the flagged samples; the workspace's dense region
+  float list_cap;      // the dense kernels list candidates down to min(thr, list_cap)
+  bool reduce;         // k_reduce_sums: the softmax denominators of EVERY row and column
+  bool rescreen;       // the exact re-screening sweep
+  bool exact_lists;    // k_exact_lists: the dense kernel's lists and their denominators made exact together
+  bool conf;           // the dense conf_matrix sweep and its patch
+  bool cell_maps;      // the assignment writes the cell -> match maps
+  SelectFlags select() const { return {rescreen, dense, cell_maps, reduce}; }
+  size_t workspace_bytes(const CoarseWs& w) const { return dense ? w.total : w.common_total; }
+};
+
+static CoarsePlan plan_coarse(int mode, bool conf, int cand_slots) {
+  const bool all_rows = conf || (mode & FM_MODE_STATS) != 0;    // the statistics of EVERY row and column are read
+  CoarsePlan p;
+  p.alone = (mode & FM_MODE_ALONE) != 0;
+  p.exact_step = (mode & FM_MODE_EXACT_STEP) != 0;
+  // (the FM_MODE_FLAT hint is not taken when every row is read: their exact rewrite reads the screening kernel's lists)
+  p.flat = (mode & FM_MODE_FLAT) != 0 && !all_rows;
+  p.allow_dead = !all_rows;
+  // (the exact screening and the conf_matrix sweep read the float16 planes too)
+  p.dense = all_rows || (mode & (FM_MODE_DENSE | FM_MODE_EXACT_SCREENING | FM_MODE_FLAT)) != 0;
+  p.prep_f16 = p.dense && !p.flat;
+  p.f16_force = (mode & FM_MODE_EXACT_SCREENING) ? 1 : (conf ? 2 : 0);
+  // (a conf_matrix request: candidates down to min(thr, 0.1) - the lists then name every entry of a dense sample with
+  // conf > 0.1, which k_exact_lists resolves from exact dot products; the assignment applies thr itself.  thr < 1)
+  p.list_cap = conf ? 0.1f : 1.f;
+  p.rescreen = (mode & FM_MODE_EXACT_SCREENING) != 0;
+  // The assignment folds the softmax denominators of its candidates from the partial sums itself.  FM_MODE_FLAT with
+  // more than the default 8 slots (rows without a peak next to peaked ones): every sample's denominators are folds of
+  // the dense kernel's 13 + 19 partials, and the assignment would redo them for every candidate and every competing row
+  // - 35 us at 16 slots against 21 us with one reduction launch (5 us) in front; at 8 slots the rows hold one or two
+  // candidates and the launch costs more than it saves
+  p.reduce = p.rescreen || all_rows || (p.flat && cand_slots > 8);
+  p.exact_lists = all_rows;
+  p.conf = conf;
+  p.cell_maps = (mode & FM_MODE_NO_CELL_MAPS) == 0;
+  return p;
 }
 
 extern "C" int fm_coarse_workspace_bytes_mode(int N, int L, int S, int C, int cand_slots, int mode, int want_conf_matrix,
                                               size_t* bytes) {
-  if (!bytes) return FM_E_NULL;
-  if (N <= 0 || L <= 0 || S <= 0) return FM_E_SHAPE;
-  if (!valid_channels(C) || !valid_slots(cand_slots)) return FM_E_UNSUPPORTED;
+  CoarseWs w;
+  if (const int bad = checked_layout(bytes != nullptr, N, L, S, C, cand_slots, &w)) return bad;
   if (mode & ~kKnownModes) return FM_E_UNSUPPORTED;
-  const CoarseWs w = coarse_layout(N, L, S, C, cand_slots);
-  *bytes = needs_dense_region(mode, want_conf_matrix != 0) ? w.total : w.common_total;
+  *bytes = plan_coarse(mode, want_conf_matrix != 0, cand_slots).workspace_bytes(w);
   return FM_OK;
 }
 
 extern "C" int fm_coarse_workspace_bytes(int N, int L, int S, int C, int cand_slots, size_t* bytes) {
   return fm_coarse_workspace_bytes_mode(N, L, S, C, cand_slots, FM_MODE_DENSE | FM_MODE_EXACT_SCREENING, 1, bytes);
-}
-
-static int check_coarse_shape(int N, int L, int S, int C, int cand_slots) {
-  if (N <= 0 || L <= 0 || S <= 0) return FM_E_SHAPE;
-  if (!valid_channels(C) || !valid_slots(cand_slots)) return FM_E_UNSUPPORTED;
-  return FM_OK;
 }
 
 // Diagnostic: the workspace layout (ints then byte offsets), so that tests can inspect the
@@ -188,9 +243,8 @@ static int check_coarse_shape(int N, int L, int S, int C, int cand_slots) {
 extern "C" int fm_debug_coarse_layout(int N, int L, int S, int C, int cand_slots, int64_t* out, int n_out) {
   if (!out) return FM_E_NULL;
   if (n_out < 40) return FM_E_SHAPE;
-  const int bad = check_coarse_shape(N, L, S, C, cand_slots);
-  if (bad) return bad;
-  const CoarseWs w = coarse_layout(N, L, S, C, cand_slots);
+  CoarseWs w;
+  if (const int bad = checked_layout(true, N, L, S, C, cand_slots, &w)) return bad;
   const int64_t v[41] = {w.N, w.L, w.S, w.C, w.Lp, w.Sp, w.panels, w.tiles, w.splits, w.slots,
                          (int64_t)w.cand_count, (int64_t)w.ccand_count, (int64_t)w.scalars, (int64_t)w.blocktot,
                          (int64_t)w.hi0, (int64_t)w.lo0, (int64_t)w.hi1, (int64_t)w.lo1, (int64_t)w.q0,
@@ -215,12 +269,73 @@ extern "C" int fm_coarse_match(const float* feat0, const float* feat1, int N, in
                                j_ids, mkpts0_c, mkpts1_c, mconf, cap, d_count, conf_matrix, stream);
 }
 
+template <int K>
+static hipError_t clear_spans(char* base, const Span (&spans)[K], hipStream_t st) {
+  for (const Span& s : spans) {
+    const hipError_t e = hipMemsetAsync(base + s.at, 0, s.bytes, st);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+// Enqueues the plan of (mode, conf_matrix, cand_slots) top to bottom.  resume (fm_coarse_match_auto): a call with the
+// same arguments on the common path - mode without FM_MODE_DENSE, the only plan whose screening reports flat similarity -
+// reported just that; its prep, max pass and screening results are in the workspace, so what its assignment left is
+// cleared and the plan of mode | FM_MODE_DENSE continues from the float16 planes.
 static int coarse_match_impl(const void* feat0, const void* feat1, int in_dtype, int N, int L, int S, int C,
                              int h0c, int w0c, int h1c, int w1c, float temperature, float thr, int border_rm,
                              float scale_px, const float* scale0, const float* scale1, void* workspace,
                              size_t workspace_bytes, int cand_slots, int mode, int64_t* b_ids,
                              int64_t* i_ids, int64_t* j_ids, float* mkpts0_c, float* mkpts1_c, float* mconf,
-                             int cap, int32_t* d_count, float* conf_matrix, const MapCopyJob* job, void* stream);
+                             int cap, int32_t* d_count, float* conf_matrix, const MapCopyJob* job, void* stream,
+                             bool resume) {
+  if (!feat0 || !feat1 || !workspace || !d_count) return FM_E_NULL;
+  if (in_dtype != FM_F32 && in_dtype != FM_F16 && in_dtype != FM_BF16) return FM_E_UNSUPPORTED;
+  if (cap > 0 && (!b_ids || !i_ids || !j_ids || !mkpts0_c || !mkpts1_c || !mconf)) return FM_E_NULL;
+  if (cap < 0 || L != h0c * w0c || S != h1c * w1c) return FM_E_SHAPE;
+  if (const int bad = check_coarse_shape(N, L, S, C, cand_slots)) return bad;
+  if (!(thr > 0.f) || !(thr < 1.f) || !(temperature > 0.f)) return FM_E_UNSUPPORTED;
+  if (mode & ~kKnownModes) return FM_E_UNSUPPORTED;
+  const CoarsePlan p = plan_coarse(mode, conf_matrix != nullptr, cand_slots);
+  const CoarseWs w = coarse_layout(N, L, S, C, cand_slots, p.alone);
+  if (workspace_bytes < p.workspace_bytes(w) || ((uintptr_t)workspace & 255)) return FM_E_WORKSPACE;
+  char* base = (char*)workspace;
+  hipStream_t st = (hipStream_t)stream;
+  const float inv_ct = 1.0f / ((float)C * temperature);
+  const float thr_list = fminf(thr, p.list_cap);     // candidate threshold of the dense kernels' LISTS
+#define FM_TRY(call) do { const hipError_t e_ = (call); if (e_ != hipSuccess) return (int)e_; } while (0)
+  if (!resume) {
+    // The common path is four launches: prep -> max pass -> sparse sum kernel -> assignment.
+    // prep: clear the per-call counters, quantise both images (one int8 step per image), L1 norms
+    FM_TRY(launch_prep(feat0, feat1, in_dtype, C, w, base, p.exact_step, p.flat, st));
+    // max pass: row / column / unit maxima of the integer screening product (atomicMax: no partials, no reduction kernel)
+    FM_TRY(launch_max_i8(w, base, st));
+    // sparse sum kernel: stabilisers, live units, exact terms of the few significant entries, candidates (listed per row
+    // and per column); flags the samples with too many significant entries per unit (flat similarity).  FM_MODE_FLAT:
+    // the sweep would only find that out again - a small kernel forms the stabilisers and flags every sample
+    if (p.flat) FM_TRY(launch_stab(w, base, inv_ct, thr, p.allow_dead, st));
+    else FM_TRY(launch_screen(feat0, feat1, in_dtype, C, w, base, inv_ct, thr, p.dense, p.allow_dead, st));
+  } else {
+    FM_TRY(clear_spans(base, w.reassign, st));
+  }
+  if (p.prep_f16) FM_TRY(launch_prep_f16(feat0, feat1, in_dtype, C, w, base, p.f16_force, st));
+  // (the dense sum kernel redoes the flagged samples - one arithmetic per sample keeps exact conf ties exact - and exits
+  // at once when there are none)
+  if (p.dense) FM_TRY(launch_dense(w, base, inv_ct, thr_list, st));
+  if (p.reduce) FM_TRY(launch_reduce(w, base, inv_ct, st));
+  // (exits immediately unless the sum kernels' screening overflowed a row's slots)
+  if (p.rescreen) FM_TRY(launch_dense(w, base, inv_ct, thr_list, st, nullptr, 1));
+  if (p.exact_lists) FM_TRY(launch_exact_lists(w, base, inv_ct, feat0, feat1, in_dtype, C, st));
+  if (p.conf) {
+    // dense data['conf_matrix'] (one more sweep), whose hi/lo-split products carry 22 bits: the entries that matter are
+    // rewritten from their exact float32 dot products (the rows' lists of significant entries)
+    FM_TRY(launch_dense(w, base, inv_ct, thr, st, conf_matrix));
+    FM_TRY(launch_conf_patch(w, base, inv_ct, conf_matrix, st));
+  }
+#undef FM_TRY
+  return (int)launch_select(w, base, h0c, w0c, h1c, w1c, inv_ct, thr, border_rm, scale_px, scale0, scale1, b_ids, i_ids,
+                            j_ids, mkpts0_c, mkpts1_c, mconf, cap, d_count, p.select(), st, job);
+}
 
 extern "C" int fm_coarse_match_dtype(const void* feat0, const void* feat1, int in_dtype, int N, int L, int S, int C,
                                      int h0c, int w0c, int h1c, int w1c, float temperature, float thr, int border_rm,
@@ -230,7 +345,7 @@ extern "C" int fm_coarse_match_dtype(const void* feat0, const void* feat1, int i
                                      int cap, int32_t* d_count, float* conf_matrix, void* stream) {
   return coarse_match_impl(feat0, feat1, in_dtype, N, L, S, C, h0c, w0c, h1c, w1c, temperature, thr, border_rm, scale_px,
                            scale0, scale1, workspace, workspace_bytes, cand_slots, mode, b_ids, i_ids, j_ids, mkpts0_c,
-                           mkpts1_c, mconf, cap, d_count, conf_matrix, nullptr, stream);
+                           mkpts1_c, mconf, cap, d_count, conf_matrix, nullptr, stream, false);
 }
 
 // fm_coarse_match_dtype + the channels-last copy of image 1's fine map as a side job of the assignment launch
@@ -248,98 +363,7 @@ extern "C" int fm_coarse_match_maps(const void* feat0, const void* feat1, int in
   const MapCopyJob job{feat_f1, (float*)scratch1, Nf, Hf1, Wf1};
   return coarse_match_impl(feat0, feat1, in_dtype, N, L, S, C, h0c, w0c, h1c, w1c, temperature, thr, border_rm, scale_px,
                            scale0, scale1, workspace, workspace_bytes, cand_slots, mode, b_ids, i_ids, j_ids, mkpts0_c,
-                           mkpts1_c, mconf, cap, d_count, conf_matrix, &job, stream);
-}
-
-static int coarse_match_impl(const void* feat0, const void* feat1, int in_dtype, int N, int L, int S, int C,
-                             int h0c, int w0c, int h1c, int w1c, float temperature, float thr, int border_rm,
-                             float scale_px, const float* scale0, const float* scale1, void* workspace,
-                             size_t workspace_bytes, int cand_slots, int mode, int64_t* b_ids,
-                             int64_t* i_ids, int64_t* j_ids, float* mkpts0_c, float* mkpts1_c, float* mconf,
-                             int cap, int32_t* d_count, float* conf_matrix, const MapCopyJob* job, void* stream) {
-  if (!feat0 || !feat1 || !workspace || !d_count) return FM_E_NULL;
-  if (in_dtype != FM_F32 && in_dtype != FM_F16 && in_dtype != FM_BF16) return FM_E_UNSUPPORTED;
-  if (cap > 0 && (!b_ids || !i_ids || !j_ids || !mkpts0_c || !mkpts1_c || !mconf)) return FM_E_NULL;
-  if (N <= 0 || L <= 0 || S <= 0 || cap < 0 || L != h0c * w0c || S != h1c * w1c) return FM_E_SHAPE;
-  if (!valid_channels(C) || !valid_slots(cand_slots)) return FM_E_UNSUPPORTED;
-  if (!(thr > 0.f) || !(thr < 1.f) || !(temperature > 0.f)) return FM_E_UNSUPPORTED;
-  if (mode & ~kKnownModes) return FM_E_UNSUPPORTED;
-  const bool exact = (mode & FM_MODE_EXACT_SCREENING) != 0;
-  const bool dense = needs_dense_region(mode, conf_matrix != nullptr);      // exact screening and conf_matrix read the planes too
-  const CoarseWs w = coarse_layout(N, L, S, C, cand_slots, (mode & FM_MODE_ALONE) != 0);
-  if (workspace_bytes < (dense ? w.total : w.common_total) || ((uintptr_t)workspace & 255)) return FM_E_WORKSPACE;
-  char* base = (char*)workspace;
-  hipStream_t st = (hipStream_t)stream;
-  const float inv_ct = 1.0f / ((float)C * temperature);
-  const float thr_list = conf_matrix ? fminf(thr, 0.1f) : thr;      // candidate threshold of the dense kernels' LISTS
-
-  // The common path is four launches: prep -> max pass -> sparse sum kernel -> assignment.
-  // one dispatch: clear the per-call counters, quantise both images (one int8 step per image), L1 norms
-  // (FM_MODE_EXACT_STEP: the images' largest |x| first - a memset node and one small kernel - and the int8 step from them)
-  // (FM_MODE_FLAT: the float16 planes of every sample too - the dense sum kernel will want them all)
-  // (a hint: not taken when the dense conf_matrix / the softmax statistics are wanted - their exact rewrite reads the
-  // screening kernel's lists)
-  const bool flat = (mode & FM_MODE_FLAT) != 0 && !conf_matrix && !(mode & FM_MODE_STATS);
-  hipError_t e = launch_prep(feat0, feat1, in_dtype, C, w, base, (mode & FM_MODE_EXACT_STEP) ? 1 : 0, flat ? 1 : 0, st);
-  if (e != hipSuccess) return (int)e;
-  // max pass: row / column / unit maxima of the integer screening product (atomicMax: no partials, no reduction kernel)
-  e = launch_max_i8(w, base, st);
-  if (e != hipSuccess) return (int)e;
-  // sparse sum kernel: stabilisers, live units, exact terms of the few significant entries, candidates (listed per row
-  // and per column); flags the samples with too many significant entries per unit (flat similarity)
-  // (dead-row certificates only when nobody reads every row's denominator: the dense conf_matrix does)
-  const bool stats = (mode & FM_MODE_STATS) != 0;      // the softmax statistics of EVERY row and column are wanted
-  // (FM_MODE_FLAT: the caller expects flat similarity everywhere - the sweep would only find that out again; a small
-  // kernel forms the stabilisers and flags every sample for the dense sum kernel)
-  if (flat) e = launch_stab(w, base, inv_ct, thr, (conf_matrix || stats) ? 0 : 1, st);
-  else e = launch_screen(feat0, feat1, in_dtype, C, w, base, inv_ct, thr, dense ? 1 : 0, (conf_matrix || stats) ? 0 : 1, st);
-  if (e != hipSuccess) return (int)e;
-  if (dense && !flat) {
-    // float16 hi / lo planes for the samples that go on to the dense kernel (all of them when the exact screening or
-    // the conf_matrix sweep will run); exits at once otherwise
-    e = launch_prep_f16(feat0, feat1, in_dtype, C, w, base, exact ? 1 : (conf_matrix ? 2 : 0), st);
-    if (e != hipSuccess) return (int)e;
-  }
-  if (dense) {
-    // dense sum kernel (float32-equivalent hi/lo product on the matrix cores): redoes the samples in which the sparse
-    // kernel flagged units (one arithmetic per sample keeps exact conf ties exact); exits at once when there are none
-    // (a conf_matrix request: candidates down to min(thr, 0.1) - the lists then name every entry of a dense sample with
-    // conf > 0.1, which k_exact_lists resolves from exact dot products; the assignment applies thr itself)
-    e = launch_dense(w, base, inv_ct, thr_list, st);
-    if (e != hipSuccess) return (int)e;
-  }
-  // The assignment folds the softmax denominators of its candidates from the partial sums itself.  The
-  // denominators / log-softmax offsets of EVERY row and column are only needed by the exact screening and by the
-  // dense conf_matrix:
-  // (FM_MODE_FLAT with more than the default 8 candidate slots - rows without a peak next to peaked ones: every sample's
-  // denominators are folds of the dense kernel's 13 + 19 partials, and the assignment would redo them for every
-  // candidate and every competing row - 35 us at 16 slots against 21 us with one reduction launch (5 us) in front; at 8
-  // slots the rows hold one or two candidates and the launch costs more than it saves)
-  const bool reduced = exact || conf_matrix || stats || (flat && cand_slots > 8);   // (the assignment then reads the folded denominators)
-  if (reduced) {
-    e = launch_reduce(1, w, base, inv_ct, st);
-    if (e != hipSuccess) return (int)e;
-  }
-  if (exact) {                 // exits immediately unless the sum kernels' screening overflowed a row's slots
-    e = launch_dense(w, base, inv_ct, thr_list, st, nullptr, 1);
-    if (e != hipSuccess) return (int)e;
-  }
-  if ((conf_matrix || stats) && dense) {  // every entry is read: the dense kernel's lists and their denominators made exact together
-    e = launch_exact_lists(w, base, inv_ct, feat0, feat1, in_dtype, C, st);
-    if (e != hipSuccess) return (int)e;
-  }
-  if (conf_matrix) {           // dense data['conf_matrix'] on request (one more sweep)
-    e = launch_dense(w, base, inv_ct, thr, st, conf_matrix);
-    if (e != hipSuccess) return (int)e;
-    // ... whose hi/lo-split products carry 22 bits: the entries that matter are rewritten from their exact float32 dot
-    // products (the rows' lists of significant entries)
-    e = launch_conf_patch(w, base, inv_ct, conf_matrix, st);
-    if (e != hipSuccess) return (int)e;
-  }
-  e = launch_select(w, base, h0c, w0c, h1c, w1c, inv_ct, thr, border_rm, scale_px, scale0, scale1,
-                    b_ids, i_ids, j_ids, mkpts0_c, mkpts1_c, mconf, cap, d_count,
-                    (dense ? (mode | FM_MODE_DENSE) : mode) | (reduced ? FM_MODE_STATS : 0), st, job);
-  return (int)e;
+                           mkpts1_c, mconf, cap, d_count, conf_matrix, &job, stream, false);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -349,32 +373,7 @@ static int coarse_match_impl(const void* feat0, const void* feat1, int in_dtype,
 // the host sync the reference has too (torch.where, :109); what is left for the caller is FM_E_CAPACITY (its output
 // buffers are too small: *m_out = the capacity needed), FM_E_RANGE (bad input) and argument errors.
 // ---------------------------------------------------------------------------------------------------------------------
-namespace {
 constexpr int kAutoDataModes = FM_MODE_DENSE | FM_MODE_EXACT_SCREENING | FM_MODE_EXACT_STEP | FM_MODE_FLAT;
-
-// FM_E_DENSE after a call on the common path: the max pass, the screening kernel's lists and its per-sample flags in
-// the workspace are all valid - what is missing is the dense sum kernel's work on the flagged samples and an
-// assignment that reads it.  Continue from there instead of repeating prep, max pass and screening.
-int resume_with_dense(const void* feat0, const void* feat1, int in_dtype, int C, const CoarseWs& w, char* base,
-                      int h0c, int w0c, int h1c, int w1c, float inv_ct, float thr, int border_rm, float scale_px,
-                      const float* scale0, const float* scale1, int64_t* b_ids, int64_t* i_ids, int64_t* j_ids,
-                      float* mkpts0_c, float* mkpts1_c, float* mconf, int cap, int32_t* d_count, int mode, hipStream_t st) {
-  // what the first assignment launch left behind: its cell maps and tie lists, the workgroup totals of its look-back;
-  // and the FM_DEV_DENSE bit (dense_units, next to it, stays: the dense kernels read it)
-  hipError_t e = hipMemsetAsync(base + w.cell0, 0, w.rowmax_u - w.cell0, st);
-  if (e != hipSuccess) return (int)e;
-  e = hipMemsetAsync(base + w.blocktot, 0, w.scalars - w.blocktot, st);
-  if (e != hipSuccess) return (int)e;
-  e = hipMemsetAsync(base + w.scalars, 0, sizeof(unsigned), st);
-  if (e != hipSuccess) return (int)e;
-  e = launch_prep_f16(feat0, feat1, in_dtype, C, w, base, 0, st);
-  if (e != hipSuccess) return (int)e;
-  e = launch_dense(w, base, inv_ct, thr, st);
-  if (e != hipSuccess) return (int)e;
-  return (int)launch_select(w, base, h0c, w0c, h1c, w1c, inv_ct, thr, border_rm, scale_px, scale0, scale1, b_ids, i_ids,
-                            j_ids, mkpts0_c, mkpts1_c, mconf, cap, d_count, mode | FM_MODE_DENSE, st, nullptr);
-}
-}  // namespace
 
 extern "C" int fm_coarse_workspace_bytes_auto(int N, int L, int S, int C, int max_cand_slots, size_t* bytes) {
   if (max_cand_slots == 0) max_cand_slots = 64;
@@ -423,18 +422,14 @@ extern "C" int fm_coarse_match_auto(const void* feat0, const void* feat1, int in
     if (st == FM_E_DENSE && !(cur & FM_MODE_DENSE) && !conf_matrix && !(mode & FM_MODE_STATS)) {
       // the common path's own results are still in the workspace: add the dense kernels' part and assign again
       cur |= FM_MODE_DENSE;
-      const CoarseWs w = coarse_layout(N, L, S, C, slots);
       // (the resume clears the WHOLE status word: only when "flat similarity" is all it holds - anything else the device
       // reported with it would be dropped, so such a call is repeated from the start instead)
-      if (workspace_bytes >= w.total && (info & ~FM_DEV_ALL_DENSE) == FM_DEV_DENSE) {
-        st = resume_with_dense(feat0, feat1, in_dtype, C, w, (char*)workspace, h0c, w0c, h1c, w1c,
-                               1.0f / ((float)C * temperature), thr, border_rm, scale_px, scale0, scale1, b_ids, i_ids, j_ids,
-                               mkpts0_c, mkpts1_c, mconf, cap, d_count, fixed | cur, (hipStream_t)stream);
-        if (st != FM_OK) return st;
-        st = fm_read_count_info(d_count, cap, &m, &info, stream);
-      } else {
-        continue;
-      }
+      if ((info & ~FM_DEV_ALL_DENSE) != FM_DEV_DENSE) continue;
+      st = coarse_match_impl(feat0, feat1, in_dtype, N, L, S, C, h0c, w0c, h1c, w1c, temperature, thr, border_rm, scale_px,
+                             scale0, scale1, workspace, workspace_bytes, slots, fixed | cur, b_ids, i_ids, j_ids, mkpts0_c,
+                             mkpts1_c, mconf, cap, d_count, conf_matrix, nullptr, stream, true);
+      if (st != FM_OK) return st;
+      st = fm_read_count_info(d_count, cap, &m, &info, stream);
     }
     if (st == FM_OK) break;
     if (st == FM_E_STEP && !(cur & FM_MODE_EXACT_STEP)) { cur |= FM_MODE_EXACT_STEP; continue; }
@@ -477,10 +472,10 @@ extern "C" int fm_coarse_match_auto(const void* feat0, const void* feat1, int in
 // (0 = cell unmatched; pitch = padded cells per sample).  fm_gather_windows_cells consumes them.
 extern "C" int fm_coarse_cell_maps(void* workspace, int N, int L, int S, int C, int cand_slots, int32_t** cell0,
                                    int* pitch0, int32_t** ties0, int32_t** cell1, int* pitch1, int32_t** ties1) {
-  if (!workspace || !cell0 || !cell1 || !pitch0 || !pitch1 || !ties0 || !ties1) return FM_E_NULL;
-  if (N <= 0 || L <= 0 || S <= 0) return FM_E_SHAPE;
-  if (!valid_channels(C) || !valid_slots(cand_slots)) return FM_E_UNSUPPORTED;
-  const CoarseWs w = coarse_layout(N, L, S, C, cand_slots);
+  CoarseWs w;
+  if (const int bad = checked_layout(workspace && cell0 && cell1 && pitch0 && pitch1 && ties0 && ties1, N, L, S, C,
+                                     cand_slots, &w))
+    return bad;
   *cell0 = (int32_t*)((char*)workspace + w.cell0); *pitch0 = w.Lp; *ties0 = (int32_t*)((char*)workspace + w.ties0);
   *cell1 = (int32_t*)((char*)workspace + w.cell1); *pitch1 = w.Sp; *ties1 = (int32_t*)((char*)workspace + w.ties1);
   return FM_OK;
@@ -493,10 +488,10 @@ extern "C" int fm_coarse_cell_maps(void* workspace, int N, int L, int S, int C, 
 extern "C" int fm_coarse_softmax_stats(void* workspace, int N, int L, int S, int C, int cand_slots, const float** nm_r,
                                        const float** sum_r, int* pitch_r, const float** nm_c, const float** sum_c,
                                        int* pitch_c) {
-  if (!workspace || !nm_r || !sum_r || !pitch_r || !nm_c || !sum_c || !pitch_c) return FM_E_NULL;
-  const int bad = check_coarse_shape(N, L, S, C, cand_slots);
-  if (bad) return bad;
-  const CoarseWs w = coarse_layout(N, L, S, C, cand_slots);
+  CoarseWs w;
+  if (const int bad = checked_layout(workspace && nm_r && sum_r && pitch_r && nm_c && sum_c && pitch_c, N, L, S, C,
+                                     cand_slots, &w))
+    return bad;
   *nm_r = (const float*)((char*)workspace + w.nmr); *sum_r = (const float*)((char*)workspace + w.rsum); *pitch_r = w.Lp;
   *nm_c = (const float*)((char*)workspace + w.nmc); *sum_c = (const float*)((char*)workspace + w.csum); *pitch_c = w.Sp;
   return FM_OK;
@@ -508,11 +503,9 @@ extern "C" int fm_coarse_softmax_stats(void* workspace, int N, int L, int S, int
 // bracket the caller places after this function's memset is enqueued... the memset precedes the kernel).
 extern "C" int fm_debug_launch_corr(void* workspace, int N, int L, int S, int C, int cand_slots, float temperature,
                                     float thr, int mode, void* stream) {
-  if (!workspace) return FM_E_NULL;
-  const int bad = check_coarse_shape(N, L, S, C, cand_slots);
-  if (bad) return bad;
+  CoarseWs w;
+  if (const int bad = checked_layout(workspace, N, L, S, C, cand_slots, &w)) return bad;
   if (mode < 0 || mode > 2) return FM_E_UNSUPPORTED;
-  const CoarseWs w = coarse_layout(N, L, S, C, cand_slots);
   hipStream_t st = (hipStream_t)stream;
   if (mode == 0) return (int)launch_max_i8(w, (char*)workspace, st);
   if (mode == 1) return (int)launch_dense(w, (char*)workspace, 1.0f / ((float)C * temperature), thr, st);
@@ -522,10 +515,8 @@ extern "C" int fm_debug_launch_corr(void* workspace, int N, int L, int S, int C,
 // Diagnostic: launch the sparse sum kernel alone on a workspace a previous fm_coarse_match filled.
 extern "C" int fm_debug_launch_screen(void* workspace, const float* feat0, const float* feat1, int N, int L, int S,
                                           int C, int cand_slots, float temperature, float thr, void* stream) {
-  if (!workspace || !feat0 || !feat1) return FM_E_NULL;
-  const int bad = check_coarse_shape(N, L, S, C, cand_slots);
-  if (bad) return bad;
-  const CoarseWs w = coarse_layout(N, L, S, C, cand_slots);
+  CoarseWs w;
+  if (const int bad = checked_layout(workspace && feat0 && feat1, N, L, S, C, cand_slots, &w)) return bad;
   return (int)launch_screen(feat0, feat1, FM_F32, C, w, (char*)workspace, 1.0f / ((float)C * temperature), thr, 1, 1,
                                 (hipStream_t)stream);
 }
@@ -534,10 +525,8 @@ extern "C" int fm_debug_launch_screen(void* workspace, const float* feat0, const
 // before anything reads the workspace's candidate lists again).
 extern "C" int fm_debug_launch_prep(void* workspace, const float* feat0, const float* feat1, int N, int L, int S, int C,
                                     int cand_slots, void* stream) {
-  if (!workspace || !feat0 || !feat1) return FM_E_NULL;
-  const int bad = check_coarse_shape(N, L, S, C, cand_slots);
-  if (bad) return bad;
-  const CoarseWs w = coarse_layout(N, L, S, C, cand_slots);
+  CoarseWs w;
+  if (const int bad = checked_layout(workspace && feat0 && feat1, N, L, S, C, cand_slots, &w)) return bad;
   return (int)launch_prep(feat0, feat1, FM_F32, C, w, (char*)workspace, 0, 0, (hipStream_t)stream);
 }
 
@@ -545,10 +534,8 @@ extern "C" int fm_debug_launch_prep(void* workspace, const float* feat0, const f
 // kernel) on a workspace a previous fm_coarse_match filled.
 extern "C" int fm_debug_launch_prep_f16(void* workspace, const float* feat0, const float* feat1, int N, int L, int S,
                                         int C, int cand_slots, int force, void* stream) {
-  if (!workspace || !feat0 || !feat1) return FM_E_NULL;
-  const int bad = check_coarse_shape(N, L, S, C, cand_slots);
-  if (bad) return bad;
-  const CoarseWs w = coarse_layout(N, L, S, C, cand_slots);
+  CoarseWs w;
+  if (const int bad = checked_layout(workspace && feat0 && feat1, N, L, S, C, cand_slots, &w)) return bad;
   return (int)launch_prep_f16(feat0, feat1, FM_F32, C, w, (char*)workspace, force, (hipStream_t)stream);
 }
 
@@ -556,11 +543,9 @@ extern "C" int fm_debug_launch_prep_f16(void* workspace, const float* feat0, con
 // 1: k_stab) on a workspace a previous FM_MODE_FLAT call filled.
 extern "C" int fm_debug_launch_flat(void* workspace, const float* feat0, const float* feat1, int N, int L, int S, int C,
                                     int cand_slots, float temperature, float thr, int which, void* stream) {
-  if (!workspace || !feat0 || !feat1) return FM_E_NULL;
-  const int bad = check_coarse_shape(N, L, S, C, cand_slots);
-  if (bad) return bad;
+  CoarseWs w;
+  if (const int bad = checked_layout(workspace && feat0 && feat1, N, L, S, C, cand_slots, &w)) return bad;
   if (which < 0 || which > 1) return FM_E_UNSUPPORTED;
-  const CoarseWs w = coarse_layout(N, L, S, C, cand_slots);
   if (which == 0) return (int)launch_prep(feat0, feat1, FM_F32, C, w, (char*)workspace, 0, 1, (hipStream_t)stream);
   return (int)launch_stab(w, (char*)workspace, 1.0f / ((float)C * temperature), thr, 1, (hipStream_t)stream);
 }
@@ -568,13 +553,9 @@ extern "C" int fm_debug_launch_flat(void* workspace, const float* feat0, const f
 // Diagnostic: zero the candidate counters and the scalars, so that the sum kernels can be launched again on a
 // workspace whose max-pass results are kept.
 extern "C" int fm_debug_reset_counters(void* workspace, int N, int L, int S, int C, int cand_slots, void* stream) {
-  if (!workspace) return FM_E_NULL;
-  const int bad = check_coarse_shape(N, L, S, C, cand_slots);
-  if (bad) return bad;
-  const CoarseWs w = coarse_layout(N, L, S, C, cand_slots);
-  hipError_t e = hipMemsetAsync((char*)workspace + w.cand_count, 0, w.cell0 - w.cand_count, (hipStream_t)stream);
-  if (e != hipSuccess) return (int)e;
-  return (int)hipMemsetAsync((char*)workspace + w.scalars, 0, sizeof(Scalars), (hipStream_t)stream);
+  CoarseWs w;
+  if (const int bad = checked_layout(workspace, N, L, S, C, cand_slots, &w)) return bad;
+  return (int)clear_spans((char*)workspace, w.counters, (hipStream_t)stream);
 }
 
 extern "C" int fm_read_count(const int32_t* d_count, int cap, int32_t* m_out, void* stream) {

@@ -397,7 +397,7 @@ static void fill_prep_args(PrepArgs& a, const void* feat0, const void* feat1, in
   a.exact_step = 0;
   a.l1_0 = (float*)(base + w.l1_0); a.l1_1 = (float*)(base + w.l1_1);
   a.bstat0 = (float4*)(base + w.bstat0); a.bstat1 = (float4*)(base + w.bstat1);
-  a.zero = (uint4*)(base + w.zero_begin); a.zero_vec = (int)((w.zero_end - w.zero_begin) / 16);
+  a.zero = (uint4*)(base + w.prep_zero.at); a.zero_vec = (int)(w.prep_zero.bytes / 16);
   a.L = w.L; a.S = w.S; a.Lp = w.Lp; a.Sp = w.Sp; a.c_in = c_in;
   a.blocks0 = (int)((long)w.N * w.Lp / 32);
   a.dense_cnt = (const int*)(base + w.dense_cnt); a.force = 0; a.f16inv = (float*)(base + w.f16inv);
@@ -512,8 +512,7 @@ __global__ __launch_bounds__(256) void k_reduce_sums(const float* __restrict__ r
   }
 }
 
-hipError_t launch_reduce(int mode, const CoarseWs& w, char* base, float inv_ct, hipStream_t st) {
-  (void)mode;
+hipError_t launch_reduce(const CoarseWs& w, char* base, float inv_ct, hipStream_t st) {
   const int chunks = (max(w.Lp, w.Sp) + 15) / 16;
   const dim3 grid(chunks, w.N, 2);
   hipLaunchKernelGGL(k_reduce_sums, grid, dim3(256), 0, st, (const float*)(base + w.rowB), (const float*)(base + w.colB),

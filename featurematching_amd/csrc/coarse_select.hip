@@ -396,11 +396,9 @@ hipError_t launch_select(const CoarseWs& w, char* base, int h0c, int w0c,
                          int h1c, int w1c, float inv_ct, float thr, int border, float scale_px,
                          const float* scale0, const float* scale1, int64_t* b_ids, int64_t* i_ids,
                          int64_t* j_ids, float* k0, float* k1, float* mconf, int cap, int32_t* d_count,
-                         int mode, hipStream_t st, const MapCopyJob* job) {
+                         SelectFlags flags, hipStream_t st, const MapCopyJob* job) {
   SelArgs a;
-  a.exact = (mode & FM_MODE_EXACT_SCREENING) ? 1 : 0;
-  a.dense_enabled = (mode & (FM_MODE_DENSE | FM_MODE_EXACT_SCREENING)) ? 1 : 0;
-  a.cell_maps = (mode & FM_MODE_NO_CELL_MAPS) ? 0 : 1;
+  a.exact = flags.exact; a.dense_enabled = flags.dense; a.cell_maps = flags.cell_maps; a.sums_ready = flags.sums_ready;
   a.nmr = (const float*)(base + w.nmr); a.nmc = (const float*)(base + w.nmc);
   a.rowB = (const float*)(base + w.rowB); a.colB = (const float*)(base + w.colB);
   a.cand_count = (const int*)(base + w.cand_count); a.cand_j = (const int*)(base + w.cand_j);
@@ -413,7 +411,6 @@ hipError_t launch_select(const CoarseWs& w, char* base, int h0c, int w0c,
   a.ccand_x_b = (const float*)(base + w.ccand_x_b);
   a.dense_cnt = (const int*)(base + w.dense_cnt);
   a.rsum = (const float*)(base + w.rsum); a.csum = (const float*)(base + w.csum);
-  a.sums_ready = (mode & (FM_MODE_EXACT_SCREENING | FM_MODE_STATS)) ? 1 : 0;     // (the caller ORs FM_MODE_STATS in whenever k_reduce_sums ran)
   a.blocktot = (int*)(base + w.blocktot);
   a.scal = (Scalars*)(base + w.scalars);
   a.N = w.N; a.L = w.L; a.S = w.S; a.C = w.C; a.Lp = w.Lp; a.Sp = w.Sp; a.splits = w.splits; a.splits_s = w.splits_s; a.panels = w.panels;

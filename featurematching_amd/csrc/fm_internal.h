@@ -29,6 +29,8 @@ inline int padded_channels(int c) { return c <= 64 ? 64 : (c <= 128 ? 128 : 256)
 inline bool valid_channels(int c) { return c >= 4 && c <= 256 && c % 4 == 0; }
 inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 
+struct Span { size_t at, bytes; };           // bytes [at, at + bytes) of a workspace
+
 // Device workspace of the coarse stage; all offsets in bytes from the base.  The regions the common path uses come
 // first (`common_total` bytes); the float16 planes, the dense sum kernel's partials and candidate set and the
 // softmax denominators of every row / column follow and are needed only with FM_MODE_DENSE / FM_MODE_EXACT_SCREENING /
@@ -37,8 +39,12 @@ struct CoarseWs {
   int N, L, S, C, Lp, Sp, panels, tiles, splits, slots;
   int splits0;                                // column splits of the max pass (its own grid size)
   int splits_s, units_s;                      // screening kernel: column chunks per row block and 32-column units per chunk (<= 64)
+  Span prep_zero;                             // zeroed by k_prep_split on every call: the (zeroed) fields below
+  Span reassign[3];                           // zeroed before the assignment runs again on a call's results: its cell
+                                              // maps and tie lists, its look-back totals, the status word
+  Span counters[2];                           // zeroed by fm_debug_reset_counters: the candidate counters, the scalars
   // zeroed on every call (contiguous, starts at the base)
-  size_t zero_begin, cand_count, ccand_count, cand_count_b, ccand_count_b, dense_cnt, scalars, zero_end;
+  size_t cand_count, ccand_count, cand_count_b, ccand_count_b, dense_cnt, scalars;
                                               // cand_count / ccand_count: candidates per row / per column found by the
                                               // sparse sum kernel (the same entries, listed from both sides); *_b: by
                                               // the dense one; dense_cnt [N]: units of a sample the sparse kernel left
@@ -102,15 +108,17 @@ hipError_t launch_max_i8(const CoarseWs& w, char* base, hipStream_t st);
 // rescreen: the exact re-screening of FM_MODE_EXACT_SCREENING with the same offsets)
 hipError_t launch_dense(const CoarseWs& w, char* base, float inv_ct, float thr, hipStream_t st, float* conf = nullptr,
                         int rescreen = 0);
-hipError_t launch_reduce(int mode, const CoarseWs& w, char* base, float inv_ct, hipStream_t st);
+hipError_t launch_reduce(const CoarseWs& w, char* base, float inv_ct, hipStream_t st);
 // side job of the assignment launch (fm_coarse_match_maps): channels-last copy of a float32 NCHW map, or src == NULL
 struct MapCopyJob {
   const float* src; float* dst; int N, Hf, Wf;
 };
+// what the assignment launch is told about the launches before it (SelArgs: exact, dense_enabled, cell_maps, sums_ready)
+struct SelectFlags { bool exact, dense, cell_maps, sums_ready; };
 hipError_t launch_select(const CoarseWs& w, char* base, int h0c, int w0c, int h1c, int w1c, float inv_ct, float thr, int border,
                          float scale_px, const float* scale0, const float* scale1,
                          int64_t* b_ids, int64_t* i_ids, int64_t* j_ids, float* k0, float* k1,
-                         float* mconf, int cap, int32_t* d_count, int mode, hipStream_t st,
+                         float* mconf, int cap, int32_t* d_count, SelectFlags flags, hipStream_t st,
                          const MapCopyJob* job = nullptr);
 hipError_t launch_conf_patch(const CoarseWs& w, char* base, float inv_ct, float* conf, hipStream_t st);
 hipError_t launch_exact_lists(const CoarseWs& w, char* base, float inv_ct, const void* feat0, const void* feat1, int in_dtype,

@@ -238,7 +238,7 @@ extern "C" int fm_coarse_workspace_bytes(int N, int L, int S, int C, int cand_sl
 // Diagnostic: the workspace layout (ints then byte offsets), so that tests can inspect the
 // intermediate statistics of a run.  out[0..9] = N,L,S,C,Lp,Sp,panels,tiles,splits,slots;
 // out[10..] = cand_count, ccand_count, scalars, blocktot, hi0, lo0, hi1, lo1, q0, q1, sigimg, l1_0,
-// rowS, colS, rowB, colB, nmr, nmc, rsum, csum, cand_j, cand_x, ccand_i, umax, dense_cnt, rowmax_u,
+// rowS, colS (both zero-length), rowB, colB, nmr, nmc, rsum, csum, cand_j, cand_x, ccand_i, umax, dense_cnt, rowmax_u,
 // colmax_u, splits_s, units_s, total; out[40] = common_total (when n_out > 40)  (40 or 41 values).
 extern "C" int fm_debug_coarse_layout(int N, int L, int S, int C, int cand_slots, int64_t* out, int n_out) {
   if (!out) return FM_E_NULL;

@@ -661,13 +661,23 @@ __global__ __launch_bounds__(NW * 64) void k_ctx_layer(TfArgs a) {
 
 constexpr int kMaxLayers = 32;
 
-size_t ws_floats(int N, int L, int S) {
-  const size_t t0 = (size_t)N * ((L + kTok - 1) / kTok), t1 = (size_t)N * ((S + kTok - 1) / kTok);
-  size_t n = (t0 + t1) * kKvFloats + 2 * (size_t)N * kKvFloats;
+// Workspace of fm_coarse_transformer, float32, [image]: tiles of 32 tokens per sample; part [N * tiles][kKvFloats]
+// (Seg::part) | kv [N][kKvFloats] (Seg::kv) | diag: TfArgs::diag of a FM_DIAG_CTF build, else empty
+struct CtfWs { int tiles[2]; Span part[2], kv[2], diag; size_t total; };
+CtfWs ctf_layout(int N, int L, int S) {
+  CtfWs w;
+  w.tiles[0] = (L + kTok - 1) / kTok;
+  w.tiles[1] = (S + kTok - 1) / kTok;
+  size_t o = 0;
+  auto take = [&](size_t floats) { const Span s{o, floats * 4}; o += s.bytes; return s; };
+  for (int i = 0; i < 2; ++i) w.part[i] = take((size_t)N * w.tiles[i] * kKvFloats);
+  for (int i = 0; i < 2; ++i) w.kv[i] = take((size_t)N * kKvFloats);
+  w.diag = take(0);
 #ifdef FM_DIAG_CTF
-  n += (t0 + t1) * 8 * 16;
+  w.diag = take((size_t)N * (w.tiles[0] + w.tiles[1]) * 8 * 16);
 #endif
-  return n;
+  w.total = o;
+  return w;
 }
 
 }  // namespace
@@ -679,7 +689,7 @@ extern "C" size_t fm_coarse_tf_packed_bytes(int n_layers) {
 extern "C" int fm_coarse_tf_workspace_bytes(int N, int L, int S, size_t* bytes) {
   if (!bytes) return FM_E_NULL;
   if (N <= 0 || L <= 0 || S <= 0) return FM_E_SHAPE;
-  *bytes = ws_floats(N, L, S) * 4;
+  *bytes = ctf_layout(N, L, S).total;
   return FM_OK;
 }
 
@@ -744,7 +754,8 @@ extern "C" int fm_coarse_transformer_masked(const float* feat0, const float* fea
         overlap(out1, n1, feat0, n0) || overlap(out1, n1, feat1, n1))
       return FM_E_UNSUPPORTED;
   }
-  if (workspace_bytes < ws_floats(N, L, S) * 4 || ((uintptr_t)workspace & 15) || ((uintptr_t)packed & 15))
+  const CtfWs ws = ctf_layout(N, L, S);
+  if (workspace_bytes < ws.total || ((uintptr_t)workspace & 15) || ((uintptr_t)packed & 15))
     return FM_E_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   static unsigned long long set_kv = 0, set_layer = 0;
@@ -759,16 +770,10 @@ extern "C" int fm_coarse_transformer_masked(const float* feat0, const float* fea
                        : ensure_dynamic_lds(&k_ctx_layer<4>, layer_lds_bytes(4), &set_layer4);
   if (e != hipSuccess) return (int)e;
 
-  const int tl[2] = {(L + kTok - 1) / kTok, (S + kTok - 1) / kTok}, len[2] = {L, S};
-  float* part[2];
-  float* kv[2];
-  part[0] = (float*)workspace;
-  part[1] = part[0] + (size_t)N * tl[0] * kKvFloats;
-  kv[0] = part[1] + (size_t)N * tl[1] * kKvFloats;
-  kv[1] = kv[0] + (size_t)N * kKvFloats;
-#ifdef FM_DIAG_CTF
-  float* const diag = kv[1] + (size_t)N * kKvFloats;
-#endif
+  const int* const tl = ws.tiles;
+  const int len[2] = {L, S};
+  float* const part[2] = {span_ptr<float>(workspace, ws.part[0]), span_ptr<float>(workspace, ws.part[1])};
+  float* const kv[2] = {span_ptr<float>(workspace, ws.kv[0]), span_ptr<float>(workspace, ws.kv[1])};
   const float* cur[2] = {feat0, feat1};
   float* out[2] = {out0, out1};
   const unsigned char* masks[2] = {mask0, mask1};
@@ -779,7 +784,7 @@ extern "C" int fm_coarse_transformer_masked(const float* feat0, const float* fea
     a.N = N;
     a.w = w;
 #ifdef FM_DIAG_CTF
-    a.diag = diag;
+    a.diag = span_ptr<float>(workspace, ws.diag);
 #endif
     // K / V side: the SOURCE tokens
     int tiles_kv = 0;

@@ -17,6 +17,8 @@
 // gradient - the dense matrix never exists.  The supervised entries' own term 2 g c is K rows: a third, tiny kernel.
 // float32 vector arithmetic on purpose: a training-only path whose bar is the agreement with float64 autograd
 // (tests), not the matrix cores.
+#include <utility>
+
 #include "fm_device.h"
 
 namespace fm {
@@ -444,8 +446,6 @@ static int dsm_zsplit(int N, int R) {
 
 using namespace fm;
 
-static bool dsm_shape_ok(int N, int L, int S, int C) { return N > 0 && L > 0 && S > 0 && valid_channels(C); }
-
 extern "C" int fm_dual_softmax_conf_at(const float* feat0, const float* feat1, int N, int L, int S, int C, float temperature,
                                        const float* ofs_r, const float* sum_r, int pitch_r, const float* ofs_c,
                                        const float* sum_c, int pitch_c,
@@ -461,51 +461,79 @@ extern "C" int fm_dual_softmax_conf_at(const float* feat0, const float* feat1, i
   return (int)hipGetLastError();
 }
 
+// Workspace of both backward entry points: v [N][L] row sums and u [N][S] column sums of g conf, one behind the other
+// (sums: the two, zeroed per call) | part, 256-byte aligned: up to 4 (dsm_zsplit) partial gradients [N][max(L, S)][C]
+struct DsmBwdWs { Span v, u, sums, part; size_t total; };
+static DsmBwdWs dsm_bwd_layout(int N, int L, int S, int C) {
+  DsmBwdWs w;
+  w.v = {0, (size_t)N * L * 4};
+  w.u = {w.v.bytes, (size_t)N * S * 4};
+  w.sums = {0, w.v.bytes + w.u.bytes};
+  w.part = {align256(w.sums.bytes), (size_t)4 * N * (size_t)(L > S ? L : S) * C * 4};
+  w.total = w.part.at + w.part.bytes;
+  return w;
+}
+
 extern "C" size_t fm_dual_softmax_backward_workspace_bytes(int N, int L, int S, int C) {
-  if (!dsm_shape_ok(N, L, S, C)) return 0;
-  const size_t m = (size_t)(L > S ? L : S);
-  return align256((size_t)N * (L + S) * 4) + (size_t)4 * N * m * C * 4;      // u, v + up to 4 partial gradients
+  return N > 0 && L > 0 && S > 0 && valid_channels(C) ? dsm_bwd_layout(N, L, S, C).total : 0;
+}
+
+// the softmax statistics the forward pass kept: -stabiliser*log2e and denominator of every row / column
+struct DsmStats {
+  const float *ofs_r, *sum_r; int pitch_r;
+  const float *ofs_c, *sum_c; int pitch_c;
+};
+// one backward call: the descriptors, the shape, the temperature terms and the carved workspace
+struct DsmProblem {
+  const float *feat0, *feat1;
+  int N, L, S, C;
+  float k2, inv_ct;
+  float *v, *u, *part;
+};
+
+// what both backward entry points do after their NULL checks: the remaining argument checks, then *p with v and u zeroed
+static int dsm_begin(const float* feat0, const float* feat1, int N, int L, int S, int C, float temperature, const DsmStats& s,
+                     void* workspace, size_t workspace_bytes, hipStream_t st, DsmProblem* p) {
+  if (!(N > 0 && L > 0 && S > 0) || s.pitch_r < L || s.pitch_c < S) return FM_E_SHAPE;
+  if (!valid_channels(C) || !(temperature > 0.f)) return FM_E_UNSUPPORTED;
+  const DsmBwdWs w = dsm_bwd_layout(N, L, S, C);
+  if (workspace_bytes < w.total || ((uintptr_t)workspace & 255)) return FM_E_WORKSPACE;
+  const float inv_ct = 1.0f / ((float)C * temperature);
+  *p = {feat0, feat1, N, L, S, C, kLog2e * inv_ct, inv_ct, span_ptr<float>(workspace, w.v), span_ptr<float>(workspace, w.u),
+        span_ptr<float>(workspace, w.part)};
+  return (int)hipMemsetAsync(span_ptr<char>(workspace, w.sums), 0, w.sums.bytes, st);
 }
 
 // the tiled sweep of one side (0: owner = image 0, 1: owner = image 1) in one of its three modes + the combine of its partials
-static int dsm_sweep(int mode, int side, const float* feat0, const float* feat1, int N, int L, int S, int C, float k2, float inv_ct,
-                     const float* ofs_r, const float* sum_r, int pitch_r, const float* ofs_c, const float* sum_c, int pitch_c,
-                     float* v, float* u, float* part, const float* G, float* d_out, hipStream_t st) {
-  const float* X = side ? feat1 : feat0;
-  const float* Y = side ? feat0 : feat1;
-  const int R = side ? S : L, T = side ? L : S;
-  const int Z = dsm_zsplit(N, R);
-  const dim3 grid((R + 31) / 32, N, Z);
-  const int Cp = padded_channels(C);
-  const int smem = (64 * (Cp + 4) + 32 * 36 + 32 * 33) * 4;
-  hipError_t e = hipSuccess;
-#define FM_DSM_LAUNCH(CC, MM)                                                                                              \
-  {                                                                                                                        \
-    static unsigned long long lds_set = 0;                                                                                 \
-    e = ensure_dynamic_lds(&k_dsm_bwd<CC, MM>, (64 * (CC + 4) + 32 * 36 + 32 * 33) * 4, &lds_set);                         \
-    if (e != hipSuccess) return (int)e;                                                                                    \
-    hipLaunchKernelGGL((k_dsm_bwd<CC, MM>), grid, dim3(256), smem, st, X, Y, R, T, C, side ? ofs_c : ofs_r,                \
-                       side ? sum_c : sum_r, side ? pitch_c : pitch_r, side ? ofs_r : ofs_c, side ? sum_r : sum_c,         \
-                       side ? pitch_r : pitch_c, side ? u : v, side ? v : u, k2, part, G, side, v, u);                     \
+static int dsm_sweep(int mode, int side, const DsmProblem& p, const DsmStats& s, const float* G, float* d_out, hipStream_t st) {
+  DsmProblem o = p;          // as the owner sees it: its own descriptors, length, statistics and sums come first
+  DsmStats t = s;
+  if (side) {
+    std::swap(o.feat0, o.feat1); std::swap(o.L, o.S); std::swap(o.v, o.u);
+    t = {s.ofs_c, s.sum_c, s.pitch_c, s.ofs_r, s.sum_r, s.pitch_r};
   }
-#define FM_DSM_CASE(CC)                                                      \
-  case CC:                                                                   \
-    if (mode == kDsmSparse) FM_DSM_LAUNCH(CC, kDsmSparse)                    \
-    else if (mode == kDsmStats) FM_DSM_LAUNCH(CC, kDsmStats)                 \
-    else FM_DSM_LAUNCH(CC, kDsmDense)                                        \
-    break;
-  switch (Cp) {
-    FM_DSM_CASE(64)
-    FM_DSM_CASE(128)
-    FM_DSM_CASE(256)
-    default: return FM_E_UNSUPPORTED;
-  }
-#undef FM_DSM_CASE
-#undef FM_DSM_LAUNCH
+  const int Z = dsm_zsplit(p.N, o.L);
+  const dim3 grid((o.L + 31) / 32, p.N, Z);
+  auto launch = [&](auto cc, auto mm) -> hipError_t {
+    constexpr int CC = decltype(cc)::value, MM = decltype(mm)::value, smem = (64 * (CC + 4) + 32 * 36 + 32 * 33) * 4;
+    static unsigned long long lds_set = 0;      // (one per instantiation of this lambda, that is, per kernel)
+    const hipError_t e = ensure_dynamic_lds(&k_dsm_bwd<CC, MM>, smem, &lds_set);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((k_dsm_bwd<CC, MM>), grid, dim3(256), smem, st, o.feat0, o.feat1, o.L, o.S, p.C, t.ofs_r, t.sum_r,
+                       t.pitch_r, t.ofs_c, t.sum_c, t.pitch_c, o.v, o.u, p.k2, p.part, G, side, p.v, p.u);
+    return hipSuccess;
+  };
+  auto with_mode = [&](auto cc) {
+    if (mode == kDsmSparse) return launch(cc, int_c<kDsmSparse>{});
+    return mode == kDsmStats ? launch(cc, int_c<kDsmStats>{}) : launch(cc, int_c<kDsmDense>{});
+  };
+  const int Cp = padded_channels(p.C);
+  const hipError_t e = Cp == 64 ? with_mode(int_c<64>{}) : Cp == 128 ? with_mode(int_c<128>{}) : with_mode(int_c<256>{});
+  if (e != hipSuccess) return (int)e;
   if (mode != kDsmStats) {
-    const long n4 = (long)N * R * C / 4;
-    hipLaunchKernelGGL(k_dsm_combine, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, (const float4*)part, n4, Z, inv_ct,
-                       (float4*)d_out);
+    const long n4 = (long)p.N * o.L * p.C / 4;
+    hipLaunchKernelGGL(k_dsm_combine, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, (const float4*)p.part, n4, Z,
+                       p.inv_ct, (float4*)d_out);
   }
   return (int)hipGetLastError();
 }
@@ -519,24 +547,16 @@ extern "C" int fm_dual_softmax_backward_dense(const float* feat0, const float* f
                                               void* workspace, size_t workspace_bytes, float* d_feat0, float* d_feat1,
                                               void* stream) {
   if (!feat0 || !feat1 || !ofs_r || !ofs_c || !sum_r || !sum_c || !G || !workspace || !d_feat0 || !d_feat1) return FM_E_NULL;
-  if (!(N > 0 && L > 0 && S > 0) || pitch_r < L || pitch_c < S) return FM_E_SHAPE;
-  if (!valid_channels(C) || !(temperature > 0.f)) return FM_E_UNSUPPORTED;
-  if (workspace_bytes < fm_dual_softmax_backward_workspace_bytes(N, L, S, C) || ((uintptr_t)workspace & 255)) return FM_E_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  const float inv_ct = 1.0f / ((float)C * temperature), k2 = kLog2e * inv_ct;
-  float* v = (float*)workspace;                 // [N][L]  row sums of G conf
-  float* u = v + (size_t)N * L;                 // [N][S]  column sums
-  float* part = (float*)((char*)workspace + align256((size_t)N * (L + S) * 4));
-  hipError_t e = hipMemsetAsync(workspace, 0, (size_t)N * (L + S) * 4, st);
-  if (e != hipSuccess) return (int)e;
-  int r = dsm_sweep(kDsmStats, 0, feat0, feat1, N, L, S, C, k2, inv_ct, ofs_r, sum_r, pitch_r, ofs_c, sum_c, pitch_c, v, u, part, G,
-                    nullptr, st);
+  const DsmStats s = {ofs_r, sum_r, pitch_r, ofs_c, sum_c, pitch_c};
+  DsmProblem p;
+  int r = dsm_begin(feat0, feat1, N, L, S, C, temperature, s, workspace, workspace_bytes, st, &p);
   if (r != FM_OK) return r;
-  r = dsm_sweep(kDsmDense, 0, feat0, feat1, N, L, S, C, k2, inv_ct, ofs_r, sum_r, pitch_r, ofs_c, sum_c, pitch_c, v, u, part, G,
-                d_feat0, st);
+  r = dsm_sweep(kDsmStats, 0, p, s, G, nullptr, st);
   if (r != FM_OK) return r;
-  return dsm_sweep(kDsmDense, 1, feat0, feat1, N, L, S, C, k2, inv_ct, ofs_r, sum_r, pitch_r, ofs_c, sum_c, pitch_c, v, u, part, G,
-                   d_feat1, st);
+  r = dsm_sweep(kDsmDense, 0, p, s, G, d_feat0, st);
+  if (r != FM_OK) return r;
+  return dsm_sweep(kDsmDense, 1, p, s, G, d_feat1, st);
 }
 
 extern "C" int fm_dual_softmax_backward(const float* feat0, const float* feat1, int N, int L, int S, int C, float temperature,
@@ -547,24 +567,19 @@ extern "C" int fm_dual_softmax_backward(const float* feat0, const float* feat1, 
                                         void* stream) {
   if (!feat0 || !feat1 || !ofs_r || !ofs_c || !sum_r || !sum_c || !workspace || !d_feat0 || !d_feat1) return FM_E_NULL;
   if (K > 0 && (!b_ids || !i_ids || !j_ids || !gc)) return FM_E_NULL;
-  if (!(N > 0 && L > 0 && S > 0) || K < 0 || pitch_r < L || pitch_c < S) return FM_E_SHAPE;
-  if (!valid_channels(C) || !(temperature > 0.f)) return FM_E_UNSUPPORTED;
-  if (workspace_bytes < fm_dual_softmax_backward_workspace_bytes(N, L, S, C) || ((uintptr_t)workspace & 255)) return FM_E_WORKSPACE;
+  if (K < 0) return FM_E_SHAPE;
   hipStream_t st = (hipStream_t)stream;
-  const float inv_ct = 1.0f / ((float)C * temperature), k2 = kLog2e * inv_ct;
-  float* v = (float*)workspace;                 // [N][L]  row sums of g c
-  float* u = v + (size_t)N * L;                 // [N][S]  column sums
-  float* part = (float*)((char*)workspace + align256((size_t)N * (L + S) * 4));
-  hipError_t e = hipMemsetAsync(workspace, 0, (size_t)N * (L + S) * 4, st);
-  if (e != hipSuccess) return (int)e;
-  if (K > 0) hipLaunchKernelGGL(k_dsm_uv, dim3((K + 255) / 256), dim3(256), 0, st, b_ids, i_ids, j_ids, gc, K, L, S, v, u);
+  const DsmStats s = {ofs_r, sum_r, pitch_r, ofs_c, sum_c, pitch_c};
+  DsmProblem p;
+  int r = dsm_begin(feat0, feat1, N, L, S, C, temperature, s, workspace, workspace_bytes, st, &p);
+  if (r != FM_OK) return r;
+  if (K > 0) hipLaunchKernelGGL(k_dsm_uv, dim3((K + 255) / 256), dim3(256), 0, st, b_ids, i_ids, j_ids, gc, K, L, S, p.v, p.u);
   for (int side = 0; side < 2; ++side) {
-    const int r = dsm_sweep(kDsmSparse, side, feat0, feat1, N, L, S, C, k2, inv_ct, ofs_r, sum_r, pitch_r, ofs_c, sum_c, pitch_c, v,
-                            u, part, nullptr, side ? d_feat1 : d_feat0, st);
+    r = dsm_sweep(kDsmSparse, side, p, s, nullptr, side ? d_feat1 : d_feat0, st);
     if (r != FM_OK) return r;
   }
   if (K > 0)
     hipLaunchKernelGGL(k_dsm_entries, dim3((K + 3) / 4), dim3(256), 0, st, feat0, feat1, L, S, C, b_ids, i_ids, j_ids, gc, K,
-                       2.0f * inv_ct, d_feat0, d_feat1);
+                       2.0f * p.inv_ct, d_feat0, d_feat1);
   return (int)hipGetLastError();
 }

@@ -604,17 +604,10 @@ template <bool MERGE>
 static void launch_list64(int W, int blocks, hipStream_t st, const float* feat_f, int Hf, int Wf, int stride, int pad,
                           int w_c, const int64_t* b_ids, const int64_t* ids, const int32_t* d_count, int m_max,
                           float* out, const half8* wpack, const float* ctx, int ctx_cells) {
-  if (W == 5)
-    hipLaunchKernelGGL((k_gather_nchw64<5, MERGE>), dim3(blocks), dim3(256), 0, st, feat_f, Hf, Wf, stride, pad, w_c,
-                       b_ids, ids, d_count, m_max, out, wpack, ctx, ctx_cells);
-  else
-    hipLaunchKernelGGL((k_gather_nchw64<7, MERGE>), dim3(blocks), dim3(256), 0, st, feat_f, Hf, Wf, stride, pad, w_c,
-                       b_ids, ids, d_count, m_max, out, wpack, ctx, ctx_cells);
-}
-template <bool MERGE>
-static void launch_cells64(int W, int blocks, int nimg, hipStream_t st, const CellArgs& a) {
-  if (W == 5) hipLaunchKernelGGL((k_gather_cellorder64<5, MERGE>), dim3(blocks, nimg), dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((k_gather_cellorder64<7, MERGE>), dim3(blocks, nimg), dim3(256), 0, st, a);
+  with_window(W, [&](auto w) {
+    hipLaunchKernelGGL((k_gather_nchw64<decltype(w)::value, MERGE>), dim3(blocks), dim3(256), 0, st, feat_f, Hf, Wf, stride,
+                       pad, w_c, b_ids, ids, d_count, m_max, out, wpack, ctx, ctx_cells);
+  });
 }
 static CellImage cell_image(const float* feat, int N, int Hf, int Wf, int h_c, int w_c, const int32_t* map, int pitch,
                             const int32_t* ties, const int64_t* ids, float* out, const float* ctx) {
@@ -623,7 +616,14 @@ static CellImage cell_image(const float* feat, int N, int Hf, int Wf, int h_c, i
   im.cell_to_match = map; im.cell_pitch = pitch; im.ties = ties; im.ids = ids; im.out = out; im.ctx = ctx;
   return im;
 }
-// the fast NCHW kernels address one sample's map with 31-bit byte offsets (buffer descriptor)
+static CellArgs cell_args(const CellImage& im0, const CellImage& im1, int stride, int pad, int m_max, const int64_t* b_ids,
+                          const int32_t* d_count, const void* packed_w) {
+  CellArgs a;
+  a.im[0] = im0; a.im[1] = im1;
+  a.stride = stride; a.pad = pad; a.m_max = m_max; a.b_ids = b_ids; a.d_count = d_count; a.wpack = (const half8*)packed_w;
+  return a;
+}
+// the 64-channel kernels (crop and fine) address one sample's float32 map with 31-bit byte offsets (buffer descriptor)
 static bool fast_nchw64(int Cf, int Hf, int Wf, int W) {
   return Cf == 64 && (W == 5 || W == 7) && (long)Hf * Wf * 64 * 4 < (1L << 31);
 }
@@ -633,6 +633,18 @@ static int list_blocks(int m_max) { return 8 * (((m_max + 7) / 8 + 3) / 4); }
 constexpr int kFineGridCap = 1 << 20;
 // one wave per cell, four per workgroup, grid a multiple of 8
 static int cell_blocks(long total) { return (int)(((total + 3) / 4 + 7) / 8 * 8); }
+// the cell-ordered crop of `nimg` images (the larger has `total` cells) in one launch; a.wpack != NULL: with the merge
+static int launch_cells64(int W, int nimg, long total, const CellArgs& a, hipStream_t st) {
+  with_window(W, [&](auto w) {
+    auto launch = [&](auto merge) {
+      hipLaunchKernelGGL((k_gather_cellorder64<decltype(w)::value, decltype(merge)::value>), dim3(cell_blocks(total), nimg),
+                         dim3(256), 0, st, a);
+    };
+    if (a.wpack) launch(std::true_type{});
+    else launch(std::false_type{});
+  });
+  return (int)hipGetLastError();
+}
 
 template <int DT>
 static void launch_generic_gather(const void* feat_f, int Cf, int Hf, int Wf, int layout, int W, int stride, int pad, int w_c,
@@ -655,7 +667,7 @@ extern "C" int fm_gather_windows_dtype(const void* feat_f, int map_dtype, int N,
   if (m_max == 0) return FM_OK;
   if (!feat_f || !b_ids || !ids || !out) return FM_E_NULL;
   if (map_dtype != FM_F32 && map_dtype != FM_F16 && map_dtype != FM_BF16) return FM_E_UNSUPPORTED;
-  if (N <= 0 || Cf <= 0 || Hf <= 0 || Wf <= 0 || W <= 0 || stride <= 0 || w_c <= 0 || m_max < 0) return FM_E_SHAPE;
+  if (!crop_shape_ok(N, Hf, Wf, stride, m_max) || Cf <= 0 || W <= 0 || w_c <= 0) return FM_E_SHAPE;
   if (W > 15 || Cf > 512 || (layout == 1 && Cf % 4) || (layout != 0 && layout != 1)) return FM_E_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   if (layout == 0 && (size_t)W * W * (Cf + 1) * sizeof(float) > 64 * 1024 &&
@@ -665,12 +677,10 @@ extern "C" int fm_gather_windows_dtype(const void* feat_f, int map_dtype, int N,
                          out, nullptr, nullptr, 0);
   } else if (map_dtype == FM_F32 && layout == 1 && Cf == 64 && (W == 5 || W == 7)) {
     // channels-last fast path: one wave per window, 16-byte chunks
-    if (W == 5)
-      hipLaunchKernelGGL(k_gather_nhwc64<5>, dim3(list_blocks(m_max)), dim3(256), 0, st, (const float*)feat_f, Hf, Wf, stride,
-                         pad, w_c, b_ids, ids, d_count, m_max, out);
-    else
-      hipLaunchKernelGGL(k_gather_nhwc64<7>, dim3(list_blocks(m_max)), dim3(256), 0, st, (const float*)feat_f, Hf, Wf, stride,
-                         pad, w_c, b_ids, ids, d_count, m_max, out);
+    with_window(W, [&](auto w) {
+      hipLaunchKernelGGL(k_gather_nhwc64<decltype(w)::value>, dim3(list_blocks(m_max)), dim3(256), 0, st,
+                         (const float*)feat_f, Hf, Wf, stride, pad, w_c, b_ids, ids, d_count, m_max, out);
+    });
   } else if (map_dtype == FM_F32) {
     launch_generic_gather<FM_F32>(feat_f, Cf, Hf, Wf, layout, W, stride, pad, w_c, b_ids, ids, d_count, m_max, out, st);
   } else if (map_dtype == FM_F16) {
@@ -696,14 +706,11 @@ extern "C" int fm_gather_windows_cells(const float* feat_f, int N, int Cf, int H
                                        const int32_t* d_count, int m_max, float* out, void* stream) {
   if (m_max == 0) return FM_OK;
   if (!feat_f || !cell_to_match || !ties || !b_ids || !ids || !out) return FM_E_NULL;
-  if (N <= 0 || Hf <= 0 || Wf <= 0 || h_c <= 0 || w_c <= 0 || stride <= 0 || m_max < 0 || cell_pitch < h_c * w_c)
-    return FM_E_SHAPE;
+  if (!crop_shape_ok(N, Hf, Wf, stride, m_max) || h_c <= 0 || w_c <= 0 || cell_pitch < h_c * w_c) return FM_E_SHAPE;
   if (!fast_nchw64(Cf, Hf, Wf, W)) return FM_E_UNSUPPORTED;
-  CellArgs a;
-  a.im[0] = a.im[1] = cell_image(feat_f, N, Hf, Wf, h_c, w_c, cell_to_match, cell_pitch, ties, ids, out, nullptr);
-  a.stride = stride; a.pad = pad; a.m_max = m_max; a.b_ids = b_ids; a.d_count = d_count; a.wpack = nullptr;
-  launch_cells64<false>(W, cell_blocks((long)N * h_c * w_c), 1, (hipStream_t)stream, a);
-  return (int)hipGetLastError();
+  const CellImage im = cell_image(feat_f, N, Hf, Wf, h_c, w_c, cell_to_match, cell_pitch, ties, ids, out, nullptr);
+  return launch_cells64(W, 1, (long)N * h_c * w_c, cell_args(im, im, stride, pad, m_max, b_ids, d_count, nullptr),
+                        (hipStream_t)stream);
 }
 
 // merge_feat.weight[:, :64] (row-major [64, 128], fine_preprocess.py:26) -> MFMA B fragments, f16 hi and lo:
@@ -742,21 +749,16 @@ extern "C" int fm_gather_merge_windows(const float* feat_f, int N, int Cf, int H
   if (m_max == 0) return FM_OK;
   if (!feat_f || !packed_w || !ctx_bias || !b_ids || !ids || !out) return FM_E_NULL;
   if (cell_to_match && !ties) return FM_E_NULL;
-  if (N <= 0 || Hf <= 0 || Wf <= 0 || h_c <= 0 || w_c <= 0 || stride <= 0 || m_max < 0) return FM_E_SHAPE;
-  if (cell_to_match && cell_pitch < h_c * w_c) return FM_E_SHAPE;
+  if (!crop_shape_ok(N, Hf, Wf, stride, m_max) || h_c <= 0 || w_c <= 0 || (cell_to_match && cell_pitch < h_c * w_c))
+    return FM_E_SHAPE;
   if (!fast_nchw64(Cf, Hf, Wf, W)) return FM_E_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
-  const long total = (long)N * h_c * w_c;
   if (cell_to_match) {
-    CellArgs a;
-    a.im[0] = a.im[1] = cell_image(feat_f, N, Hf, Wf, h_c, w_c, cell_to_match, cell_pitch, ties, ids, out, ctx_bias);
-    a.stride = stride; a.pad = pad; a.m_max = m_max; a.b_ids = b_ids; a.d_count = d_count;
-    a.wpack = (const half8*)packed_w;
-    launch_cells64<true>(W, cell_blocks(total), 1, st, a);
+    const CellImage im = cell_image(feat_f, N, Hf, Wf, h_c, w_c, cell_to_match, cell_pitch, ties, ids, out, ctx_bias);
+    return launch_cells64(W, 1, (long)N * h_c * w_c, cell_args(im, im, stride, pad, m_max, b_ids, d_count, packed_w), st);
   }
-  else
-    launch_list64<true>(W, list_blocks(m_max), st, feat_f, Hf, Wf, stride, pad, w_c, b_ids, ids, d_count, m_max, out,
-                        (const half8*)packed_w, ctx_bias, h_c * w_c);
+  launch_list64<true>(W, list_blocks(m_max), st, feat_f, Hf, Wf, stride, pad, w_c, b_ids, ids, d_count, m_max, out,
+                      (const half8*)packed_w, ctx_bias, h_c * w_c);
   return (int)hipGetLastError();
 }
 
@@ -771,20 +773,15 @@ extern "C" int fm_gather_windows_pair(const float* feat_f0, const float* feat_f1
   if (!feat_f0 || !feat_f1 || !cell0 || !cell1 || !ties0 || !ties1 || !b_ids || !i_ids || !j_ids || !out0 || !out1)
     return FM_E_NULL;
   if (packed_w && (!ctx0 || !ctx1)) return FM_E_NULL;
-  if (N <= 0 || Hf0 <= 0 || Wf0 <= 0 || Hf1 <= 0 || Wf1 <= 0 || h0c <= 0 || w0c <= 0 || h1c <= 0 || w1c <= 0 ||
-      stride <= 0 || m_max < 0 || pitch0 < h0c * w0c || pitch1 < h1c * w1c)
+  if (!crop_shape_ok(N, Hf0, Wf0, stride, m_max) || !crop_shape_ok(N, Hf1, Wf1, stride, m_max) || h0c <= 0 || w0c <= 0 ||
+      h1c <= 0 || w1c <= 0 || pitch0 < h0c * w0c || pitch1 < h1c * w1c)
     return FM_E_SHAPE;
   if (!fast_nchw64(Cf, Hf0, Wf0, W) || !fast_nchw64(Cf, Hf1, Wf1, W)) return FM_E_UNSUPPORTED;
-  CellArgs a;
-  a.im[0] = cell_image(feat_f0, N, Hf0, Wf0, h0c, w0c, cell0, pitch0, ties0, i_ids, out0, ctx0);
-  a.im[1] = cell_image(feat_f1, N, Hf1, Wf1, h1c, w1c, cell1, pitch1, ties1, j_ids, out1, ctx1);
-  a.stride = stride; a.pad = pad; a.m_max = m_max; a.b_ids = b_ids; a.d_count = d_count;
-  a.wpack = (const half8*)packed_w;
+  const CellArgs a = cell_args(cell_image(feat_f0, N, Hf0, Wf0, h0c, w0c, cell0, pitch0, ties0, i_ids, out0, ctx0),
+                               cell_image(feat_f1, N, Hf1, Wf1, h1c, w1c, cell1, pitch1, ties1, j_ids, out1, ctx1), stride,
+                               pad, m_max, b_ids, d_count, packed_w);
   const long t0 = (long)N * h0c * w0c, t1 = (long)N * h1c * w1c;
-  const int blocks = cell_blocks(t0 > t1 ? t0 : t1);
-  if (packed_w) launch_cells64<true>(W, blocks, 2, (hipStream_t)stream, a);
-  else launch_cells64<false>(W, blocks, 2, (hipStream_t)stream, a);
-  return (int)hipGetLastError();
+  return launch_cells64(W, 2, t0 > t1 ? t0 : t1, a, (hipStream_t)stream);
 }
 
 extern "C" int fm_fine_match(const float* win0, const float* win1, int m_max, const int32_t* d_count, int WW, int Cf,
@@ -796,26 +793,37 @@ extern "C" int fm_fine_match(const float* win0, const float* win1, int m_max, co
   if (Cf != 64 || (WW != 25 && WW != 49)) return FM_E_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   const int blocks = (m_max + 3) / 4;
-  if (WW == 49)
-    hipLaunchKernelGGL(k_fine<7>, dim3(blocks), dim3(256), 0, st, win0, win1, m_max, d_count, mix0, mix1, mkpts0_c,
-                       mkpts1_c, scale_f, out0, out1);
-  else
-    hipLaunchKernelGGL(k_fine<5>, dim3(blocks), dim3(256), 0, st, win0, win1, m_max, d_count, mix0, mix1, mkpts0_c,
-                       mkpts1_c, scale_f, out0, out1);
+  with_window(WW == 25 ? 5 : 7, [&](auto w) {
+    hipLaunchKernelGGL(k_fine<decltype(w)::value>, dim3(blocks), dim3(256), 0, st, win0, win1, m_max, d_count, mix0, mix1,
+                       mkpts0_c, mkpts1_c, scale_f, out0, out1);
+  });
   return (int)hipGetLastError();
 }
 
-// the fine maps of one sample must be addressable with 31-bit byte offsets (buffer descriptor)
-static bool maps64_ok(int Cf, int Hf, int Wf, int W) {
-  return Cf == 64 && (W == 5 || W == 7) && (long)Hf * Wf * 256 < (1L << 31);
+// Scratch of fm_fine_match_maps for NCHW maps: the channels-last copies k_fine_maps reads.  float32 maps: image 1's
+// only (image 0 is read as it is: map[0] is empty).  Half-precision maps: both images' (2-byte elements), image 0's
+// first, image 1's 256-byte aligned.
+struct FineMapsScratch { Span map[2]; size_t total; };
+static FineMapsScratch fine_maps_layout(int N, int Cf, int Hf0, int Wf0, int Hf1, int Wf1, int map_dtype) {
+  const size_t elem = map_dtype == FM_F32 ? 4 : 2;
+  FineMapsScratch s;
+  s.map[0] = {0, map_dtype == FM_F32 ? 0 : (size_t)N * Cf * elem * (size_t)Hf0 * Wf0};
+  s.map[1] = {align256(s.map[0].bytes), (size_t)N * Cf * elem * (size_t)Hf1 * Wf1};
+  s.total = s.map[1].at + s.map[1].bytes;
+  return s;
 }
 
 extern "C" size_t fm_fine_maps_scratch_bytes_dtype(int N, int Cf, int Hf0, int Wf0, int Hf1, int Wf1, int layout, int map_dtype) {
   if (layout != 0 || N <= 0 || Cf <= 0 || Hf0 <= 0 || Wf0 <= 0 || Hf1 <= 0 || Wf1 <= 0) return 0;
-  if (map_dtype == FM_F32) return (size_t)N * Cf * 4 * (size_t)Hf1 * Wf1;      // the channels-last copy of image 1
-  // half-precision maps: channels-last copies of BOTH images (2-byte elements), image 0's first, 256-byte aligned
-  const size_t b0 = (size_t)N * Cf * 2 * (size_t)Hf0 * Wf0, b1 = (size_t)N * Cf * 2 * (size_t)Hf1 * Wf1;
-  return align256(b0) + b1;
+  return fine_maps_layout(N, Cf, Hf0, Wf0, Hf1, Wf1, map_dtype).total;
+}
+
+// [N, 64, Hf, Wf] -> [N, Hf, Wf, 64] of T (k_nchw_to_nhwc64): one workgroup per piece, or grid_cap of them in strides
+template <typename T>
+static void launch_channels_last_copy(const void* src, void* dst, int N, int Hf, int Wf, int grid_cap, hipStream_t st) {
+  const long pieces = (long)((Wf + 63) / 64) * Hf * N;
+  hipLaunchKernelGGL(k_nchw_to_nhwc64<T>, dim3((unsigned)(pieces < grid_cap ? pieces : grid_cap)), dim3(256), 0, st,
+                     (const T*)src, (T*)dst, Hf, Wf, N);
 }
 extern "C" size_t fm_fine_maps_scratch_bytes(int N, int Cf, int Hf0, int Wf0, int Hf1, int Wf1, int layout) {
   return fm_fine_maps_scratch_bytes_dtype(N, Cf, Hf0, Wf0, Hf1, Wf1, layout, FM_F32);
@@ -830,11 +838,11 @@ extern "C" int fm_fine_match_maps_dtype(const void* feat_f0, const void* feat_f1
   if (m_max == 0) return FM_OK;
   if (!feat_f0 || !feat_f1 || !b_ids || !i_ids || !j_ids || !mix0 || !mix1 || !mkpts0_c || !mkpts1_c || !out0 || !out1)
     return FM_E_NULL;
-  if (N <= 0 || Hf0 <= 0 || Wf0 <= 0 || Hf1 <= 0 || Wf1 <= 0 || stride <= 0 || w0c <= 0 || w1c <= 0 || m_max < 0)
+  if (!crop_shape_ok(N, Hf0, Wf0, stride, m_max) || !crop_shape_ok(N, Hf1, Wf1, stride, m_max) || w0c <= 0 || w1c <= 0)
     return FM_E_SHAPE;
   if (map_dtype != FM_F32 && map_dtype != FM_F16 && map_dtype != FM_BF16) return FM_E_UNSUPPORTED;
-  if ((layout != 0 && layout != 1 && layout != FM_LAYOUT_NCHW_PREPARED) || !maps64_ok(Cf, Hf0, Wf0, W) ||
-      !maps64_ok(Cf, Hf1, Wf1, W))
+  if ((layout != 0 && layout != 1 && layout != FM_LAYOUT_NCHW_PREPARED) || !fast_nchw64(Cf, Hf0, Wf0, W) ||
+      !fast_nchw64(Cf, Hf1, Wf1, W))
     return FM_E_UNSUPPORTED;
   // (image 1's channels-last copy was made by the coarse call - fm_coarse_match_maps - into `scratch`: float32 maps only)
   const bool prepared = layout == FM_LAYOUT_NCHW_PREPARED;
@@ -848,37 +856,31 @@ extern "C" int fm_fine_match_maps_dtype(const void* feat_f0, const void* feat_f1
 #ifdef FM_TUNE_ENV
   if (const char* e = getenv("FM_FINE_GRID")) grid_cap = atoi(e) > 0 ? atoi(e) / 8 * 8 : kFineGridCap;
 #endif
-  const bool half = map_dtype != FM_F32;
-  if (layout == 0 && !half) {   // NCHW: a channels-last copy of image 1 (coalesced on both sides); image 0 is read as it is
-    float* s1 = (float*)scratch;
-    const long pieces = (long)((Wf1 + 63) / 64) * Hf1 * N;
-    if (!prepared)
-      hipLaunchKernelGGL(k_nchw_to_nhwc64<float>, dim3((unsigned)(pieces < grid_cap ? pieces : grid_cap)), dim3(256), 0, st,
-                         (const float*)feat_f1, s1, Hf1, Wf1, N);
+  if (layout == 0) {   // NCHW: channels-last copies (coalesced on both sides), element type kept
+    const FineMapsScratch sc = fine_maps_layout(N, Cf, Hf0, Wf0, Hf1, Wf1, map_dtype);
+    float* s0 = span_ptr<float>(scratch, sc.map[0]);
+    float* s1 = span_ptr<float>(scratch, sc.map[1]);
+    if (map_dtype == FM_F32) {     // image 0 is read as it is; image 1's copy may have been made by the coarse call
+      if (!prepared) launch_channels_last_copy<float>(feat_f1, s1, N, Hf1, Wf1, grid_cap, st);
+    } else {
+      launch_channels_last_copy<unsigned short>(feat_f0, s0, N, Hf0, Wf0, grid_cap, st);
+      launch_channels_last_copy<unsigned short>(feat_f1, s1, N, Hf1, Wf1, grid_cap, st);
+      m0 = s0;
+    }
     m1 = s1;
-  } else if (layout == 0) {     // NCHW float16 / bfloat16: channels-last copies of both maps, element type kept
-    unsigned short* s0 = (unsigned short*)scratch;
-    unsigned short* s1 = (unsigned short*)((char*)scratch + align256((size_t)N * Cf * 2 * (size_t)Hf0 * Wf0));
-    const long p0 = (long)((Wf0 + 63) / 64) * Hf0 * N, p1 = (long)((Wf1 + 63) / 64) * Hf1 * N;
-    hipLaunchKernelGGL(k_nchw_to_nhwc64<unsigned short>, dim3((unsigned)(p0 < grid_cap ? p0 : grid_cap)), dim3(256), 0, st,
-                       (const unsigned short*)feat_f0, s0, Hf0, Wf0, N);
-    hipLaunchKernelGGL(k_nchw_to_nhwc64<unsigned short>, dim3((unsigned)(p1 < grid_cap ? p1 : grid_cap)), dim3(256), 0, st,
-                       (const unsigned short*)feat_f1, s1, Hf1, Wf1, N);
-    m0 = (const float*)s0;
-    m1 = (const float*)s1;
   }
   const int blocks = list_blocks(m_max) < grid_cap ? list_blocks(m_max) : grid_cap;
-#define FM_FINE_MAPS_LAUNCH(WQ, N0, DTQ)                                                                                 \
-  hipLaunchKernelGGL((k_fine_maps<WQ, N0, DTQ>), dim3(blocks), dim3(256), 0, st, m0, m1, Hf0, Wf0, Hf1, Wf1, stride, pad, \
-                     w0c, w1c, b_ids, i_ids, j_ids, d_count, m_max, mix0, mix1, mkpts0_c, mkpts1_c, scale_f, out0, out1)
-#define FM_FINE_MAPS_W(WQ)                                                        \
-  if (map_dtype == FM_F16) FM_FINE_MAPS_LAUNCH(WQ, false, FM_F16);                \
-  else if (map_dtype == FM_BF16) FM_FINE_MAPS_LAUNCH(WQ, false, FM_BF16);         \
-  else if (layout == 0) FM_FINE_MAPS_LAUNCH(WQ, true, FM_F32);                    \
-  else FM_FINE_MAPS_LAUNCH(WQ, false, FM_F32)
-  if (W == 5) { FM_FINE_MAPS_W(5); } else { FM_FINE_MAPS_W(7); }
-#undef FM_FINE_MAPS_W
-#undef FM_FINE_MAPS_LAUNCH
+  with_window(W, [&](auto w) {
+    auto launch = [&](auto nchw0, auto dt) {
+      hipLaunchKernelGGL((k_fine_maps<decltype(w)::value, decltype(nchw0)::value, decltype(dt)::value>), dim3(blocks),
+                         dim3(256), 0, st, m0, m1, Hf0, Wf0, Hf1, Wf1, stride, pad, w0c, w1c, b_ids, i_ids, j_ids, d_count,
+                         m_max, mix0, mix1, mkpts0_c, mkpts1_c, scale_f, out0, out1);
+    };
+    if (map_dtype == FM_F16) launch(std::false_type{}, int_c<FM_F16>{});
+    else if (map_dtype == FM_BF16) launch(std::false_type{}, int_c<FM_BF16>{});
+    else if (layout == 0) launch(std::true_type{}, int_c<FM_F32>{});
+    else launch(std::false_type{}, int_c<FM_F32>{});
+  });
   return (int)hipGetLastError();
 }
 

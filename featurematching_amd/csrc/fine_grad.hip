@@ -277,21 +277,30 @@ extern "C" int fm_fine_match_backward(const float* win0, const float* win1, int 
   hipStream_t st = (hipStream_t)stream;
   float* part = (float*)workspace;
   const int blocks = (m_max + 3) / 4;
-  if (WW == 49)
-    hipLaunchKernelGGL(k_fine_bwd<7>, dim3(blocks), dim3(256), 0, st, win0, win1, m_max, d_count, mix0, mix1, scale_f,
-                       d_out0, d_out1, d_win0, d_win1, part);
-  else
-    hipLaunchKernelGGL(k_fine_bwd<5>, dim3(blocks), dim3(256), 0, st, win0, win1, m_max, d_count, mix0, mix1, scale_f,
-                       d_out0, d_out1, d_win0, d_win1, part);
+  with_window(WW == 25 ? 5 : 7, [&](auto w) {
+    hipLaunchKernelGGL(k_fine_bwd<decltype(w)::value>, dim3(blocks), dim3(256), 0, st, win0, win1, m_max, d_count, mix0,
+                       mix1, scale_f, d_out0, d_out1, d_win0, d_win1, part);
+  });
   hipLaunchKernelGGL(k_fine_mix_reduce, dim3(2 * (WW + 1)), dim3(256), 0, st, part, m_max, d_count, WW, d_mix0, d_mix1);
   return (int)hipGetLastError();
 }
 
-// workspace layout: starts [N cells + 1] | cursors [N cells] | match list [m_max], int32, each 256-byte aligned
-extern "C" size_t fm_gather_windows_backward_workspace_bytes(int N, int h_c, int w_c, int m_max) {
-  if (N <= 0 || h_c <= 0 || w_c <= 0 || m_max < 0) return 0;
+// Workspace of fm_gather_windows_backward, the CSR of matches per cell: starts [N cells + 1] | fill cursors [N cells] |
+// match list [m_max], int32, each 256-byte aligned.  counts: where k_csr_count adds up the cells' counts, zeroed per call.
+struct CropBwdWs { Span start, cursor, list, counts; size_t total; };
+static CropBwdWs crop_bwd_layout(int N, int h_c, int w_c, int m_max) {
   const size_t n = (size_t)N * h_c * w_c;
-  return align256((n + 1) * 4) + align256(n * 4) + align256((size_t)m_max * 4);
+  CropBwdWs w;
+  w.start = {0, (n + 1) * 4};
+  w.cursor = {align256(w.start.bytes), n * 4};
+  w.list = {w.cursor.at + align256(w.cursor.bytes), (size_t)m_max * 4};
+  w.counts = {0, n * 4};
+  w.total = w.list.at + align256(w.list.bytes);
+  return w;
+}
+
+extern "C" size_t fm_gather_windows_backward_workspace_bytes(int N, int h_c, int w_c, int m_max) {
+  return N > 0 && h_c > 0 && w_c > 0 && m_max >= 0 ? crop_bwd_layout(N, h_c, w_c, m_max).total : 0;
 }
 
 extern "C" int fm_gather_windows_backward(const float* d_win, const int64_t* b_ids, const int64_t* ids,
@@ -300,18 +309,17 @@ extern "C" int fm_gather_windows_backward(const float* d_win, const int64_t* b_i
                                           size_t workspace_bytes, float* d_feat, void* stream) {
   if (m_max == 0) return FM_OK;
   if (!d_win || !b_ids || !ids || !workspace || !d_feat) return FM_E_NULL;
-  if (N <= 0 || Cf <= 0 || Hf <= 0 || Wf <= 0 || W <= 0 || stride <= 0 || h_c <= 0 || w_c <= 0 || m_max < 0)
-    return FM_E_SHAPE;
+  if (!crop_shape_ok(N, Hf, Wf, stride, m_max) || Cf <= 0 || W <= 0 || h_c <= 0 || w_c <= 0) return FM_E_SHAPE;
   if (W > 15 || Cf > 512 || (layout != 0 && layout != 1)) return FM_E_UNSUPPORTED;
   if ((long)N * h_c * w_c >= (1L << 31) - 1 || (long)N * Hf >= (1L << 31) / ((Wf + 7) / 8)) return FM_E_UNSUPPORTED;
-  if (workspace_bytes < fm_gather_windows_backward_workspace_bytes(N, h_c, w_c, m_max) || ((uintptr_t)workspace & 255))
-    return FM_E_WORKSPACE;
+  const CropBwdWs ws = crop_bwd_layout(N, h_c, w_c, m_max);
+  if (workspace_bytes < ws.total || ((uintptr_t)workspace & 255)) return FM_E_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   const int cells = h_c * w_c, n = N * cells;
-  int* start = (int*)workspace;
-  int* cursor = (int*)((char*)workspace + align256(((size_t)n + 1) * 4));
-  int* list = (int*)((char*)cursor + align256((size_t)n * 4));
-  hipError_t e = hipMemsetAsync(start, 0, (size_t)n * 4, st);
+  int* start = span_ptr<int>(workspace, ws.start);
+  int* cursor = span_ptr<int>(workspace, ws.cursor);
+  int* list = span_ptr<int>(workspace, ws.list);
+  hipError_t e = hipMemsetAsync(span_ptr<int>(workspace, ws.counts), 0, ws.counts.bytes, st);
   if (e != hipSuccess) return (int)e;
   const int mb = (m_max + 255) / 256, cb = (n + 255) / 256;
   hipLaunchKernelGGL(k_csr_count, dim3(mb), dim3(256), 0, st, b_ids, ids, d_count, m_max, N, cells, start);

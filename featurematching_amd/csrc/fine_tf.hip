@@ -584,17 +584,17 @@ extern "C" int fm_fine_transformer_start(const float* win0, const float* win1, i
   constexpr int NW = 8;               // matches (waves) per workgroup: two waves per SIMD share the staged weights
   const int blocks = (m_max + NW - 1) / NW;
   const int smem = 2 * kRegionBytes;
-  static unsigned long long set49 = 0, set25 = 0;
-  if (WW == 49) {
-    hipError_t e = ensure_dynamic_lds(&k_fine_tf<49, NW>, smem, &set49);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL((k_fine_tf<49, NW>), dim3(blocks), dim3(NW * 64), smem, st, win0, win1, m_max, d_count, frag, ln, out0, out1, pstat, d_status, start_log2_scale, d_lowered);
-  } else {
-    hipError_t e = ensure_dynamic_lds(&k_fine_tf<25, NW>, smem, &set25);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL((k_fine_tf<25, NW>), dim3(blocks), dim3(NW * 64), smem, st, win0, win1, m_max, d_count, frag, ln, out0, out1, pstat, d_status, start_log2_scale, d_lowered);
-  }
-  return (int)hipGetLastError();
+  hipError_t e = hipSuccess;
+  with_window(WW == 25 ? 5 : 7, [&](auto w) {
+    constexpr int kWW = decltype(w)::value * decltype(w)::value;
+    static unsigned long long lds_set = 0;      // (one per instantiation of this lambda, that is, per kernel)
+    e = ensure_dynamic_lds(&k_fine_tf<kWW, NW>, smem, &lds_set);
+    if (e != hipSuccess) return;
+    hipLaunchKernelGGL((k_fine_tf<kWW, NW>), dim3(blocks), dim3(NW * 64), smem, st, win0, win1, m_max, d_count, frag, ln, out0,
+                       out1, pstat, d_status, start_log2_scale, d_lowered);
+    e = hipGetLastError();
+  });
+  return (int)e;
 }
 
 extern "C" int fm_fine_transformer(const float* win0, const float* win1, int m_max, const int32_t* d_count, int WW, int Cf,

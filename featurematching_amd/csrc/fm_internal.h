@@ -4,18 +4,18 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "fmatch.h"
 
 namespace fm {
 
 constexpr int kPanelRows = 256;   // coarse rows (image-0 cells) one workgroup owns
-// column partials each panel writes (one per wave: 8 waves x 32 rows)
 constexpr int kColParts = 1;         // column partials per 256-row panel (the 8 waves' partials are folded in LDS)
 constexpr int kTieCap = 1023;        // listed tie losers per image; beyond it the gathers scan the match list
 constexpr int kTileCols = 64;     // coarse columns (image-1 cells) per streamed tile
-constexpr int kUnitsPerSplit = 64; // 32-column units one workgroup of the dense-path kernels covers at most (64-bit live mask)
 constexpr float kLog2e = 1.4426950408889634f;
-constexpr float kSkipLog2 = 32.f;    // terms more than 2^32 below every stabiliser are negligible (see coarse_sum_sparse.hip)
+constexpr float kSkipLog2 = 32.f;    // terms more than 2^32 below every stabiliser are negligible (see sig_threshold in coarse_screen.hip)
 // internal status bit (not reported): pass B's max-based screening overflowed a row's slots
 constexpr unsigned FM_INT_SCREEN_OVERFLOW = 16u;
 constexpr unsigned FM_INT_LOOKBACK_TIMEOUT = 64u;   // k_select: a predecessor's total never showed up (reported as FM_DEV_INTERNAL)
@@ -30,6 +30,25 @@ inline bool valid_channels(int c) { return c >= 4 && c <= 256 && c % 4 == 0; }
 inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 
 struct Span { size_t at, bytes; };           // bytes [at, at + bytes) of a workspace
+template <typename T>
+inline T* span_ptr(void* base, const Span& s) { return reinterpret_cast<T*>(static_cast<char*>(base) + s.at); }
+
+// A runtime choice as a compile-time constant, so that a launch's argument list is written once: with_window calls
+// f(int_c<W>) for the window sizes the fine kernels are instantiated for and returns false (f not called) for any other
+// size; which status that is stays with the entry point's own checks.
+template <int V> using int_c = std::integral_constant<int, V>;
+template <typename F>
+inline bool with_window(int W, F&& f) {
+  if (W == 5) f(int_c<5>{});
+  else if (W == 7) f(int_c<7>{});
+  else return false;
+  return true;
+}
+
+// what every window-crop entry point asks of the batch, a fine map, the stride and the list capacity (else FM_E_SHAPE)
+inline bool crop_shape_ok(int N, int Hf, int Wf, int stride, int m_max) {
+  return N > 0 && Hf > 0 && Wf > 0 && stride > 0 && m_max >= 0;
+}
 
 // Device workspace of the coarse stage; all offsets in bytes from the base.  The regions the common path uses come
 // first (`common_total` bytes); the float16 planes, the dense sum kernel's partials and candidate set and the
@@ -64,8 +83,9 @@ struct CoarseWs {
   size_t bstat0, bstat1;                      // float4 per 32-row block: {largest L1 norm (+inf: a bad value), largest
                                               // clipped L1 mass sum_k max(|x_k| - 127 sigma, 0), largest |x|, 0}
   size_t emarg;                               // [N] log2-domain bound of k * |screening product - exact product|
-  size_t rowS, colS;                          // (round 3: partial sum-exp of the sparse sum kernel; empty since the
-                                              // screening kernel hands over lists of significant entries)
+  size_t rowS, colS;                          // zero-length (the sparse sum kernel's partial sum-exp, until the screening
+                                              // kernel handed over lists of significant entries); kept because
+                                              // fm_debug_coarse_layout exports its slots by index
   size_t nmr, nmc;                            // -stabiliser*log2e per row / column
   size_t umax;                                // unit maxima [N][Lp/32][Sp/32] of the integer screening product (as float)
   size_t cand_j, cand_x;                      // k_screen: every significant entry of a row (column, exact dot product)

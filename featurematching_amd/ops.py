@@ -697,10 +697,12 @@ def _crop_layout(feat_f: torch.Tensor) -> int:
 
 
 def gather_windows_backward(d_win: torch.Tensor, b_ids: torch.Tensor, ids: torch.Tensor, shape, w: int, stride: int,
-                            w_c: int, h_c: int, pad: int = 2, layout: int = 0) -> torch.Tensor:
+                            w_c: int, h_c: int, pad: int = 2, layout: int = 0,
+                            count: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The adjoint of gather_windows (fm_gather_windows_backward): d_feat float32 of the logical shape [N, Cf, Hf, Wf]
     (stored channels-last for layout 1), the sum of d_win over every (match, window position) that read each pixel, in
-    a fixed order (bitwise reproducible)."""
+    a fixed order (bitwise reproducible).  count = the coarse stage's device-side int32 count: rows at or beyond
+    min(count[0], M) contribute nothing (no host sync)."""
     lib = _lib.load()
     n, cf, hf, wf = shape
     dev = d_win.device
@@ -714,10 +716,10 @@ def gather_windows_backward(d_win: torch.Tensor, b_ids: torch.Tensor, ids: torch
     bb, ii = b64(b_ids), b64(ids)
     need = int(lib.fm_gather_windows_backward_workspace_bytes(n, int(h_c), int(w_c), m_max))
     ws, wsp = _aligned_workspace(need, dev)
-    _lib.check(lib.fm_gather_windows_backward(_ptr(g), _ptr(bb), _ptr(ii), None, m_max, n, cf, hf, wf, layout, w, stride,
-                                              pad, int(h_c), int(w_c), wsp, need, _ptr(d_feat), _stream(dev)),
+    _lib.check(lib.fm_gather_windows_backward(_ptr(g), _ptr(bb), _ptr(ii), _ptr(count), m_max, n, cf, hf, wf, layout, w,
+                                              stride, pad, int(h_c), int(w_c), wsp, need, _ptr(d_feat), _stream(dev)),
                "fm_gather_windows_backward")
-    d_feat._keep = (ws, g, bb, ii)
+    d_feat._keep = (ws, g, bb, ii, count)
     return d_feat
 
 

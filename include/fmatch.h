@@ -247,7 +247,15 @@ int fm_read_count_info(const int32_t* d_count, int cap, int32_t* m_out, int32_t*
  * W in {5,7} a copy in 16-byte chunks, one wave per window: a window row is W*256
  * contiguous bytes there).
  * The number of windows is min(*d_count, m_max) when d_count != NULL (device
- * side, no host sync), else m_max.  out [m_max, W*W, Cf] float32.
+ * side, no host sync), else m_max.  out [m_max, W*W, Cf] float32; rows at or beyond
+ * that number are left untouched.  The counted rows must be valid (b in [0, N), id a
+ * cell of the coarse grid): the crop does not check them.
+ * Shapes: Cf <= 512, W <= 15, any stride >= 1, any pad >= 0, any w_c >= 1 (the grid may
+ * overhang the map: windows wholly in the padding are all zero); layout 1 needs Cf % 4 == 0.
+ * The NCHW crop outside the 64-channel fast path (float32, Cf = 64, W in {5,7}) stages one
+ * window in LDS, W*W*(Cf+1)*4 bytes: beyond 64 KiB (e.g. W = 15 with Cf > 71, W = 7 with
+ * Cf > 333) it answers FM_E_UNSUPPORTED - hand such a map over channels-last (layout 1),
+ * which has no such limit.
  */
 int fm_gather_windows(const float* feat_f, int N, int Cf, int Hf, int Wf, int layout,
                       int W, int stride, int pad, int w_c,
@@ -268,7 +276,9 @@ int fm_gather_windows_dtype(const void* feat_f, int map_dtype, int N, int Cf, in
  * cell of THIS image (0 = unmatched); ties[0] = number of matches that lost their cell to an exactly
  * tied match, ties[1..] = their indices (at most 1023 listed; beyond that the kernel scans the match
  * list).  fm_coarse_cell_maps returns the maps and tie lists the coarse stage keeps in its workspace
- * (valid until the workspace is reused).  Same outputs as fm_gather_windows.
+ * (valid until the workspace is reused).  Same outputs as fm_gather_windows, rows at or beyond
+ * min(*d_count, m_max) included: they are left untouched whatever the cell map and the tie list say
+ * about them (this holds for fm_gather_merge_windows and fm_gather_windows_pair too).
  * FM_E_UNSUPPORTED when the shape is outside this path: call fm_gather_windows instead.
  */
 int fm_coarse_cell_maps(void* workspace, int N, int L, int S, int C, int cand_slots,
@@ -350,9 +360,12 @@ int fm_fine_match(const float* win0, const float* win1, int m_max, const int32_t
  *                            Window positions in the padding contribute nothing; rows whose (b, id) lies outside
  *                            [0, N) x [0, h_c*w_c) read nothing and are skipped.  Gather form (a CSR of matches per
  *                            (b, cell) in the workspace; each pixel sums its covering cells in row-major order and each
- *                            cell's matches in ascending index).  workspace: fm_gather_windows_backward_workspace_bytes
- *                            bytes [dev], 256-byte aligned.  Any Cf <= 512, W <= 15 (else FM_E_UNSUPPORTED); m_max = 0:
- *                            returns at once, d_feat untouched.
+ *                            cell's matches in ascending index).  Rows at or beyond min(*d_count, m_max) (d_count
+ *                            may be NULL) contribute nothing, as if the list ended there: *d_count = 0 gives an all-zero
+ *                            d_feat.  workspace: fm_gather_windows_backward_workspace_bytes
+ *                            bytes [dev], 256-byte aligned.  Any Cf <= 512, W <= 15 (else FM_E_UNSUPPORTED), any stride,
+ *                            pad and layout (no LDS limit, no Cf % 4 rule here); m_max = 0: returns at once, d_feat
+ *                            untouched.
  * Statuses: FM_E_NULL (a required pointer is NULL; d_count may be NULL), FM_E_SHAPE (m_max < 0, non-positive sizes),
  * FM_E_UNSUPPORTED, FM_E_WORKSPACE (too small or misaligned), or a hipError_t.  The *_workspace_bytes functions return 0
  * for invalid sizes.

@@ -55,6 +55,69 @@ def fine_backward(win0, win1, mix0, mix1, scale, d_out0, d_out1):
     return d_win[0], d_win[1], d_mix[0], d_mix[1]
 
 
+# (Cf, W, stride, pad) of the general crop tests (tests/test_crop_ref.py pins the yardsticks at these,
+# tests/test_gpu_crop_general.py runs the kernels at them), on a 2 x Cf x 37 x 45 map
+CROP_CASES = [
+    (64, 7, 4, 2),      # the fast paths, as the anchor
+    (64, 7, 4, 3),      # fast kernels with a pad other than 2
+    (64, 5, 2, 2),      # fast kernels, overlapping windows: three covering cells per axis in the backward
+    (32, 3, 2, 1),      # Cf < 64: idle lanes of the backward's wave
+    (20, 9, 8, 4),      # ... a large stride under a large window
+    (20, 3, 8, 1),      # ... windows narrower than the stride: pixels between the windows
+    (65, 7, 4, 2),      # k_crop_bwd<2>: the first channel past a wave
+    (96, 7, 1, 3),      # ... stride 1: 49 covering cells
+    (128, 7, 4, 3),
+    (130, 5, 4, 0),     # k_crop_bwd<4>; pad 0: no negative origin
+    (200, 7, 3, 2),     # ... a stride that does not divide W
+    (256, 5, 2, 2),
+    (260, 3, 1, 1),     # k_crop_bwd<8>
+    (512, 3, 1, 1),     # ... the ABI's upper Cf
+    (6, 15, 4, 7),      # the ABI's upper W; Cf not a multiple of 4: NCHW only in the forward
+    (64, 15, 4, 7),     # the largest NCHW tile of the generic crop that fits the LDS (58 500 bytes)
+    (1, 1, 1, 0),       # degenerate sizes
+]
+CROP_MAP = (2, 37, 45)  # N, Hf, Wf: odd on purpose, Wf no multiple of the backward's 64 / 32 / 16 / 8 pixel tiles
+
+
+def unfold_grid(hf: int, wf: int, w: int, stride: int, pad: int):
+    """(h_c, w_c) of F.unfold(kernel_size=w, stride=stride, padding=pad) on an hf x wf map"""
+    return (hf + 2 * pad - w) // stride + 1, (wf + 2 * pad - w) // stride + 1
+
+
+def crop_unfold(feat, b_ids, ids, w: int, stride: int, pad: int, h_c: int, w_c: int):
+    """[M, W*W, Cf]: the crop through torch's own unfold (differentiable; the float32 autograd route the backward's
+    tolerance is measured with).  The map is zero-padded by `pad` on the top / left and by whatever the h_c x w_c grid
+    needs on the bottom / right, so a grid that overhangs the map is served too"""
+    n, cf, hf, wf = feat.shape
+    pb = max(0, (h_c - 1) * stride + w - hf - pad)
+    pr = max(0, (w_c - 1) * stride + w - wf - pad)
+    big = torch.nn.functional.pad(feat, (pad, pr, pad, pb))
+    w_u = (big.shape[3] - w) // stride + 1                      # unfold's own grid width (>= w_c)
+    u = torch.nn.functional.unfold(big, kernel_size=w, stride=stride)       # [N, Cf*WW, L], rows c * WW + r
+    u = u.view(n, cf, w * w, -1).permute(0, 3, 2, 1)
+    b_ids, ids = b_ids.long(), ids.long()
+    return u[b_ids, (ids // w_c) * w_u + ids % w_c]
+
+
+def crop_ref(feat, b_ids, ids, w: int, stride: int, pad: int, w_c: int):
+    """[M, W*W, Cf] in feat's dtype: the window crop by plain index arithmetic, y = (id // w_c) * stride - pad + wy,
+    x = (id % w_c) * stride - pad + wx, position wy * W + wx, zero outside the map.  Any pad, any grid: nothing assumes
+    that the coarse grid times the stride equals the map"""
+    feat = feat.cpu()
+    n, cf, hf, wf = feat.shape
+    b_ids, ids = b_ids.long().cpu(), ids.long().cpu()
+    wy = torch.arange(w).repeat_interleave(w)
+    wx = torch.arange(w).repeat(w)
+    y = (ids // w_c)[:, None] * stride - pad + wy[None, :]
+    x = (ids % w_c)[:, None] * stride - pad + wx[None, :]
+    ok = (y >= 0) & (y < hf) & (x >= 0) & (x < wf)
+    pix = (b_ids[:, None] * hf + y) * wf + x                     # [M, WW] flat (b, y, x)
+    rows = feat.permute(0, 2, 3, 1).reshape(n * hf * wf, cf)
+    out = torch.zeros(ids.shape[0], w * w, cf, dtype=feat.dtype)
+    out[ok] = rows[pix[ok]]
+    return out
+
+
 def crop_adjoint(d_win, b_ids, ids, shape, w: int, stride: int, w_c: int, pad: int = 2):
     """(d_feat, reads) float64 [N, Cf, Hf, Wf] by index_add: the sum of d_win over every (match, window position) that
     read each pixel, and how many reads each pixel had"""

@@ -105,6 +105,51 @@ def test_workspace_query_and_argument_checks():
     assert lib.fm_merge_pack_weights(one, 32, one, null) == -3
 
 
+def test_crop_shape_limits():
+    """What the window crops refuse, with pointers that are never dereferenced: every call returns before it launches.
+    (The accepted side of the NCHW LDS limit - W = 15, Cf = 64, 58 500 bytes - launches: tests/test_gpu_crop_general.py.)"""
+    lib = _lib.load()
+    one = C.c_void_p(256)
+
+    def crop(cf, w, layout=0, dtype=None, stride=4, w_c=2):
+        tail = (1, cf, 8, 8, layout, w, stride, 2, w_c, one, one, None, 3, one, None)
+        return lib.fm_gather_windows(one, *tail) if dtype is None else lib.fm_gather_windows_dtype(one, dtype, *tail)
+
+    for dtype in (None, _lib.FM_F32, _lib.FM_F16, _lib.FM_BF16):
+        assert crop(64, 16, dtype=dtype) == -3                     # W > 15
+        assert crop(513, 7, dtype=dtype) == -3                     # Cf > 512
+        assert crop(513, 7, layout=1, dtype=dtype) == -3
+        assert crop(64, 7, layout=2, dtype=dtype) == -3            # unknown layout
+        assert crop(64, 7, layout=-1, dtype=dtype) == -3
+        assert crop(6, 7, layout=1, dtype=dtype) == -3             # channels-last reads four channels at a time
+        assert crop(66, 3, layout=1, dtype=dtype) == -3
+        # the generic NCHW crop stages one window in LDS, W*W*(Cf+1)*4 bytes: 64 KiB at the most
+        assert crop(128, 15, dtype=dtype) == -3                    # 116 100 bytes
+        assert crop(512, 7, dtype=dtype) == -3                     # 100 548 bytes
+        assert crop(72, 15, dtype=dtype) == -3                     # 65 700 bytes: the first Cf beyond the limit at W = 15
+        assert crop(334, 7, dtype=dtype) == -3                     # 65 660 bytes: ... at W = 7
+        assert crop(64, 7, stride=0, dtype=dtype) == -2
+        assert crop(64, 7, w_c=0, dtype=dtype) == -2
+        assert crop(0, 7, dtype=dtype) == -2
+        assert crop(64, 0, dtype=dtype) == -2
+    assert crop(64, 7, dtype=3) == -3                              # unknown element type
+    # the 64-channel entry points: Cf = 64 and W in {5, 7} only
+    for cf, w in ((32, 7), (64, 3), (32, 3), (128, 5), (64, 15)):
+        assert lib.fm_gather_windows_cells(one, 1, cf, 8, 8, w, 4, 2, 2, 2, one, 4, one, one, one, None, 3, one, None) == -3
+        for cell, ties in ((None, None), (one, one)):              # list order and cell order
+            assert lib.fm_gather_merge_windows(one, 1, cf, 8, 8, w, 4, 2, 2, 2, cell, 4, ties, one, one, one, one, None, 3,
+                                               one, None) == -3
+        for packed in (None, one):                                 # plain and merged
+            assert lib.fm_gather_windows_pair(one, one, 1, cf, 8, 8, 8, 8, w, 4, 2, 2, 2, 2, 2, one, 4, one, one, 4, one,
+                                              packed, one, one, one, one, one, None, 3, one, one, None) == -3
+        for layout in (0, 1, _lib.FM_LAYOUT_NCHW_PREPARED):
+            assert lib.fm_fine_match_maps(one, one, layout, 1, cf, 8, 8, 8, 8, w, 4, 2, 2, 2, one, one, one, None, 3, one,
+                                          one, one, one, 2.0, one, one, one, None) == -3
+            for dtype in (_lib.FM_F32, _lib.FM_F16, _lib.FM_BF16):
+                assert lib.fm_fine_match_maps_dtype(one, one, dtype, layout, 1, cf, 8, 8, 8, 8, w, 4, 2, 2, 2, one, one,
+                                                    one, None, 3, one, one, one, one, 2.0, one, one, one, None) == -3
+
+
 def test_debug_entry_points_validate_their_shapes():
     """The diagnostic entry points make the same N/L/S/C/slots checks as the product ones (a zero N used to reach
     an integer division on the host)."""

@@ -49,6 +49,24 @@ def test_argument_checks():
     assert _crop(lib, 8, layout=2) == FM_E_UNSUPPORTED
 
 
+def test_crop_backward_shape_limits():
+    """the crop backward takes any Cf <= 512 and W <= 15 in both layouts (no Cf % 4 rule, no LDS limit: those belong to
+    the forward); what it refuses is refused before anything launches"""
+    lib = _lib.load()
+    for layout in (0, 1):
+        assert _crop(lib, 8, cf=513, layout=layout) == FM_E_UNSUPPORTED
+        assert _crop(lib, 8, w=16, layout=layout) == FM_E_UNSUPPORTED
+        assert _crop(lib, 8, cf=0, layout=layout) == FM_E_SHAPE
+        assert _crop(lib, 8, w=0, layout=layout) == FM_E_SHAPE
+    assert _crop(lib, 8, layout=-1) == FM_E_UNSUPPORTED
+    # the workspace is checked after the shape: too small, misaligned
+    args = lambda ws, nbytes: (FAKE, FAKE, FAKE, None, 8, 1, 6, 120, 160, 1, 15, 4, 7, 30, 40, ws, nbytes, FAKE, None)
+    need = lib.fm_gather_windows_backward_workspace_bytes(1, 30, 40, 8)
+    assert need > 0
+    assert lib.fm_gather_windows_backward(*args(FAKE, need - 1)) == -4
+    assert lib.fm_gather_windows_backward(*args(C.c_void_p(264), need)) == -4
+
+
 def test_workspace_bytes_monotone_in_m():
     lib = _lib.load()
     for ww in (25, 49):

@@ -167,14 +167,10 @@ __device__ __forceinline__ void wave_load_window64(const float* src, int Hf, int
   __builtin_amdgcn_wave_barrier();       // same-wave LDS accesses are processed in order: no s_barrier needed
 }
 
-template <int W, bool MERGE = false>
-__device__ __forceinline__ void wave_copy_window64(const float* src, int Hf, int Wf, int oy, int ox,
-                                                   float* __restrict__ dst, float* tile, int lane,
-                                                   const half8* __restrict__ wpack = nullptr,
-                                                   const float* __restrict__ ctx_row = nullptr) {
+// the tile [position][channel] leaves as one contiguous window record [WW][64] in 16-byte stores
+template <int W>
+__device__ __forceinline__ void wave_store_tile64(const float* tile, float* __restrict__ dst, int lane) {
   constexpr int CF = 64, WW = W * W, TOTAL = CF * WW, PITCH = CF + 4;
-  wave_load_window64<W>(src, Hf, Wf, oy, ox, tile, lane);
-  if (MERGE) wave_merge_tile<W>(tile, lane, wpack, ctx_row);
   float4* dst4 = reinterpret_cast<float4*>(dst);
 #pragma unroll
   for (int it = 0; it < (TOTAL / 4 + 63) / 64; ++it) {
@@ -189,6 +185,16 @@ __device__ __forceinline__ void wave_copy_window64(const float* src, int Hf, int
     }
   }
   __builtin_amdgcn_wave_barrier();       // the tile may be refilled by this wave right away
+}
+
+template <int W, bool MERGE = false>
+__device__ __forceinline__ void wave_copy_window64(const float* src, int Hf, int Wf, int oy, int ox,
+                                                   float* __restrict__ dst, float* tile, int lane,
+                                                   const half8* __restrict__ wpack = nullptr,
+                                                   const float* __restrict__ ctx_row = nullptr) {
+  wave_load_window64<W>(src, Hf, Wf, oy, ox, tile, lane);
+  if (MERGE) wave_merge_tile<W>(tile, lane, wpack, ctx_row);
+  wave_store_tile64<W>(tile, dst, lane);
 }
 
 constexpr int kGatherTileFloats(int W) { return W * W * 68; }
@@ -507,6 +513,71 @@ __global__ __launch_bounds__(256) void k_gather_nhwc64(const float* __restrict__
   }
 }
 
+// k_gather_merge_nhwc64<W, DT>: the crop fused with the context merge (wave_merge_tile) for channels-last maps of
+// float32 / float16 / bfloat16 elements.  One wave per window, four per workgroup, no workgroup barrier (the shape of
+// k_gather_nchw64<W, true>); list order, an XCD a contiguous range of the live windows (a window is W rows of W x 256
+// contiguous bytes, see above: no cell-ordered walk needed); blockIdx.y = image, as in k_gather_cellorder64.  The loader
+// is k_gather_nhwc64's - one chunk of four channels per lane and step (16 bytes, or 8 bytes of a half-precision map,
+// widened exactly), every load of the window in flight before the first use, clamped address + select for the zero
+// padding - and fills the wave-private tile [position][channel] (chunk k belongs to position k / 16, channels
+// 4 * (k % 16) ..).  From there on the window takes the NCHW kernel's path instruction for instruction, so the
+// outputs are bit-identical to k_gather_nchw64<W, true> / k_gather_cellorder64<W, true> on the same logical tensor.
+struct MergeNhwcImage {
+  const void* feat; int Hf, Wf, w_c, cells;
+  const int64_t* ids; float* out; const float* ctx;
+};
+struct MergeNhwcArgs {
+  MergeNhwcImage im[2];
+  int stride, pad, m_max;
+  const int64_t* b_ids; const int32_t* d_count; const half8* wpack;
+};
+
+template <int W, int DT>
+__global__ __launch_bounds__(256) void k_gather_merge_nhwc64(MergeNhwcArgs a) {
+  constexpr int WW = W * W, PITCH = 68;
+  constexpr int TOTAL16 = WW * 16;           // chunks of four channels per window: 400 / 784
+  constexpr int NIT = (TOTAL16 + 63) / 64;
+  using Chunk = typename std::conditional<DT == FM_F32, float4, uint2>::type;
+  __shared__ __attribute__((aligned(16))) float tile_all[4 * kGatherTileFloats(W)];
+  const MergeNhwcImage& I = a.im[blockIdx.y];
+  const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  float* tile = tile_all + wv * kGatherTileFloats(W);
+  const int M = a.d_count ? min(a.d_count[0], a.m_max) : a.m_max;
+  const int per = (M + 7) >> 3;
+  const int slot = (int)(blockIdx.x >> 3) * 4 + wv;
+  const int m = (blockIdx.x & 7) * per + slot;
+  if (slot >= per || m >= M) return;
+  const int b = __builtin_amdgcn_readfirstlane((int)a.b_ids[m]);
+  const int id = __builtin_amdgcn_readfirstlane((int)I.ids[m]);
+  const int cy = id / I.w_c;
+  const int oy = cy * a.stride - a.pad, ox = (id - cy * I.w_c) * a.stride - a.pad;
+  const Chunk* src = reinterpret_cast<const Chunk*>(I.feat) + (long)b * I.Hf * I.Wf * 16;
+  Chunk v[NIT];
+#pragma unroll
+  for (int it = 0; it < NIT; ++it) {
+    const int k = it * 64 + lane;
+    const int pos = k >> 4, wy = pos / W;
+    const int y = oy + wy, x = ox + (pos - wy * W);
+    const bool ok = k < TOTAL16 && y >= 0 && y < I.Hf && x >= 0 && x < I.Wf;
+    // (clamped address + select: no load behind a branch)
+    const Chunk t = src[ok ? ((long)y * I.Wf + x) * 16 + (k & 15) : 0];
+    if constexpr (DT == FM_F32) v[it] = ok ? t : make_float4(0.f, 0.f, 0.f, 0.f);
+    else v[it] = ok ? t : make_uint2(0u, 0u);
+  }
+#pragma unroll
+  for (int it = 0; it < NIT; ++it) {
+    const int k = it * 64 + lane;
+    if (k < TOTAL16) {
+      float4* slot4 = reinterpret_cast<float4*>(tile + (k >> 4) * PITCH + (k & 15) * 4);
+      if constexpr (DT == FM_F32) *slot4 = v[it];
+      else *slot4 = half4_to_float4(v[it], DT);
+    }
+  }
+  __builtin_amdgcn_wave_barrier();       // same-wave LDS accesses are processed in order: no s_barrier needed
+  wave_merge_tile<W>(tile, lane, a.wpack, I.ctx + ((long)b * I.cells + id) * 64);
+  wave_store_tile64<W>(tile, I.out + (long)m * WW * 64, lane);
+}
+
 // NCHW0: image 0 is still in the reference's NCHW layout - its windows are visited in raster order here (the match list
 // is sorted by the image-0 cell), which is the access pattern the NCHW loader of the cell-ordered crop copes with, so only
 // image 1 (whose windows land wherever the partners are) needs the channels-last copy.
@@ -782,6 +853,42 @@ extern "C" int fm_gather_windows_pair(const float* feat_f0, const float* feat_f1
                                pad, m_max, b_ids, d_count, packed_w);
   const long t0 = (long)N * h0c * w0c, t1 = (long)N * h1c * w1c;
   return launch_cells64(W, 2, t0 > t1 ? t0 : t1, a, (hipStream_t)stream);
+}
+
+static MergeNhwcImage merge_nhwc_image(const void* feat, int Hf, int Wf, int h_c, int w_c, const int64_t* ids, float* out,
+                                       const float* ctx) {
+  MergeNhwcImage im;
+  im.feat = feat; im.Hf = Hf; im.Wf = Wf; im.w_c = w_c; im.cells = h_c * w_c; im.ids = ids; im.out = out; im.ctx = ctx;
+  return im;
+}
+
+extern "C" int fm_gather_merge_windows_nhwc(const void* feat_f0, const void* feat_f1, int map_dtype, int N, int Cf, int Hf0,
+                                            int Wf0, int Hf1, int Wf1, int W, int stride, int pad, int h0c, int w0c,
+                                            int h1c, int w1c, const void* packed_w, const float* ctx0, const float* ctx1,
+                                            const int64_t* b_ids, const int64_t* i_ids, const int64_t* j_ids,
+                                            const int32_t* d_count, int m_max, float* out0, float* out1, void* stream) {
+  if (m_max == 0) return FM_OK;
+  const bool pair = feat_f1 != nullptr;
+  if (!feat_f0 || !packed_w || !ctx0 || !b_ids || !i_ids || !out0) return FM_E_NULL;
+  if (pair && (!ctx1 || !j_ids || !out1)) return FM_E_NULL;
+  if (!crop_shape_ok(N, Hf0, Wf0, stride, m_max) || h0c <= 0 || w0c <= 0) return FM_E_SHAPE;
+  if (pair && (!crop_shape_ok(N, Hf1, Wf1, stride, m_max) || h1c <= 0 || w1c <= 0)) return FM_E_SHAPE;
+  if (map_dtype != FM_F32 && map_dtype != FM_F16 && map_dtype != FM_BF16) return FM_E_UNSUPPORTED;
+  if (Cf != 64 || (W != 5 && W != 7)) return FM_E_UNSUPPORTED;
+  MergeNhwcArgs a;
+  a.im[0] = merge_nhwc_image(feat_f0, Hf0, Wf0, h0c, w0c, i_ids, out0, ctx0);
+  a.im[1] = pair ? merge_nhwc_image(feat_f1, Hf1, Wf1, h1c, w1c, j_ids, out1, ctx1) : a.im[0];
+  a.stride = stride; a.pad = pad; a.m_max = m_max; a.b_ids = b_ids; a.d_count = d_count; a.wpack = (const half8*)packed_w;
+  with_window(W, [&](auto w) {
+    auto launch = [&](auto dt) {
+      hipLaunchKernelGGL((k_gather_merge_nhwc64<decltype(w)::value, decltype(dt)::value>),
+                         dim3(list_blocks(m_max), pair ? 2 : 1), dim3(256), 0, (hipStream_t)stream, a);
+    };
+    if (map_dtype == FM_F16) launch(int_c<FM_F16>{});
+    else if (map_dtype == FM_BF16) launch(int_c<FM_BF16>{});
+    else launch(int_c<FM_F32>{});
+  });
+  return (int)hipGetLastError();
 }
 
 extern "C" int fm_fine_match(const float* win0, const float* win1, int m_max, const int32_t* d_count, int WW, int Cf,

@@ -125,10 +125,18 @@ class FinePreprocess(nn.Module):
 
     def _fused_ok(self, feat_f0, feat_f1, feat_c0, feat_c1, W) -> bool:
         """The fused crop+merge kernel serves eval mode (no autograd through the two Linear layers: inputs that
-        require grad under grad mode take the torch layers) on NCHW maps with 64 fine channels and W in {5,7}."""
+        require grad under grad mode take the torch layers) on maps with 64 fine channels and W in {5,7}: both maps
+        NCHW-contiguous, or both channels-last with one element type out of float32 / float16 / bfloat16 (read in
+        place: no layout copy, no up-cast pass)."""
         wants_grad = torch.is_grad_enabled() and any(t.requires_grad for t in (feat_f0, feat_f1, feat_c0, feat_c1))
+        nchw = feat_f0.is_contiguous() and feat_f1.is_contiguous()
         return self.fused_merge and not self.training and not wants_grad and self.d_model_f == 64 and W in (5, 7) \
-            and feat_f0.shape[1] == 64 and feat_f0.is_contiguous() and feat_f1.is_contiguous()
+            and feat_f0.shape[1] == 64 and (nchw or self._both_channels_last(feat_f0, feat_f1))
+
+    @staticmethod
+    def _both_channels_last(feat_f0, feat_f1) -> bool:
+        return feat_f0.is_cuda and feat_f0.dtype == feat_f1.dtype and ops.merge_reads_in_place(feat_f0) \
+            and ops.merge_reads_in_place(feat_f1)
 
     def _merge_constants(self):
         """(packed W_w fragments, E = W_c . down_proj.weight [64, C], e = W_c . down_proj.bias + merge bias),
@@ -188,9 +196,13 @@ class FinePreprocess(nn.Module):
                 else:
                     ctx0 = F.linear(feat_c0.float(), e_w, e_b)      # [N, L, 64] = W_c.(down_proj(feat_c)) + bias
                     ctx1 = F.linear(feat_c1.float(), e_w, e_b)
-                if cells0 is not None and feat_f1.shape[1] == 64:
+                # one launch for both images: cell order on NCHW maps (needs this coarse call's cell maps), list order on
+                # channels-last maps (fm_gather_merge_windows_nhwc reads them in place and needs no cell map)
+                nhwc = self._both_channels_last(feat_f0, feat_f1)
+                if (cells0 is not None or nhwc) and feat_f1.shape[1] == 64:
                     win0, win1 = ops.gather_windows_pair(feat_f0, feat_f1, b_ids, i_ids, j_ids, W, stride, hw0_c, hw1_c,
-                                                         (cells0, cells1), packed_w=packed, ctx0=ctx0, ctx1=ctx1)
+                                                         None if nhwc else (cells0, cells1), packed_w=packed, ctx0=ctx0,
+                                                         ctx1=ctx1)
                 else:
                     win0 = ops.gather_merge_windows(feat_f0, packed, ctx0, b_ids, i_ids, W, stride, hw0_c[0], hw0_c[1])
                     win1 = ops.gather_merge_windows(feat_f1, packed, ctx1, b_ids, j_ids, W, stride, hw1_c[0], hw1_c[1])

@@ -564,18 +564,29 @@ def pack_merge_weights(merge_w: torch.Tensor) -> torch.Tensor:
     return packed
 
 
+def merge_reads_in_place(feat_f: torch.Tensor) -> bool:
+    """A channels-last float32 / float16 / bfloat16 map goes to fm_gather_merge_windows_nhwc as it is (no layout
+    copy, no up-cast pass); every other map takes the NCHW float32 kernels."""
+    return (feat_f.dim() == 4 and feat_f.dtype in _DTYPES and not feat_f.is_contiguous()
+            and feat_f.is_contiguous(memory_format=torch.channels_last))
+
+
 def gather_merge_windows(feat_f: torch.Tensor, packed_w: torch.Tensor, ctx_bias: torch.Tensor, b_ids: torch.Tensor,
                          ids: torch.Tensor, w: int, stride: int, h_c: int, w_c: int, pad: int = 2,
                          count: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
                          cells=None) -> torch.Tensor:
     """Window crop fused with FinePreprocess's context merge (fine_preprocess.py:43-60): returns
     merge_feat(cat[window, down_proj(feat_c)]) for the selected cells, [M, WW, 64].  ctx_bias [N, h_c*w_c, 64]
-    is the position-independent half (W_c . down_proj(feat_c) + bias) per coarse cell."""
+    is the position-independent half (W_c . down_proj(feat_c) + bias) per coarse cell.
+    A channels-last map (float32, float16 or bfloat16) is read in place, in list order (`cells` is ignored); the
+    result is bit-identical to the call on the same float32 values stored NCHW."""
     lib = _lib.load()
     if not feat_f.is_cuda:
         raise RuntimeError("feat_f must live on the GPU: the HIP path has no CPU fallback")
     n, cf, hf, wf = feat_f.shape
-    feat_f = _f32c(feat_f, "feat_f")
+    nhwc = merge_reads_in_place(feat_f)
+    if not nhwc:
+        feat_f = _f32c(feat_f, "feat_f")
     ctx_bias = _f32c(ctx_bias, "ctx_bias")
     if tuple(ctx_bias.shape) != (n, h_c * w_c, 64):
         raise ValueError(f"ctx_bias must be [{n}, {h_c * w_c}, 64], got {tuple(ctx_bias.shape)}")
@@ -583,6 +594,13 @@ def gather_merge_windows(feat_f: torch.Tensor, packed_w: torch.Tensor, ctx_bias:
     if out is None:
         out = torch.empty(m_max, w * w, cf, dtype=torch.float32, device=feat_f.device)
     if m_max == 0:
+        return out
+    if nhwc:        # list order (`cells` is not needed: a channels-last window is W contiguous runs wherever it lies)
+        st = lib.fm_gather_merge_windows_nhwc(_ptr(feat_f), None, _DTYPES[feat_f.dtype], n, cf, hf, wf, 0, 0, w, stride,
+                                              pad, int(h_c), int(w_c), 0, 0, _ptr(packed_w), _ptr(ctx_bias), None,
+                                              _ptr(b_ids), _ptr(ids), None, _ptr(count), m_max, _ptr(out), None,
+                                              _stream(feat_f.device))
+        _lib.check(st, "fm_gather_merge_windows_nhwc")
         return out
     cm, cp, ct = (C.c_void_p(cells[0]), int(cells[1]), C.c_void_p(cells[2])) if cells is not None else (None, 0, None)
     st = lib.fm_gather_merge_windows(_ptr(feat_f), n, cf, hf, wf, w, stride, pad, int(h_c), int(w_c), cm, cp, ct,
@@ -596,9 +614,13 @@ def gather_windows_pair(feat_f0: torch.Tensor, feat_f1: torch.Tensor, b_ids, i_i
                         hw0_c, hw1_c, cells, pad: int = 2, count: Optional[torch.Tensor] = None, out0=None, out1=None,
                         packed_w: Optional[torch.Tensor] = None, ctx0=None, ctx1=None):
     """Both images' window crops in one launch (cell order; cells = CoarseBuffers.cell_maps()); with
-    packed_w / ctx0 / ctx1 the crop is fused with the context merge.  NCHW maps, Cf = 64, W in {5,7}."""
+    packed_w / ctx0 / ctx1 the crop is fused with the context merge.  NCHW maps, Cf = 64, W in {5,7}.
+    The fused form also reads two channels-last maps of one element type (float32, float16, bfloat16) in place, in
+    list order (`cells` is ignored, may be None): same outputs, bit for bit."""
     lib = _lib.load()
-    f0, f1 = _f32c(feat_f0, "feat_f0"), _f32c(feat_f1, "feat_f1")
+    nhwc = packed_w is not None and feat_f0.is_cuda and feat_f0.dtype == feat_f1.dtype \
+        and merge_reads_in_place(feat_f0) and merge_reads_in_place(feat_f1)
+    f0, f1 = (feat_f0, feat_f1) if nhwc else (_f32c(feat_f0, "feat_f0"), _f32c(feat_f1, "feat_f1"))
     n, cf, hf0, wf0 = f0.shape
     hf1, wf1 = f1.shape[2:]
     m_max = int(b_ids.shape[0])
@@ -610,6 +632,16 @@ def gather_windows_pair(feat_f0: torch.Tensor, feat_f1: torch.Tensor, b_ids, i_i
         return out0, out1
     if packed_w is not None:
         ctx0, ctx1 = _f32c(ctx0, "ctx0"), _f32c(ctx1, "ctx1")
+    if nhwc:
+        for name, ctx, hw in (("ctx0", ctx0, hw0_c), ("ctx1", ctx1, hw1_c)):
+            if tuple(ctx.shape) != (n, int(hw[0]) * int(hw[1]), 64):
+                raise ValueError(f"{name} must be [{n}, {int(hw[0]) * int(hw[1])}, 64], got {tuple(ctx.shape)}")
+        st = lib.fm_gather_merge_windows_nhwc(_ptr(f0), _ptr(f1), _DTYPES[f0.dtype], n, cf, hf0, wf0, hf1, wf1, w, stride,
+                                              pad, int(hw0_c[0]), int(hw0_c[1]), int(hw1_c[0]), int(hw1_c[1]),
+                                              _ptr(packed_w), _ptr(ctx0), _ptr(ctx1), _ptr(b_ids), _ptr(i_ids),
+                                              _ptr(j_ids), _ptr(count), m_max, _ptr(out0), _ptr(out1), _stream(f0.device))
+        _lib.check(st, "fm_gather_merge_windows_nhwc")
+        return out0, out1
     (m0, p0, t0), (m1, p1, t1) = cells
     st = lib.fm_gather_windows_pair(_ptr(f0), _ptr(f1), n, cf, hf0, wf0, hf1, wf1, w, stride, pad, int(hw0_c[0]),
                                     int(hw0_c[1]), int(hw1_c[0]), int(hw1_c[1]), C.c_void_p(m0), int(p0), C.c_void_p(t0),

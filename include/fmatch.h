@@ -325,6 +325,25 @@ int fm_gather_windows_pair(const float* feat_f0, const float* feat_f1, int N, in
                            const int32_t* d_count, int m_max, float* out0, float* out1, void* stream);
 
 /*
+ * The crop fused with the context merge for CHANNELS-LAST maps: feat_f0 / feat_f1 are the storage
+ * [N, Hf, Wf, 64] of the logical [N, 64, Hf, Wf] tensors, elements of map_dtype (enum fm_dtype: float16 /
+ * bfloat16 maps are read as they are - every value is exact in float32 - no up-cast pass, no layout copy).
+ * One launch serves both images: out0 from feat_f0 / i_ids / ctx0, out1 from feat_f1 / j_ids / ctx1.
+ * feat_f1 == NULL means ONE image: feat_f1, ctx1, j_ids, out1, Hf1, Wf1, h1c and w1c are then ignored.
+ * packed_w (fm_merge_pack_weights), ctx0 / ctx1 ([N, h0c*w0c, 64] / [N, h1c*w1c, 64]) and the arithmetic are
+ * those of fm_gather_merge_windows: the outputs are bit-identical to that call on the same logical float32
+ * tensor stored NCHW.  Windows are visited in list order (a channels-last window is W runs of W*256 contiguous
+ * bytes wherever it lies: no cell map needed).  Rows at or beyond min(*d_count, m_max) are left untouched.
+ * Cf = 64, W in {5,7}, any map_dtype of the enum; else FM_E_UNSUPPORTED.
+ */
+int fm_gather_merge_windows_nhwc(const void* feat_f0, const void* feat_f1, int map_dtype, int N, int Cf,
+                                 int Hf0, int Wf0, int Hf1, int Wf1, int W, int stride, int pad,
+                                 int h0c, int w0c, int h1c, int w1c,
+                                 const void* packed_w, const float* ctx0, const float* ctx1,
+                                 const int64_t* b_ids, const int64_t* i_ids, const int64_t* j_ids,
+                                 const int32_t* d_count, int m_max, float* out0, float* out1, void* stream);
+
+/*
  * Fine stage (fine_matching_new.py:50-79): dual-direction window correlation,
  * softmax heat-map, spatial expectation, std.  win0/win1 [m_max, WW, Cf];
  * mix0/mix1 [dev] float32 [WW+1] = Linear(WW,1) weight then bias;

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Stage times of Matcher.forward_features (network/net.py:66-83) at 640x480 on one GPU: coarse context layers,
-coarse matching, crop + context merge, fine context layers, fine matching.  Event-timed, eager, one pair."""
+coarse matching, crop + context merge, fine context layers, fine matching.  Event-timed, eager, one pair.
+--channels-last hands forward_features channels-last views of the same maps (the crop + merge then reads them in place:
+fm_gather_merge_windows_nhwc)."""
 import argparse
 import os
 import sys
@@ -33,6 +35,7 @@ def main():
     ap.add_argument("--hc", type=int, default=60)
     ap.add_argument("--wc", type=int, default=80)
     ap.add_argument("--hip-only", action="store_true", help="skip the PyTorch-module comparison (counter runs)")
+    ap.add_argument("--channels-last", action="store_true", help="hand the coarse and fine maps over channels-last")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
@@ -45,6 +48,8 @@ def main():
     g = torch.Generator(device=dev).manual_seed(3)
     ff0 = torch.randn(n, 64, hc * 4, wc * 4, device=dev, generator=g)
     ff1 = torch.randn(n, 64, hc * 4, wc * 4, device=dev, generator=g)
+    if a.channels_last:
+        fc0, fc1, ff0, ff1 = (t.contiguous(memory_format=torch.channels_last) for t in (fc0, fc1, ff0, ff1))
     base = {'bs': n, 'hw0_i': (hc * 8, wc * 8), 'hw1_i': (hc * 8, wc * 8), 'hw0_c': (hc, wc), 'hw1_c': (hc, wc),
             'hw0_f': (hc * 4, wc * 4), 'hw1_f': (hc * 4, wc * 4)}
     with torch.no_grad():
@@ -64,8 +69,8 @@ def main():
             t_ftf_t, _ = timed(lambda: m.fine(w0, w1))
             m.fine.use_hip = True
     mm = int(d['b_ids'].numel())
-    print(f"forward_features N={n} {hc * 8}x{wc * 8}: {t_all:.3f} ms per call (matches through the random context layers: "
-          f"{int(data['b_ids'].numel())})")
+    print(f"forward_features N={n} {hc * 8}x{wc * 8} {'channels-last' if a.channels_last else 'NCHW'} maps: "
+          f"{t_all:.3f} ms per call (matches through the random context layers: {int(data['b_ids'].numel())})")
     print(f"  coarse context layers (8 x [N,{l},256]) {t_ctf:8.3f} ms")
     print(f"  coarse matching (M={mm})               {t_cm:8.3f} ms")
     print(f"  crop + context merge                   {t_fp:8.3f} ms")

@@ -25,6 +25,7 @@ FM_DEV_ALL_DENSE = 256                              # informational device statu
 FM_MODE_EXACT_SCREENING, FM_MODE_DENSE, FM_MODE_NO_CELL_MAPS, FM_MODE_EXACT_STEP, FM_MODE_STATS = 1, 2, 4, 8, 16   # `mode` bits
 FM_MODE_FLAT = 32
 FM_MODE_ALONE = 64      # hint about the device: this call has the GPU to itself (grids sized for the kernel alone)
+FM_LOSS_CROSS_ENTROPY, FM_LOSS_FOCAL = 0, 1              # enum fm_loss_kind
 FM_LAYOUT_NCHW_PREPARED = 2                         # fm_fine_match_maps*: image 1's channels-last copy is already in `scratch`
 
 _lib = None
@@ -66,6 +67,11 @@ SIGNATURES = {
     "fm_dual_softmax_backward": (_i, [_p, _p, _i, _i, _i, _i, _f, _p, _p, _i, _p, _p, _i, _p, _p, _p, _p, _i, _p, C.c_size_t, _p,
                                       _p, _p]),
     "fm_dual_softmax_backward_dense": (_i, [_p, _p, _i, _i, _i, _i, _f, _p, _p, _i, _p, _p, _i, _p, _p, C.c_size_t, _p, _p, _p]),
+    "fm_coarse_loss_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i]),
+    "fm_coarse_loss_forward": (_i, [_p, _p, _i, _i, _i, _i, _f, _p, _p, _i, _p, _p, _i, _i, _f, _f, _f, _f, _p, _p, _p, _i, _p,
+                                    C.c_size_t, _p, _p]),
+    "fm_coarse_loss_backward": (_i, [_p, _p, _i, _i, _i, _i, _f, _p, _p, _i, _p, _p, _i, _i, _f, _f, _f, _f, _p, _p, _p, _i, _p,
+                                     C.c_size_t, _p, _p, _p, _p]),
     "fm_gather_windows": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p, _p]),
     "fm_gather_windows_dtype": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p, _p]),
     "fm_coarse_cell_maps": (_i, [_p, _i, _i, _i, _i, _i, C.POINTER(_p), C.POINTER(_i), C.POINTER(_p),

@@ -1,0 +1,520 @@
+// The reference's coarse loss over ALL entries of conf_matrix (losses/loss.py:44-50 cross entropy, :62-67 focal with dense
+// supervision) and its gradient w.r.t. the descriptors, without conf_matrix, conf_matrix_gt or any other [N, L, S] array.
+//
+// With c = clamp(conf, lo, hi), P the distinct supervised entries, l_neg / l_pos the reference's per-entry terms,
+// wn = neg_weight / (N L S - |P|) and wp = pos_weight / |P|:
+//     loss = wn ( sum_all l_neg(c) - sum_P l_neg(c_e) ) + wp sum_P l_pos(c_e)
+//     G    = dloss/dconf = wn l_neg'(c) [lo <= conf <= hi]                               at every entry
+//                        + ( wp l_pos'(c_e) - wn l_neg'(c_e) ) [lo <= conf_e <= hi]      at e in P
+// The dense part of G is a function of conf alone, so the tiled sweep of dsm_grad.hip (a workgroup owns 32 rows, sweeps
+// the other image in 32-descriptor tiles, conf = A B from exact float32 dot products and the forward call's softmax
+// statistics) forms it in registers; the correction at P is a sparse g_e of the kind fm_dual_softmax_backward takes.
+// The backward of the dual softmax is linear in G: both parts land in the same row sums v and column sums u, and one
+// pair of gradient sweeps serves them together (D = 2 g conf - A u - B v; the entries' own 2 g_e c_e is k_dsm_entries).
+//
+//   forward : k_closs_entries (conf, l_pos, l_neg, g_e conf_e at P) -> k_dsm_uv -> k_closs_sweep<.., kSums> on side 0
+//             (sum of l_neg, v, u) -> k_closs_finish (the three numbers of loss_out, fixed order)
+//   backward: k_closs_sweep<.., kGrad> + k_closs_combine per side (the upstream gradient d_loss is read on the device by
+//             the combine) -> k_closs_scale + k_dsm_entries
+// k_closs_sweep is a sibling of k_dsm_bwd<C, kDsmDense> with G computed instead of loaded; that kernel is left as it is
+// (its three instantiations compile to the code they compiled to before - shared through inline functions, its tile
+// loads came out differently - so the tiling is repeated here).
+//
+// Two things differ from that kernel because the loss is not linear in conf:
+//   * the clamp's gate [lo <= conf <= hi] decides whether an entry has a gradient at all, and a peaked entry (conf within
+//     1e-6 of 1) is only on the right side of hi when the entry and its two denominators hold the SAME dot product.  The
+//     denominators come from the coarse stage's exact phase, so the sweep takes that phase's summation order (k_conf_at:
+//     16 partial sums over the float4 groups l, l + 16, l + 32, l + 48, folded as a balanced tree) instead of channel
+//     order.  The supervised entries (k_closs_entries) use the same order and the same expression, so l_neg(c_e) is bit for
+//     bit the term the sweep added;
+//   * the sum of l_neg mixes terms of 1e-6 with terms of 13.8 (a positive at the upper bound): it is kept in double from
+//     the first addition, so the subtraction above removes the positives' terms exactly.
+#include <utility>
+
+#include "fm_device.h"
+
+namespace fm {
+
+enum { kCeLoss = 0, kFocal2 = 1, kFocalG = 2 };     // cross entropy | focal, gamma = 2 (a multiply) | focal, any gamma > 0
+enum { kSums = 0, kGrad = 1 };
+
+struct LossParams {
+  float alpha, gamma;
+  float wn, wp;          // neg_weight / (N L S - |P|), pos_weight / |P|
+  float lo, hi;          // float32 roundings of 1e-6 and 1 - 1e-6: the reference runs its clamp in float32
+};
+
+// One of the reference's two per-entry terms: l = -alpha a^gamma log b and q = alpha (a^gamma / b - gamma a^(gamma-1) log b).
+//   negatives: a = c, b = 1 - c:  l_neg = l, dl_neg/dc = q;     positives: a = 1 - c, b = c:  l_pos = l, dl_pos/dc = -q
+// (cross entropy: l = -log b, q = 1 / b)
+template <int KIND>
+__device__ __forceinline__ void loss_term(float a, float b, const LossParams& p, float& l, float& q) {
+  const float rb = __builtin_amdgcn_rcpf(b);
+  if (KIND == kCeLoss) {
+    l = -__ocml_log_f32(b);
+    q = rb;
+  } else {
+    const float lg = __ocml_log_f32(b);
+    float pw1, g;                        // a^(gamma - 1), gamma
+    if (KIND == kFocal2) { pw1 = a; g = 2.0f; }
+    else { pw1 = __builtin_amdgcn_exp2f((p.gamma - 1.0f) * __builtin_amdgcn_logf(a)); g = p.gamma; }
+    const float pw = pw1 * a;
+    l = -p.alpha * pw * lg;
+    q = p.alpha * (pw * rb - g * pw1 * lg);
+  }
+}
+
+// Folds the 16 partial sums of a dot product as row_sum16_g (dsm_grad.hip) does across 16 lanes - pairs, quads, halves,
+// all: a balanced tree, every level commutative - when they arrive one after the other: lv is a binary counter of
+// finished subtrees, x the result after l = 15.  (l is uniform: scalar branches, lv stays in registers.)
+__device__ __forceinline__ void dot_fold(int l, float s, float (&lv)[4], float& x) {
+  if (!(l & 1)) { lv[0] = s; return; }
+  s = lv[0] + s;
+  if (!(l & 2)) { lv[1] = s; return; }
+  s = lv[1] + s;
+  if (!(l & 4)) { lv[2] = s; return; }
+  s = lv[2] + s;
+  if (!(l & 8)) { lv[3] = s; return; }
+  x = lv[3] + s;
+}
+
+// conf = softmax over the rows * softmax over the columns, from the raw dot product and the statistics of its row (ox, isx =
+// 1 / denominator) and its column (oy, isy); the one expression the sweep and the entries kernel share
+__device__ __forceinline__ float conf_from(float x, float k2, float ox, float isx, float oy, float isy, float& ar, float& br) {
+  ar = __builtin_amdgcn_exp2f(__builtin_fmaf(x, k2, oy)) * isy;
+  br = __builtin_amdgcn_exp2f(__builtin_fmaf(x, k2, ox)) * isx;
+  return ar * br;
+}
+
+// the dense part of G at one entry, times conf; l = l_neg(c)
+template <int KIND>
+__device__ __forceinline__ float dense_gc(float conf, const LossParams& p, float& l) {
+  const float c = fminf(fmaxf(conf, p.lo), p.hi);
+  float q;
+  loss_term<KIND>(c, 1.0f - c, p, l, q);
+  return (conf >= p.lo && conf <= p.hi) ? p.wn * q * conf : 0.f;        // torch's clamp backward: the closed interval
+}
+
+// The supervised entries: one thread per entry, the dot product in the sweep's order (see above).
+// l_pos[e], l_neg[e] and gc[e] = g_e conf_e with g_e the correction of G at e.
+template <int KIND>
+__global__ __launch_bounds__(256) void k_closs_entries(const float* __restrict__ f0, const float* __restrict__ f1, int L, int S,
+                                                       int c_in, float k2, const float* __restrict__ nm_r,
+                                                       const float* __restrict__ sum_r, int pitch_r,
+                                                       const float* __restrict__ nm_c, const float* __restrict__ sum_c,
+                                                       int pitch_c, const int64_t* __restrict__ b_ids,
+                                                       const int64_t* __restrict__ i_ids, const int64_t* __restrict__ j_ids,
+                                                       int K, LossParams p, float* __restrict__ l_pos,
+                                                       float* __restrict__ l_neg, float* __restrict__ gc) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= K) return;
+  const long b = b_ids[e], i = i_ids[e], j = j_ids[e];
+  const float4* ra = reinterpret_cast<const float4*>(f0 + (b * L + i) * c_in);
+  const float4* rb = reinterpret_cast<const float4*>(f1 + (b * S + j) * c_in);
+  const int vpr = c_in >> 2;
+  float lv[4], x = 0.f;                       // the exact phase's order: see dot_fold
+#pragma unroll
+  for (int l = 0; l < 16; ++l) {
+    float sl = 0.f;
+    for (int v4 = l; v4 < vpr; v4 += 16) {
+      const float4 a = ra[v4], y = rb[v4];
+      sl = __builtin_fmaf(a.x, y.x, sl);
+      sl = __builtin_fmaf(a.y, y.y, sl);
+      sl = __builtin_fmaf(a.z, y.z, sl);
+      sl = __builtin_fmaf(a.w, y.w, sl);
+    }
+    dot_fold(l, sl, lv, x);
+  }
+  float ar, br;
+  const float conf = conf_from(x, k2, nm_r[b * pitch_r + i], 1.0f / sum_r[b * pitch_r + i], nm_c[b * pitch_c + j],
+                               1.0f / sum_c[b * pitch_c + j], ar, br);
+  const float c = fminf(fmaxf(conf, p.lo), p.hi);
+  float ln, qn, lp, qp;
+  loss_term<KIND>(c, 1.0f - c, p, ln, qn);
+  loss_term<KIND>(1.0f - c, c, p, lp, qp);
+  l_pos[e] = lp;
+  l_neg[e] = ln;
+  gc[e] = (conf >= p.lo && conf <= p.hi) ? (-p.wp * qp - p.wn * qn) * conf : 0.f;
+}
+
+// The tiled sweep (k_dsm_bwd's tiling: Xs / Ys [32][C + 4], D transposed with pitch 36; grid (ceil(R / 32), N, Z)).
+//   kSums : per entry gc = g conf with g the dense part of G; row sums into v_out, column sums into u_out (float atomics in
+//           arrival order, as kDsmStats), l_neg(c) into a per-thread sum (double), one partial per workgroup into loss_part in a
+//           fixed order.  Side 0 only.
+//   kGrad : D = 2 gc - A w_y - B w_x accumulated into the rows' gradient, partials per z into `part`.
+template <int C, int MODE, int KIND>
+__global__ __launch_bounds__(256) void k_closs_sweep(const float* __restrict__ X, const float* __restrict__ Y, int R, int T,
+                                                     int c_in, const float* __restrict__ ofs_x, const float* __restrict__ sum_x,
+                                                     int pitch_x, const float* __restrict__ ofs_y,
+                                                     const float* __restrict__ sum_y, int pitch_y,
+                                                     const float* __restrict__ w_x, const float* __restrict__ w_y, float k2,
+                                                     LossParams p, float* __restrict__ part, float* __restrict__ v_out,
+                                                     float* __restrict__ u_out, double* __restrict__ loss_part) {
+  constexpr int P = C + 4;                   // row pitch (floats): 16-byte reads of 16 consecutive rows hit all banks
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  float* Xs = sm;                            // [32][P]
+  float* Ys = sm + 32 * P;                   // [32][P]
+  float* Dt = sm + 64 * P;                   // [32 (l)][36]: D transposed
+  const int tid = threadIdx.x, b = blockIdx.y, k0 = blockIdx.x * 32;
+  const int ntiles = (T + 31) / 32, Z = gridDim.z, z = blockIdx.z;
+  const int t_lo = (int)((long)ntiles * z / Z), t_hi = (int)((long)ntiles * (z + 1) / Z);
+  const float* Xb = X + (long)b * R * c_in;
+  const float* Yb = Y + (long)b * T * c_in;
+  const int vpr = c_in >> 2;
+  auto load_tile = [&](float* dst, const float* src, int row0, int rows) {
+#pragma unroll
+    for (int q = 0; q < 32 * (C / 4) / 256; ++q) {
+      const int idx = q * 256 + tid, row = idx / (C / 4), v4 = idx % (C / 4);
+      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (row0 + row < rows && v4 < vpr) v = reinterpret_cast<const float4*>(src + (long)(row0 + row) * c_in)[v4];
+      *reinterpret_cast<float4*>(&dst[row * P + 4 * v4]) = v;
+    }
+  };
+  load_tile(Xs, Xb, k0, R);
+  const int tx = tid & 31, ty = tid >> 5;                 // similarity phase: column tx, rows ty + 8 q
+  float ox[4], wx[4], isx[4], vacc[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int k = k0 + ty + 8 * q;
+    ox[q] = k < R ? ofs_x[(long)b * pitch_x + k] : 0.f;
+    isx[q] = k < R ? 1.0f / sum_x[(long)b * pitch_x + k] : 0.f;
+    wx[q] = (MODE == kGrad && k < R) ? w_x[(long)b * R + k] : 0.f;
+    vacc[q] = 0.f;
+  }
+  double lacc = 0.0;
+  const int c4 = tid & 63, rg = tid >> 6;                 // gradient phase: channels 4 c4 .. + 3, rows 8 rg .. + 7
+  float acc[8][4];
+#pragma unroll
+  for (int r = 0; r < 8; ++r)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) acc[r][e] = 0.f;
+  for (int t = t_lo; t < t_hi; ++t) {
+    const int l0 = t * 32;
+    __syncthreads();                                      // the previous tile's readers are done with Ys and Dt
+    load_tile(Ys, Yb, l0, T);
+    const int l = l0 + tx;
+    const float oy = l < T ? ofs_y[(long)b * pitch_y + l] : 0.f;
+    const float isy = l < T ? 1.0f / sum_y[(long)b * pitch_y + l] : 0.f;
+    const float wy = (MODE == kGrad && l < T) ? w_y[(long)b * T + l] : 0.f;
+    __syncthreads();
+    float sv[4] = {0.f, 0.f, 0.f, 0.f}, lv[4][4];
+#pragma unroll 1                                          // (unrolled, the loads of all 16 partial sums are hoisted: spills)
+    for (int pl = 0; pl < 16; ++pl) {                     // partial sum pl: the float4 groups pl, pl + 16, ... (see above)
+      float sl[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int c = 4 * pl; c < C; c += 64) {
+        const float4 y = *reinterpret_cast<const float4*>(&Ys[tx * P + c]);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const float4 x = *reinterpret_cast<const float4*>(&Xs[(ty + 8 * q) * P + c]);
+          sl[q] = __builtin_fmaf(x.x, y.x, sl[q]);
+          sl[q] = __builtin_fmaf(x.y, y.y, sl[q]);
+          sl[q] = __builtin_fmaf(x.z, y.z, sl[q]);
+          sl[q] = __builtin_fmaf(x.w, y.w, sl[q]);
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < 4; ++q) dot_fold(pl, sl[q], lv[q], sv[q]);
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const bool ok = l < T && k0 + ty + 8 * q < R;
+      float ar, br, ln;
+      // (which image owns the rows does not matter to conf: the two factors commute)
+      const float conf = conf_from(sv[q], k2, ox[q], isx[q], oy, isy, ar, br);
+      const float gc = ok ? dense_gc<KIND>(conf, p, ln) : 0.f;
+      if (MODE == kSums) {
+        vacc[q] += gc;
+        lacc += ok ? (double)ln : 0.0;
+        Dt[tx * 36 + ty + 8 * q] = gc;
+      } else {
+        Dt[tx * 36 + ty + 8 * q] = ok ? 2.0f * gc - ar * wy - br * wx[q] : 0.f;
+      }
+    }
+    __syncthreads();
+    if (MODE == kSums) {
+      // column sums of this tile's g conf: 32 threads add the 32 owner rows of their column in a fixed order
+      if (tid < 32 && l0 + tid < T) {
+        float cs = 0.f;
+#pragma unroll 8
+        for (int rr = 0; rr < 32; ++rr) cs += Dt[tid * 36 + rr];
+        atomicAdd(&u_out[(long)b * T + l0 + tid], cs);
+      }
+      continue;
+    }
+    if (4 * c4 < C) {
+#pragma unroll 4
+      for (int ll = 0; ll < 32; ++ll) {
+        const float4 y = *reinterpret_cast<const float4*>(&Ys[ll * P + 4 * c4]);
+        const float4 d0 = *reinterpret_cast<const float4*>(&Dt[ll * 36 + 8 * rg]);
+        const float4 d1 = *reinterpret_cast<const float4*>(&Dt[ll * 36 + 8 * rg + 4]);
+        const float d[8] = {d0.x, d0.y, d0.z, d0.w, d1.x, d1.y, d1.z, d1.w};
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+          acc[r][0] = __builtin_fmaf(d[r], y.x, acc[r][0]);
+          acc[r][1] = __builtin_fmaf(d[r], y.y, acc[r][1]);
+          acc[r][2] = __builtin_fmaf(d[r], y.z, acc[r][2]);
+          acc[r][3] = __builtin_fmaf(d[r], y.w, acc[r][3]);
+        }
+      }
+    }
+  }
+  if (MODE == kSums) {
+    // row sums: the 32 columns a row's partial sums sit in are the 32 lanes of a half wave
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      float t = vacc[q];
+#pragma unroll
+      for (int m = 16; m >= 1; m >>= 1) t += __shfl_xor(t, m);
+      const int k = k0 + ty + 8 * q;
+      if (tx == 0 && k < R) atomicAdd(&v_out[(long)b * R + k], t);
+    }
+    // the workgroup's sum of l_neg: butterfly within each wave, then the four waves in index order - the same bits
+    // every run
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) lacc += __shfl_xor(lacc, m);
+    __syncthreads();                                      // the last tile's column sums are done with Dt
+    double* red = reinterpret_cast<double*>(Dt);
+    if ((tid & 63) == 0) red[tid >> 6] = lacc;
+    __syncthreads();
+    if (tid == 0) loss_part[((long)z * gridDim.y + b) * gridDim.x + blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+    return;
+  }
+  if (c4 < vpr) {
+    float* out = part + (((long)z * gridDim.y + b) * R) * c_in;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+      const int k = k0 + 8 * rg + r;
+      if (k < R) reinterpret_cast<float4*>(out + (long)k * c_in)[c4] = make_float4(acc[r][0], acc[r][1], acc[r][2], acc[r][3]);
+    }
+  }
+}
+
+// sum of n numbers in double, in an order that depends on n alone: thread t adds elements t, t + 256, ..., then a tree
+template <typename T>
+__device__ __forceinline__ double block_sum_fixed(const T* __restrict__ x, long n, double* red) {
+  double s = 0.0;
+  for (long i = threadIdx.x; i < n; i += 256) s += (double)x[i];
+  __syncthreads();
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int m = 128; m >= 1; m >>= 1) {
+    if ((int)threadIdx.x < m) red[threadIdx.x] += red[threadIdx.x + m];
+    __syncthreads();
+  }
+  return red[0];
+}
+
+// loss_out = {loss, mean of l_pos over P, mean of l_neg over the negatives}; one workgroup.  leave: the listed entries are
+// positives and leave the negatives' sum (0: the stand-in entry of an empty supervision)
+__global__ __launch_bounds__(256) void k_closs_finish(const double* __restrict__ loss_part, long n_part,
+                                                      const float* __restrict__ l_pos, const float* __restrict__ l_neg, int K,
+                                                      double inv_pos, double inv_neg, float pos_weight, float neg_weight,
+                                                      int leave, float* __restrict__ loss_out) {
+  __shared__ double red[256];
+  const double all = block_sum_fixed(loss_part, n_part, red);
+  const double neg_p = block_sum_fixed(l_neg, K, red);
+  const double pos_p = block_sum_fixed(l_pos, K, red);
+  if (threadIdx.x == 0) {
+    const double pos_mean = pos_p * inv_pos, neg_mean = (leave ? all - neg_p : all) * inv_neg;
+    loss_out[0] = (float)((double)pos_weight * pos_mean + (double)neg_weight * neg_mean);
+    loss_out[1] = (float)pos_mean;
+    loss_out[2] = (float)neg_mean;
+  }
+}
+
+// out = scale * d_loss * sum_z part[z]   (fixed order; d_loss [1] on the device: the upstream gradient of the scalar)
+__global__ __launch_bounds__(256) void k_closs_combine(const float4* __restrict__ part, long n4, int Z, float scale,
+                                                       const float* __restrict__ d_loss, float4* __restrict__ out) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n4) return;
+  const float f = scale * d_loss[0];
+  float4 s = part[i];
+  for (int z = 1; z < Z; ++z) {
+    const float4 v = part[(long)z * n4 + i];
+    s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+  }
+  out[i] = make_float4(s.x * f, s.y * f, s.z * f, s.w * f);
+}
+
+__global__ __launch_bounds__(256) void k_closs_scale(const float* __restrict__ gc, int K, const float* __restrict__ d_loss,
+                                                     float* __restrict__ out) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e < K) out[e] = gc[e] * d_loss[0];
+}
+
+// Workspace: the dual softmax backward's (v, u, part: fm_internal.h) | one loss partial (double) per workgroup of the kSums sweep |
+// the ids (0, 0, 0) of the stand-in entry of an empty supervision | per entry l_pos, l_neg, gc and gc * d_loss
+struct ClossWs { DsmBwdWs dsm; Span loss_part, zero_ids, l_pos, l_neg, gc, gcs; int Ke; size_t total; };
+static ClossWs closs_layout(int N, int L, int S, int C, int K) {
+  ClossWs w;
+  w.dsm = dsm_bwd_layout(N, L, S, C);
+  w.Ke = K > 0 ? K : 1;
+  const size_t per = align256((size_t)w.Ke * 4);
+  w.loss_part = {align256(w.dsm.total), align256((size_t)4 * N * ((L + 31) / 32) * 8)};
+  w.zero_ids = {w.loss_part.at + w.loss_part.bytes, 256};
+  w.l_pos = {w.zero_ids.at + w.zero_ids.bytes, per};
+  w.l_neg = {w.l_pos.at + per, per};
+  w.gc = {w.l_neg.at + per, per};
+  w.gcs = {w.gc.at + per, per};
+  w.total = w.gcs.at + per;
+  return w;
+}
+
+// one call of either entry point after its checks
+struct ClossCall {
+  DsmProblem p;
+  DsmStats s;
+  ClossWs w;
+  LossParams lp;
+  int kind;                                   // kCeLoss / kFocal2 / kFocalG
+  const int64_t *b_ids, *i_ids, *j_ids;       // Ke entries (the workspace's zeros when the supervision is empty)
+  float pos_weight, neg_weight;               // as they count: 0 where the reference's degenerate cases set them to 0
+  double inv_pos, inv_neg;
+  bool stand_in;                              // empty supervision: the one listed entry is loss.py:38's (0, 0, 0)
+};
+
+static int closs_begin(const float* feat0, const float* feat1, int N, int L, int S, int C, float temperature, const DsmStats& s,
+                       int kind, float alpha, float gamma, float pos_weight, float neg_weight, const int64_t* b_ids,
+                       const int64_t* i_ids, const int64_t* j_ids, int K, void* workspace, size_t workspace_bytes,
+                       bool forward, hipStream_t st, ClossCall* c) {
+  if (!feat0 || !feat1 || !s.ofs_r || !s.ofs_c || !s.sum_r || !s.sum_c || !workspace) return FM_E_NULL;
+  if (K > 0 && (!b_ids || !i_ids || !j_ids)) return FM_E_NULL;
+  if (K < 0 || !(N > 0 && L > 0 && S > 0) || s.pitch_r < L || s.pitch_c < S) return FM_E_SHAPE;
+  if (!valid_channels(C) || !(temperature > 0.f)) return FM_E_UNSUPPORTED;
+  if ((kind != FM_LOSS_CROSS_ENTROPY && kind != FM_LOSS_FOCAL) || !(gamma > 0.f)) return FM_E_UNSUPPORTED;
+  const double total = (double)N * L * S;
+  if ((double)K > total) return FM_E_SHAPE;
+  c->w = closs_layout(N, L, S, C, K);
+  if (workspace_bytes < c->w.total || ((uintptr_t)workspace & 255)) return FM_E_WORKSPACE;
+  c->s = s;
+  if (forward) {
+    const int r = dsm_begin(feat0, feat1, N, L, S, C, temperature, s, workspace, workspace_bytes, st, &c->p);
+    if (r != FM_OK) return r;
+  } else {                                    // v and u are the forward call's
+    const float inv_ct = 1.0f / ((float)C * temperature);
+    c->p = {feat0, feat1, N, L, S, C, kLog2e * inv_ct, inv_ct, span_ptr<float>(workspace, c->w.dsm.v),
+            span_ptr<float>(workspace, c->w.dsm.u), span_ptr<float>(workspace, c->w.dsm.part)};
+  }
+  // loss.py:37-42: without a positive, entry (0, 0, 0) stands in with weight 0 - in pos_mask only: neg_mask was taken
+  // before, so the entry stays among the negatives; without a negative the negatives' weight is 0
+  c->stand_in = K == 0;
+  c->pos_weight = K > 0 ? pos_weight : 0.f;
+  const double n_neg = total - (double)K;
+  c->neg_weight = n_neg > 0 ? neg_weight : 0.f;
+  c->inv_pos = 1.0 / (double)c->w.Ke;
+  c->inv_neg = n_neg > 0 ? 1.0 / n_neg : 0.0;
+  c->kind = kind == FM_LOSS_CROSS_ENTROPY ? kCeLoss : (gamma == 2.0f ? kFocal2 : kFocalG);
+  c->lp = {alpha, gamma, (float)(c->neg_weight * c->inv_neg), (float)(c->pos_weight * c->inv_pos), 1e-6f, 1.0f - 1e-6f};
+  if (K > 0) {
+    c->b_ids = b_ids; c->i_ids = i_ids; c->j_ids = j_ids;
+  } else {
+    c->b_ids = c->i_ids = c->j_ids = span_ptr<const int64_t>(workspace, c->w.zero_ids);
+    if (forward) return (int)hipMemsetAsync(span_ptr<char>(workspace, c->w.zero_ids), 0, c->w.zero_ids.bytes, st);
+  }
+  return FM_OK;
+}
+
+template <typename F>
+static hipError_t with_kind(int kind, F&& f) {
+  return kind == kCeLoss ? f(int_c<kCeLoss>{}) : kind == kFocal2 ? f(int_c<kFocal2>{}) : f(int_c<kFocalG>{});
+}
+
+// the tiled sweep of one side (0: owner = image 0, 1: owner = image 1), as dsm_sweep in dsm_grad.hip
+static int closs_sweep(int mode, int side, const ClossCall& c, void* workspace, const float* d_loss, float* d_out,
+                       hipStream_t st) {
+  DsmProblem o = c.p;
+  DsmStats t = c.s;
+  if (side) {
+    std::swap(o.feat0, o.feat1); std::swap(o.L, o.S); std::swap(o.v, o.u);
+    t = {c.s.ofs_c, c.s.sum_c, c.s.pitch_c, c.s.ofs_r, c.s.sum_r, c.s.pitch_r};
+  }
+  const int Z = dsm_zsplit(c.p.N, o.L);
+  const dim3 grid((o.L + 31) / 32, c.p.N, Z);
+  double* loss_part = span_ptr<double>(workspace, c.w.loss_part);
+  auto launch = [&](auto cc, auto mm, auto kk) -> hipError_t {
+    constexpr int CC = decltype(cc)::value, MM = decltype(mm)::value, KK = decltype(kk)::value;
+    constexpr int smem = (64 * (CC + 4) + 32 * 36) * 4;
+    static unsigned long long lds_set = 0;      // (one per instantiation of this lambda, that is, per kernel)
+    const hipError_t e = ensure_dynamic_lds(&k_closs_sweep<CC, MM, KK>, smem, &lds_set);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((k_closs_sweep<CC, MM, KK>), grid, dim3(256), smem, st, o.feat0, o.feat1, o.L, o.S, c.p.C, t.ofs_r,
+                       t.sum_r, t.pitch_r, t.ofs_c, t.sum_c, t.pitch_c, o.v, o.u, c.p.k2, c.lp, c.p.part, c.p.v, c.p.u,
+                       loss_part);
+    return hipSuccess;
+  };
+  auto with_mode = [&](auto cc) {
+    return with_kind(c.kind, [&](auto kk) {
+      return mode == kSums ? launch(cc, int_c<kSums>{}, kk) : launch(cc, int_c<kGrad>{}, kk);
+    });
+  };
+  const int Cp = padded_channels(c.p.C);
+  const hipError_t e = Cp == 64 ? with_mode(int_c<64>{}) : Cp == 128 ? with_mode(int_c<128>{}) : with_mode(int_c<256>{});
+  if (e != hipSuccess) return (int)e;
+  if (mode == kSums) {
+    hipLaunchKernelGGL(k_closs_finish, dim3(1), dim3(256), 0, st, (const double*)loss_part, (long)grid.x * grid.y * grid.z,
+                       span_ptr<const float>(workspace, c.w.l_pos), span_ptr<const float>(workspace, c.w.l_neg), c.w.Ke,
+                       c.inv_pos, c.inv_neg, c.pos_weight, c.neg_weight, c.stand_in ? 0 : 1, d_out);
+  } else {
+    const long n4 = (long)c.p.N * o.L * c.p.C / 4;
+    hipLaunchKernelGGL(k_closs_combine, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, (const float4*)c.p.part, n4, Z,
+                       c.p.inv_ct, d_loss, (float4*)d_out);
+  }
+  return (int)hipGetLastError();
+}
+
+}  // namespace fm
+
+using namespace fm;
+
+extern "C" size_t fm_coarse_loss_workspace_bytes(int N, int L, int S, int C, int K) {
+  return N > 0 && L > 0 && S > 0 && K >= 0 && valid_channels(C) ? closs_layout(N, L, S, C, K).total : 0;
+}
+
+extern "C" int fm_coarse_loss_forward(const float* feat0, const float* feat1, int N, int L, int S, int C, float temperature,
+                                      const float* nm_r, const float* sum_r, int pitch_r, const float* nm_c,
+                                      const float* sum_c, int pitch_c, int kind, float alpha, float gamma, float pos_weight,
+                                      float neg_weight, const int64_t* b_ids, const int64_t* i_ids, const int64_t* j_ids, int K,
+                                      void* workspace, size_t workspace_bytes, float* loss_out, void* stream) {
+  if (!loss_out) return FM_E_NULL;
+  hipStream_t st = (hipStream_t)stream;
+  ClossCall c;
+  int r = closs_begin(feat0, feat1, N, L, S, C, temperature, {nm_r, sum_r, pitch_r, nm_c, sum_c, pitch_c}, kind, alpha, gamma,
+                      pos_weight, neg_weight, b_ids, i_ids, j_ids, K, workspace, workspace_bytes, true, st, &c);
+  if (r != FM_OK) return r;
+  float* gc = span_ptr<float>(workspace, c.w.gc);
+  LossParams lp_e = c.lp;                     // the listed entries leave the negatives - the stand-in does not
+  if (c.stand_in) lp_e.wn = 0.f;
+  const hipError_t e = with_kind(c.kind, [&](auto kk) {
+    hipLaunchKernelGGL((k_closs_entries<decltype(kk)::value>), dim3((c.w.Ke + 255) / 256), dim3(256), 0, st, feat0, feat1, L, S, C,
+                       c.p.k2, nm_r, sum_r, pitch_r, nm_c, sum_c, pitch_c, c.b_ids, c.i_ids, c.j_ids, c.w.Ke, lp_e,
+                       span_ptr<float>(workspace, c.w.l_pos), span_ptr<float>(workspace, c.w.l_neg), gc);
+    return hipGetLastError();
+  });
+  if (e != hipSuccess) return (int)e;
+  r = (int)launch_dsm_uv(c.b_ids, c.i_ids, c.j_ids, gc, c.w.Ke, L, S, c.p.v, c.p.u, st);
+  if (r != FM_OK) return r;
+  return closs_sweep(kSums, 0, c, workspace, nullptr, loss_out, st);
+}
+
+extern "C" int fm_coarse_loss_backward(const float* feat0, const float* feat1, int N, int L, int S, int C, float temperature,
+                                       const float* nm_r, const float* sum_r, int pitch_r, const float* nm_c,
+                                       const float* sum_c, int pitch_c, int kind, float alpha, float gamma, float pos_weight,
+                                       float neg_weight, const int64_t* b_ids, const int64_t* i_ids, const int64_t* j_ids,
+                                       int K, void* workspace, size_t workspace_bytes, const float* d_loss, float* d_feat0,
+                                       float* d_feat1, void* stream) {
+  if (!d_loss || !d_feat0 || !d_feat1) return FM_E_NULL;
+  hipStream_t st = (hipStream_t)stream;
+  ClossCall c;
+  int r = closs_begin(feat0, feat1, N, L, S, C, temperature, {nm_r, sum_r, pitch_r, nm_c, sum_c, pitch_c}, kind, alpha, gamma,
+                      pos_weight, neg_weight, b_ids, i_ids, j_ids, K, workspace, workspace_bytes, false, st, &c);
+  if (r != FM_OK) return r;
+  for (int side = 0; side < 2; ++side) {
+    r = closs_sweep(kGrad, side, c, workspace, d_loss, side ? d_feat1 : d_feat0, st);
+    if (r != FM_OK) return r;
+  }
+  float* gcs = span_ptr<float>(workspace, c.w.gcs);
+  hipLaunchKernelGGL(k_closs_scale, dim3((c.w.Ke + 255) / 256), dim3(256), 0, st, span_ptr<const float>(workspace, c.w.gc),
+                     c.w.Ke, d_loss, gcs);
+  return (int)launch_dsm_entries(c.p, c.b_ids, c.i_ids, c.j_ids, gcs, c.w.Ke, d_feat0, d_feat1, st);
+}

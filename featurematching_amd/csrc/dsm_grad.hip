@@ -436,10 +436,23 @@ hipError_t launch_conf_patch(const CoarseWs& w, char* base, float inv_ct, float*
   return hipGetLastError();
 }
 
-static int dsm_zsplit(int N, int R) {
+int dsm_zsplit(int N, int R) {
   const int wgs = N * ((R + 31) / 32);
   int z = (512 + wgs - 1) / wgs;
   return z < 1 ? 1 : (z > 4 ? 4 : z);
+}
+
+hipError_t launch_dsm_uv(const int64_t* b_ids, const int64_t* i_ids, const int64_t* j_ids, const float* gc, int K, int L, int S,
+                         float* v, float* u, hipStream_t st) {
+  hipLaunchKernelGGL(k_dsm_uv, dim3((K + 255) / 256), dim3(256), 0, st, b_ids, i_ids, j_ids, gc, K, L, S, v, u);
+  return hipGetLastError();
+}
+
+hipError_t launch_dsm_entries(const DsmProblem& p, const int64_t* b_ids, const int64_t* i_ids, const int64_t* j_ids,
+                              const float* gc, int K, float* d_feat0, float* d_feat1, hipStream_t st) {
+  hipLaunchKernelGGL(k_dsm_entries, dim3((K + 3) / 4), dim3(256), 0, st, p.feat0, p.feat1, p.L, p.S, p.C, b_ids, i_ids, j_ids, gc,
+                     K, 2.0f * p.inv_ct, d_feat0, d_feat1);
+  return hipGetLastError();
 }
 
 }  // namespace fm
@@ -461,38 +474,12 @@ extern "C" int fm_dual_softmax_conf_at(const float* feat0, const float* feat1, i
   return (int)hipGetLastError();
 }
 
-// Workspace of both backward entry points: v [N][L] row sums and u [N][S] column sums of g conf, one behind the other
-// (sums: the two, zeroed per call) | part, 256-byte aligned: up to 4 (dsm_zsplit) partial gradients [N][max(L, S)][C]
-struct DsmBwdWs { Span v, u, sums, part; size_t total; };
-static DsmBwdWs dsm_bwd_layout(int N, int L, int S, int C) {
-  DsmBwdWs w;
-  w.v = {0, (size_t)N * L * 4};
-  w.u = {w.v.bytes, (size_t)N * S * 4};
-  w.sums = {0, w.v.bytes + w.u.bytes};
-  w.part = {align256(w.sums.bytes), (size_t)4 * N * (size_t)(L > S ? L : S) * C * 4};
-  w.total = w.part.at + w.part.bytes;
-  return w;
-}
-
 extern "C" size_t fm_dual_softmax_backward_workspace_bytes(int N, int L, int S, int C) {
   return N > 0 && L > 0 && S > 0 && valid_channels(C) ? dsm_bwd_layout(N, L, S, C).total : 0;
 }
 
-// the softmax statistics the forward pass kept: -stabiliser*log2e and denominator of every row / column
-struct DsmStats {
-  const float *ofs_r, *sum_r; int pitch_r;
-  const float *ofs_c, *sum_c; int pitch_c;
-};
-// one backward call: the descriptors, the shape, the temperature terms and the carved workspace
-struct DsmProblem {
-  const float *feat0, *feat1;
-  int N, L, S, C;
-  float k2, inv_ct;
-  float *v, *u, *part;
-};
-
 // what both backward entry points do after their NULL checks: the remaining argument checks, then *p with v and u zeroed
-static int dsm_begin(const float* feat0, const float* feat1, int N, int L, int S, int C, float temperature, const DsmStats& s,
+int fm::dsm_begin(const float* feat0, const float* feat1, int N, int L, int S, int C, float temperature, const DsmStats& s,
                      void* workspace, size_t workspace_bytes, hipStream_t st, DsmProblem* p) {
   if (!(N > 0 && L > 0 && S > 0) || s.pitch_r < L || s.pitch_c < S) return FM_E_SHAPE;
   if (!valid_channels(C) || !(temperature > 0.f)) return FM_E_UNSUPPORTED;
@@ -573,13 +560,14 @@ extern "C" int fm_dual_softmax_backward(const float* feat0, const float* feat1, 
   DsmProblem p;
   int r = dsm_begin(feat0, feat1, N, L, S, C, temperature, s, workspace, workspace_bytes, st, &p);
   if (r != FM_OK) return r;
-  if (K > 0) hipLaunchKernelGGL(k_dsm_uv, dim3((K + 255) / 256), dim3(256), 0, st, b_ids, i_ids, j_ids, gc, K, L, S, p.v, p.u);
+  if (K > 0) {
+    r = (int)launch_dsm_uv(b_ids, i_ids, j_ids, gc, K, L, S, p.v, p.u, st);
+    if (r != FM_OK) return r;
+  }
   for (int side = 0; side < 2; ++side) {
     r = dsm_sweep(kDsmSparse, side, p, s, nullptr, side ? d_feat1 : d_feat0, st);
     if (r != FM_OK) return r;
   }
-  if (K > 0)
-    hipLaunchKernelGGL(k_dsm_entries, dim3((K + 3) / 4), dim3(256), 0, st, feat0, feat1, L, S, C, b_ids, i_ids, j_ids, gc, K,
-                       2.0f * p.inv_ct, d_feat0, d_feat1);
+  if (K > 0) return (int)launch_dsm_entries(p, b_ids, i_ids, j_ids, gc, K, d_feat0, d_feat1, st);
   return (int)hipGetLastError();
 }

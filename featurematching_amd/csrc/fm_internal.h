@@ -148,6 +148,41 @@ hipError_t launch_exact_lists(const CoarseWs& w, char* base, float inv_ct, const
 hipError_t launch_screen(const void* feat0, const void* feat1, int in_dtype, int c_in, const CoarseWs& w, char* base,
                              float inv_ct, float thr, int dense_enabled, int allow_dead, hipStream_t st);
 
+// ---- backward of the dual softmax (dsm_grad.hip) and the matrix-free coarse loss on top of it (coarse_loss.hip) ----
+// Workspace of the backward entry points: v [N][L] row sums and u [N][S] column sums of g conf, one behind the other
+// (sums: the two, zeroed per call) | part, 256-byte aligned: up to 4 (dsm_zsplit) partial gradients [N][max(L, S)][C]
+struct DsmBwdWs { Span v, u, sums, part; size_t total; };
+inline DsmBwdWs dsm_bwd_layout(int N, int L, int S, int C) {
+  DsmBwdWs w;
+  w.v = {0, (size_t)N * L * 4};
+  w.u = {w.v.bytes, (size_t)N * S * 4};
+  w.sums = {0, w.v.bytes + w.u.bytes};
+  w.part = {align256(w.sums.bytes), (size_t)4 * N * (size_t)(L > S ? L : S) * C * 4};
+  w.total = w.part.at + w.part.bytes;
+  return w;
+}
+// the softmax statistics the forward pass kept: -stabiliser*log2e and denominator of every row / column
+struct DsmStats {
+  const float *ofs_r, *sum_r; int pitch_r;
+  const float *ofs_c, *sum_c; int pitch_c;
+};
+// one backward call: the descriptors, the shape, the temperature terms and the carved workspace
+struct DsmProblem {
+  const float *feat0, *feat1;
+  int N, L, S, C;
+  float k2, inv_ct;
+  float *v, *u, *part;
+};
+// what every backward entry point does after its NULL checks: the remaining argument checks, then *p with v and u zeroed
+int dsm_begin(const float* feat0, const float* feat1, int N, int L, int S, int C, float temperature, const DsmStats& s,
+              void* workspace, size_t workspace_bytes, hipStream_t st, DsmProblem* p);
+int dsm_zsplit(int N, int R);      // z slices of a sweep's column range, so that N * ceil(R / 32) * z fills the chip
+// v / u contributions and own term 2 g c of K listed entries (k_dsm_uv, k_dsm_entries), gc[e] = g_e conf_e
+hipError_t launch_dsm_uv(const int64_t* b_ids, const int64_t* i_ids, const int64_t* j_ids, const float* gc, int K, int L, int S,
+                         float* v, float* u, hipStream_t st);
+hipError_t launch_dsm_entries(const DsmProblem& p, const int64_t* b_ids, const int64_t* i_ids, const int64_t* j_ids,
+                              const float* gc, int K, float* d_feat0, float* d_feat1, hipStream_t st);
+
 // Raises a kernel's dynamic-LDS limit once per (kernel, device) instead of on every launch: the
 // attribute call costs tens of host microseconds, which an eager (non-graph) caller would pay per step.
 template <typename K>

@@ -6,6 +6,8 @@
         (network/module/fine_preprocess.py:32)
     FineMatching.forward(feat_f0, feat_f1, data) -> None
         (network/utils/fine_matching_new.py:22)
+    CoarseLoss.forward(data) -> Tensor
+        (Loss.compute_coarse_loss, losses/loss.py:27, from the supervision ids instead of two [N,L,S] arrays)
 
 Constructors take the same lower-cased config sub-dicts as network/net.py:29-32.  The
 computation runs in the HIP kernels of libfmatch_hip.so (see ops.py); only the learned
@@ -32,9 +34,12 @@ class CoarseMatching(nn.Module):
     softmax back to the descriptors (ops.attach_conf_matrix_grad).
     `gt_pad_sampler=True` selects the older training sampler (network/utils/coarse_matching.py:114-141: predicted
     matches sub-sampled to train_coarse_percent and padded with ground-truth matches up to train_pad_num_gt_min)
-    instead of coarse_matching_new.py's plain substitution of the supervision ids (:113-116)."""
+    instead of coarse_matching_new.py's plain substitution of the supervision ids (:113-116).
+    `loss_stats=True` trains without the matrix: the coarse call keeps its softmax statistics (stats=True) and
+    data['_fm_coarse_loss'] = (buffers, feat_c0, feat_c1) - the descriptors as handed in, with their autograd history -
+    is what CoarseLoss reads; no data['conf_matrix'] is written unless conf_matrix=True asks for it as well."""
 
-    def __init__(self, config, conf_matrix: bool = False, gt_pad_sampler: bool = False):
+    def __init__(self, config, conf_matrix: bool = False, gt_pad_sampler: bool = False, loss_stats: bool = False):
         super().__init__()
         self.config = config
         self.thr = config['thr']
@@ -44,6 +49,7 @@ class CoarseMatching(nn.Module):
         self.temperature = config['dsmax_temperature']
         self.conf_matrix = conf_matrix
         self.gt_pad_sampler = gt_pad_sampler
+        self.loss_stats = loss_stats
 
     def forward(self, feat_c0, feat_c1, data, mask_c0=None, mask_c1=None):
         """Writes b_ids, i_ids, j_ids, gt_mask, m_bids, mkpts0_c, mkpts1_c, mconf (and conf_matrix on
@@ -52,13 +58,16 @@ class CoarseMatching(nn.Module):
         supervision ids data['spv_*_ids'] (:113-116); data['conf_matrix'] then carries the gradient of the dual
         softmax (the match lists themselves are not differentiable, as in the reference's @torch.no_grad
         get_coarse_match)."""
-        if self.training and not self.conf_matrix:
-            raise RuntimeError("training-mode CoarseMatching needs conf_matrix=True (the loss reads data['conf_matrix'])")
+        if self.training and not (self.conf_matrix or self.loss_stats):
+            raise RuntimeError("training-mode CoarseMatching needs conf_matrix=True (the loss reads data['conf_matrix']) "
+                               "or loss_stats=True (CoarseLoss reads the softmax statistics)")
         scale = data['hw0_i'][0] / data['hw0_c'][0]
         with torch.no_grad():
             out = ops.coarse_match(feat_c0, feat_c1, data['hw0_c'], data['hw1_c'], scale, self.thr, self.border_rm,
                                    self.temperature, data.get('scale0'), data.get('scale1'),
-                                   conf_matrix=self.conf_matrix)
+                                   conf_matrix=self.conf_matrix, stats=self.loss_stats)
+        if self.loss_stats:
+            data['_fm_coarse_loss'] = (out['_coarse_buffers'], feat_c0, feat_c1)
         if self.conf_matrix:
             conf = out['conf_matrix']
             if torch.is_grad_enabled() and (feat_c0.requires_grad or feat_c1.requires_grad):
@@ -98,6 +107,31 @@ class CoarseMatching(nn.Module):
         data.update({'b_ids': b_ids, 'i_ids': i_ids, 'j_ids': j_ids,
                      'gt_mask': mconf == 0, 'm_bids': b_ids,
                      'mkpts0_c': mkpts0_c, 'mkpts1_c': mkpts1_c, 'mconf': mconf[mconf != 0] if padded else mconf})
+
+
+class CoarseLoss(nn.Module):
+    """Loss.compute_coarse_loss (losses/loss.py:27-67) without conf_matrix and conf_matrix_gt: forward(data) reads the
+    supervision ids data['spv_b_ids' | 'spv_i_ids' | 'spv_j_ids'] (compute_supervision_coarse writes them next to
+    conf_matrix_gt) and what CoarseMatching(..., loss_stats=True) left under data['_fm_coarse_loss'], and returns the
+    loss the reference computes from the two [N, L, S] arrays (ops.coarse_loss).  `config`: the reference's loss section
+    (coarse_type, focal_alpha, focal_gamma, pos_weight, neg_weight); `sparse_spvs`: config['module']['match_coarse']
+    ['sparse_spvs'] of the reference."""
+
+    def __init__(self, config, sparse_spvs: bool = False):
+        super().__init__()
+        self.coarse_type = config['coarse_type']
+        self.alpha = config.get('focal_alpha', 0.25)
+        self.gamma = config.get('focal_gamma', 2.0)
+        self.pos_weight = config.get('pos_weight', 1.0)
+        self.neg_weight = config.get('neg_weight', 1.0)
+        self.sparse_spvs = sparse_spvs
+
+    def forward(self, data):
+        if '_fm_coarse_loss' not in data:
+            raise RuntimeError("CoarseLoss needs the statistics of CoarseMatching(..., loss_stats=True)")
+        buffers, feat_c0, feat_c1 = data['_fm_coarse_loss']
+        return ops.coarse_loss(feat_c0, feat_c1, data['spv_b_ids'], data['spv_i_ids'], data['spv_j_ids'], buffers,
+                               self.coarse_type, self.alpha, self.gamma, self.pos_weight, self.neg_weight, self.sparse_spvs)
 
 
 class FinePreprocess(nn.Module):

@@ -510,6 +510,84 @@ def attach_conf_matrix_grad(feat_c0: torch.Tensor, feat_c1: torch.Tensor, conf_m
     return _ConfMatrixGrad.apply(feat_c0, feat_c1, conf_matrix, temperature, buffers)
 
 
+_LOSS_KINDS = {'cross_entropy': _lib.FM_LOSS_CROSS_ENTROPY, 'focal': _lib.FM_LOSS_FOCAL}
+
+
+def _distinct_entries(b_ids, i_ids, j_ids, l: int, s: int, device):
+    """the distinct (b, i, j) triples, as conf_matrix_gt[b, i, j] = 1 collapses repeated ones: one torch.unique over a
+    linearised int64 key (its data-dependent output size is a host sync)"""
+    b, i, j = (torch.as_tensor(t).to(device=device, dtype=torch.int64) for t in (b_ids, i_ids, j_ids))
+    key = torch.unique((b * l + i) * s + j)
+    rows = torch.div(key, s, rounding_mode='floor')
+    return torch.div(rows, l, rounding_mode='floor'), rows % l, key % s
+
+
+class _CoarseLoss(torch.autograd.Function):
+    """fm_coarse_loss_forward / fm_coarse_loss_backward: the workspace of the forward call (row / column sums of
+    dloss/dconf * conf, the entries' terms) stays on ctx for the backward call."""
+
+    @staticmethod
+    def forward(ctx, feat_c0, feat_c1, bb, ii, jj, buffers, kind, alpha, gamma, pos_weight, neg_weight):
+        lib = _lib.load()
+        x0, x1 = _f32c(feat_c0, "feat_c0"), _f32c(feat_c1, "feat_c1")
+        n, l, c = x0.shape
+        s = x1.shape[1]
+        k = int(bb.shape[0])
+        need = int(lib.fm_coarse_loss_workspace_bytes(n, l, s, c, k))
+        ws = torch.empty(need + 256, dtype=torch.uint8, device=x0.device)
+        out = torch.empty(3, dtype=torch.float32, device=x0.device)
+        ids = (_ptr(bb), _ptr(ii), _ptr(jj)) if k else (None, None, None)
+        problem = (_ptr(x0), _ptr(x1), n, l, s, c, float(buffers._temperature), *buffers.softmax_stats(), kind, float(alpha),
+                   float(gamma), float(pos_weight), float(neg_weight), *ids, k,
+                   C.c_void_p(ws.data_ptr() + (-ws.data_ptr()) % 256), need)
+        _lib.check(lib.fm_coarse_loss_forward(*problem, _ptr(out), _stream(x0.device)), "fm_coarse_loss_forward")
+        ctx.problem, ctx.keep = problem, (x0, x1, bb, ii, jj, ws, buffers)
+        ctx.dtypes = (feat_c0.dtype, feat_c1.dtype)
+        ctx.mark_non_differentiable(out)
+        return out[0].clone(), out
+
+    @staticmethod
+    def backward(ctx, grad, _):
+        lib = _lib.load()
+        x0, x1 = ctx.keep[0], ctx.keep[1]
+        d_loss = grad.detach().to(torch.float32).reshape(1).contiguous()
+        d0, d1 = torch.empty_like(x0), torch.empty_like(x1)
+        _lib.check(lib.fm_coarse_loss_backward(*ctx.problem, _ptr(d_loss), _ptr(d0), _ptr(d1), _stream(x0.device)),
+                   "fm_coarse_loss_backward")
+        d0._keep = (ctx.keep, d_loss)
+        return (d0.to(ctx.dtypes[0]), d1.to(ctx.dtypes[1])) + (None,) * 9
+
+
+def coarse_loss(feat_c0: torch.Tensor, feat_c1: torch.Tensor, b_ids, i_ids, j_ids, buffers: CoarseBuffers,
+                coarse_type: str = 'focal', alpha: float = 0.25, gamma: float = 2.0, pos_weight: float = 1.0,
+                neg_weight: float = 1.0, sparse_spvs: bool = False) -> torch.Tensor:
+    """What the reference's Loss.compute_coarse_loss(conf_matrix, conf_matrix_gt) returns (losses/loss.py:27-67), as a
+    differentiable function of the descriptors, without conf_matrix and without conf_matrix_gt: the supervision is the
+    id lists compute_supervision_coarse writes (spv_b_ids, spv_i_ids, spv_j_ids; any integer type, repeated triples
+    count once) and `buffers` the CoarseBuffers of a coarse call on the same descriptors that ran with stats=True or
+    conf_matrix=True, as for dual_softmax_at.  'cross_entropy' and 'focal' over all negatives are one tiled HIP sweep
+    forward and two backward (fm_coarse_loss_forward / _backward), O(N (L + S) C) bytes; 'focal' with sparse_spvs reads
+    the supervised entries only and goes through dual_softmax_at.  One host sync: the number of distinct triples
+    (torch.unique).  An empty supervision and the upstream gradient are handled on the device.  The returned scalar
+    carries `.means` = (mean positive term, mean negative term) for logging (dense forms only)."""
+    if coarse_type not in _LOSS_KINDS:
+        raise ValueError(f"coarse_type {coarse_type!r}: 'focal' or 'cross_entropy'")
+    if not gamma > 0:
+        raise ValueError("gamma must be positive")
+    l, s = feat_c0.shape[1], feat_c1.shape[1]
+    bb, ii, jj = _distinct_entries(b_ids, i_ids, j_ids, l, s, feat_c0.device)
+    if coarse_type == 'focal' and sparse_spvs:                   # loss.py:57-61
+        if bb.shape[0] == 0:                                       # :37-39: entry (0, 0, 0) with weight 0
+            bb = ii = jj = torch.zeros(1, dtype=torch.int64, device=feat_c0.device)
+            pos_weight = 0.0
+        p = torch.clamp(dual_softmax_at(feat_c0, feat_c1, bb, ii, jj, buffers), 1e-6, 1 - 1e-6)
+        return pos_weight * (-alpha * torch.pow(1 - p, gamma) * p.log()).mean()
+    loss, out = _CoarseLoss.apply(feat_c0, feat_c1, bb, ii, jj, buffers, _LOSS_KINDS[coarse_type], alpha, gamma, pos_weight,
+                                  neg_weight)
+    loss.means = out[1:]
+    return loss
+
+
 def gather_windows(feat_f: torch.Tensor, b_ids: torch.Tensor, ids: torch.Tensor, w: int, stride: int,
                    w_c: int, pad: int = 2, count: Optional[torch.Tensor] = None,
                    out: Optional[torch.Tensor] = None, cells=None, h_c: Optional[int] = None) -> torch.Tensor:

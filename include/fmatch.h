@@ -556,6 +556,40 @@ int fm_dual_softmax_backward_dense(const float* feat0, const float* feat1, int N
                                    int pitch_c, const float* G, void* workspace, size_t workspace_bytes, float* d_feat0,
                                    float* d_feat1, void* stream);
 
+/*
+ * The reference's coarse loss over ALL entries of conf_matrix (losses/loss.py:44-50 cross entropy, :62-67 focal with
+ * sparse_spvs = False) and its gradient w.r.t. the descriptors, without conf_matrix, conf_matrix_gt or any other
+ * [N, L, S] array.  With c = clamp(conf, lo, hi) (lo, hi: the float32 roundings of 1e-6 and 1 - 1e-6, the bounds the
+ * reference's float32 clamp uses), P the K supervised entries (b_ids, i_ids, j_ids [dev] int64, DISTINCT triples):
+ *     loss = neg_weight / (N L S - K) * ( sum_all l_neg(c) - sum_P l_neg(c_e) ) + pos_weight / K * sum_P l_pos(c_e)
+ *     FM_LOSS_CROSS_ENTROPY : l_pos = -log c,                         l_neg = -log(1 - c)
+ *     FM_LOSS_FOCAL         : l_pos = -alpha (1 - c)^gamma log c,     l_neg = -alpha c^gamma log(1 - c)
+ * conf is recomputed tile by tile from exact float32 dot products and the softmax statistics of the coarse call
+ * (fm_coarse_softmax_stats), as in fm_dual_softmax_backward_dense; dloss/dconf is formed in registers.
+ *   fm_coarse_loss_forward  : loss_out [dev] float32 [3] = {loss, mean of l_pos over P, mean of l_neg over the negatives}.
+ *                             The loss is the same bits on every run (its sums are taken in a fixed order).  One sweep.
+ *   fm_coarse_loss_backward : d_feat0 [N,L,C], d_feat1 [N,S,C] = d_loss[0] * dloss/dfeat; d_loss [dev] float32 [1] is read
+ *                             on the device.  Same problem arguments as the forward call and ITS workspace, untouched
+ *                             since.  Two sweeps; reproducible to float32 rounding as fm_dual_softmax_backward_dense.
+ * workspace: fm_coarse_loss_workspace_bytes bytes [dev], 256-byte aligned (0 for an invalid shape).  No host
+ * synchronisation in either call.  K = 0 (the id pointers may be NULL) and K = N L S are the reference's degenerate cases
+ * (loss.py:37-42): entry (0, 0, 0) stands in as the one positive with pos_weight 0 and, as in the reference, stays among
+ * the N L S negatives; without a negative neg_weight counts as 0 and loss_out[2] is 0.  Statuses: FM_E_NULL, FM_E_SHAPE (K < 0, K > N L S, non-positive sizes, pitches below L / S),
+ * FM_E_UNSUPPORTED (C, temperature <= 0, unknown kind, gamma <= 0), FM_E_WORKSPACE (too small / misaligned), a hipError_t.
+ */
+enum fm_loss_kind { FM_LOSS_CROSS_ENTROPY = 0, FM_LOSS_FOCAL = 1 };
+size_t fm_coarse_loss_workspace_bytes(int N, int L, int S, int C, int K);
+int fm_coarse_loss_forward(const float* feat0, const float* feat1, int N, int L, int S, int C, float temperature,
+                           const float* nm_r, const float* sum_r, int pitch_r, const float* nm_c, const float* sum_c,
+                           int pitch_c, int kind, float alpha, float gamma, float pos_weight, float neg_weight,
+                           const int64_t* b_ids, const int64_t* i_ids, const int64_t* j_ids, int K, void* workspace,
+                           size_t workspace_bytes, float* loss_out, void* stream);
+int fm_coarse_loss_backward(const float* feat0, const float* feat1, int N, int L, int S, int C, float temperature,
+                            const float* nm_r, const float* sum_r, int pitch_r, const float* nm_c, const float* sum_c,
+                            int pitch_c, int kind, float alpha, float gamma, float pos_weight, float neg_weight,
+                            const int64_t* b_ids, const int64_t* i_ids, const int64_t* j_ids, int K, void* workspace,
+                            size_t workspace_bytes, const float* d_loss, float* d_feat0, float* d_feat1, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -77,8 +77,10 @@ __global__ __launch_bounds__(256) void k_fine_bwd(const float* __restrict__ win0
     const float dvy = vy >= 1e-10f ? g[2] * 0.5f / sqrtf(vy) : 0.f;
     const float k = (float)(W / 2) * scale_f;
     const float dcx = g[0] * k - 2.f * cx * dvx, dcy = g[1] * k - 2.f * cy * dvy;
-    const float hdh = dcx * cx + dcy * cy + dvx * ex2 + dvy * ey2;          // sum_r h dh
-    const float dh = dcx * gx + dcy * gy + dvx * gx * gx + dvy * gy * gy;
+    // (both sums as the SAME explicit fma chain: left to the compiler the two expressions contract in different orders
+    // and a one-hot heat map - cx == gx, cy == gy bit for bit, ds = 0 exactly - got an ulp of dh as its gradient)
+    const float hdh = __builtin_fmaf(dvy, ey2, __builtin_fmaf(dvx, ex2, __builtin_fmaf(dcy, cy, dcx * cx)));   // sum_r h dh
+    const float dh = __builtin_fmaf(dvy * gy, gy, __builtin_fmaf(dvx * gx, gx, __builtin_fmaf(dcy, gy, dcx * gx)));
     ds[d] = s.on ? (d ? e.e1 : e.e0) * inv * (dh - hdh) : 0.f;
   }
   // lane = channel again: ds[r] is read from the lane that holds position r (tr_index: r itself, or 2r at NP = 32)

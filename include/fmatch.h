@@ -349,6 +349,9 @@ int fm_gather_merge_windows_nhwc(const void* feat_f0, const void* feat_f1, int m
  * mix0/mix1 [dev] float32 [WW+1] = Linear(WW,1) weight then bias;
  * out0/out1 [m_max,3] = (x_px, y_px, std) with
  *   xy = mkpts_c + coords*(W/2)*scale_f + W/2        (:75-76)
+ * d_count [dev] may be NULL: the list then has m_max rows.  Rows at or beyond min(*d_count, m_max) are left
+ * untouched - out0 / out1 keep whatever they held - and nothing of those rows is read (windows, mkpts*_c);
+ * *d_count = 0 writes nothing, m_max = 0 returns at once.  The counted rows do not depend on the count.
  */
 int fm_fine_match(const float* win0, const float* win1, int m_max, const int32_t* d_count,
                   int WW, int Cf, const float* mix0, const float* mix1,
@@ -408,7 +411,12 @@ int fm_gather_windows_backward(const float* d_win, const int64_t* b_ids, const i
  * NCHW map as it is (the match list walks image 0 in raster order, which the NCHW window loader copes with); image 1,
  * whose windows land wherever the partners are, first gets a channels-last copy in `scratch`
  * (fm_fine_maps_scratch_bytes bytes [dev], 16-byte aligned; 0 bytes / NULL for layout 1) by a tiled transpose.  b_ids / i_ids / j_ids, d_count, mkpts*_c as the coarse stage left them; mix0 / mix1, scale_f,
- * out0 / out1 as in fm_fine_match.  Cf = 64, W in {5,7}.  Results equal fm_gather_windows + fm_fine_match bit for bit.
+ * out0 / out1 as in fm_fine_match.  Cf = 64, W in {5,7}.  Results equal fm_gather_windows + fm_fine_match bit for bit,
+ * at any stride and pad, for any order of b_ids, and whether or not w0c / w1c times the stride equals the map (cells
+ * beyond the map give zero windows).  The count as in fm_fine_match: d_count may be NULL; rows at or beyond
+ * min(*d_count, m_max) are left untouched in out0 / out1 and their ids are not read; *d_count = 0 writes nothing (the
+ * channels-last copies of layout 0 are still made).  The same holds for fm_fine_match_maps_dtype below and for
+ * layout = FM_LAYOUT_NCHW_PREPARED.
  */
 #define FM_LAYOUT_NCHW_PREPARED 2  /* layout of fm_fine_match_maps*: NCHW maps whose image-1 channels-last copy already sits in
                                      `scratch` - made by fm_coarse_match_maps, whose assignment launch carries the

@@ -13,7 +13,9 @@ def grid(w: int, dtype=torch.float64):
 
 
 def fine_forward(win0, win1, mix0, mix1, mkpts0_c, mkpts1_c, scale):
-    """(out0, out1) [M, 3] = (x, y, std) in the dtype of the inputs; mix = [WW + 1] (weights, then bias)"""
+    """(out0, out1) [M, 3] = (x, y, std) in the dtype of the inputs; mix = [WW + 1] (weights, then bias).
+    fine_forward_parts below repeats this body line for line (tests/test_fine_ref.py holds the two to torch.equal):
+    an edit here belongs there too"""
     m, ww, c = win0.shape
     w = int(math.isqrt(ww))
     gx, gy = (g.to(win0.dtype).to(win0.device) for g in grid(w))
@@ -26,6 +28,137 @@ def fine_forward(win0, win1, mix0, mix1, mkpts0_c, mkpts1_c, scale):
         std = torch.sqrt(torch.clamp(var, min=1e-10)).sum(1)
         outs.append(torch.cat([kc + co * (w // 2) * scale + w // 2, std[:, None]], 1))
     return outs[0], outs[1]
+
+
+def fine_forward_parts(win0, win1, mix0, mix1, mkpts0_c, mkpts1_c, scale):
+    """fine_forward, plus what the keypoint add and the clamp hide: (out0, out1, off0, off1, var0, var1) with
+    off_d [M, 2] = co * (W // 2) * scale + W // 2 (the offsets before mkpts_c is added) and var_d [M, 2] = the (x, y)
+    variances of the heat map before clamp(min=1e-10); out_d is fine_forward's, operation for operation.  The dtype
+    follows the inputs"""
+    m, ww, c = win0.shape
+    w = int(math.isqrt(ww))
+    gx, gy = (g.to(win0.dtype).to(win0.device) for g in grid(w))
+    outs, offs, vars_ = [], [], []
+    for wa, wb, mix, kc in ((win0, win1, mix0, mkpts0_c), (win1, win0, mix1, mkpts1_c)):
+        q = torch.einsum('r,mrc->mc', mix[:ww], wa) + mix[ww]
+        h = torch.softmax(torch.einsum('mc,mrc->mr', q, wb) / math.sqrt(c), dim=1)
+        co = torch.stack([(h * gx).sum(1), (h * gy).sum(1)], 1)
+        var = torch.stack([(h * gx * gx).sum(1), (h * gy * gy).sum(1)], 1) - co ** 2
+        std = torch.sqrt(torch.clamp(var, min=1e-10)).sum(1)
+        outs.append(torch.cat([kc + co * (w // 2) * scale + w // 2, std[:, None]], 1))
+        offs.append(co * (w // 2) * scale + w // 2)
+        vars_.append(var)
+    return outs[0], outs[1], offs[0], offs[1], vars_[0], vars_[1]
+
+
+# ---- inputs with known answers (tests/test_fine_ref.py pins them on the yardstick, tests/test_gpu_fine_forward.py
+# runs them on the device).  All of them: mix weights 0, bias 1, so q = 1 in every channel and the logit of window
+# position r is sum_c win_other[r, c] / 8.
+def known_mix(ww: int, dtype=torch.float64):
+    mix = torch.zeros(ww + 1, dtype=dtype)
+    mix[ww] = 1
+    return mix
+
+
+def one_hot_windows(w: int, direction: int, dtype=torch.float64):
+    """(win0, win1) [WW, WW, 64]: match r has a heat map of `direction` that is one-hot at window position r (the window
+    that direction correlates against is 40 at position r in every channel: logit 320 there, 0 elsewhere; exp(-320)
+    is 0 in float32 and 1e-139 in float64).  The other window is zero, so the other direction's heat map is flat;
+    direction 2: both windows are the hot one, both heat maps one-hot at r"""
+    ww = w * w
+    hot = torch.zeros(ww, ww, 64, dtype=dtype)
+    hot[torch.arange(ww), torch.arange(ww)] = 40
+    zero = torch.zeros(ww, ww, 64, dtype=dtype)
+    if direction == 2:
+        return hot, hot.clone()
+    return (zero, hot) if direction == 0 else (hot, zero)     # direction 0 reads its heat map off win1
+
+
+def two_point_windows(w: int, dtype=torch.float64):
+    """(win0, win1, pairs): match k has the same window on both sides, 40 at the two positions pairs[k] = (r, s) in
+    every channel: both directions' heat maps are 1/2 at r and at s (everything else exp(-320))"""
+    ww = w * w
+    g = torch.Generator().manual_seed(w)
+    r = torch.arange(ww)
+    s = (r + 1 + torch.randint(ww - 1, (ww,), generator=g)) % ww          # any other position
+    win = torch.zeros(ww, ww, 64, dtype=dtype)
+    win[r, r] = 40
+    win[r, s] = 40
+    return win, win.clone(), torch.stack([r, s], 1)
+
+
+def two_point_answer(w: int, pairs, scale: float):
+    """(off [K, 2], var [K, 2]) float64: the closed form for a heat map that is 1/2 at each of the two positions
+    pairs[k] - the mean of the two grid points, and per axis the square of half their distance"""
+    g = torch.stack(grid(w), 1)                                        # [WW, 2]
+    a, b = g[pairs[:, 0]], g[pairs[:, 1]]
+    return (a + b) / 2 * (w // 2) * scale + w // 2, ((a - b) / 2) ** 2
+
+
+def flat_answer(w: int, k: int):
+    """(off [K, 2], var [K, 2]) float64 of a flat heat map: the window centre, and the mean of the squared grid"""
+    gx, _ = grid(w)
+    return torch.full((k, 2), float(w // 2), dtype=torch.float64), torch.full((k, 2), (gx ** 2).mean().item(),
+                                                                             dtype=torch.float64)
+
+
+# ---- the regimes of the fine forward's accuracy test: windows gain * N(0, 1)
+FINE_GAINS = (0.0, 0.02, 0.3, 1.0, 3.0, 10.0)
+FINE_M = 2002           # >= 2000, no multiple of 4 (k_fine runs four matches per workgroup)
+FINE_TIED = 300         # the first rows have win1 = 3 * win0 (the recipe of test_fine_match_vs_oracle)
+FINE_SCALE = 2.0
+
+
+def regime_inputs(w: int, gain: float, m: int = FINE_M):
+    """(win0, win1, mix0, mix1) float32 on the CPU, seeded by (W, gain): windows gain * N(0, 1), the first FINE_TIED
+    rows with win1 = 3 * win0, mix = [WW + 1] uniform in +-1/sqrt(WW) (torch's init range of Linear(WW, 1))"""
+    ww = w * w
+    g = torch.Generator().manual_seed(1000 * w + int(round(gain * 100)))
+    win0 = gain * torch.randn(m, ww, 64, generator=g)
+    win1 = gain * torch.randn(m, ww, 64, generator=g)
+    win1[:FINE_TIED] = 3 * win0[:FINE_TIED]
+    mix0, mix1 = ((2 * torch.rand(ww + 1, generator=g) - 1) / math.sqrt(ww) for _ in range(2))
+    return win0, win1, mix0, mix1
+
+
+def fine_yardstick(win0, win1, mix0, mix1, scale=FINE_SCALE):
+    """(off64 [M, 4], var64 [M, 4], e32, d0) of float32 inputs with mkpts_c = 0: the float64 offsets and variances
+    (columns: direction 0 x, y, direction 1 x, y) and the errors of torch's float32 fine_forward_parts on the very same
+    inputs against them - e32 = its largest offset error (px), d0 = its largest variance error.  Nothing here comes
+    from a kernel"""
+    z = torch.zeros(win0.shape[0], 2)
+    p64 = fine_forward_parts(win0.double(), win1.double(), mix0.double(), mix1.double(), z.double(), z.double(), scale)
+    p32 = fine_forward_parts(win0, win1, mix0, mix1, z, z, scale)
+    off64, var64 = torch.cat(p64[2:4], 1), torch.cat(p64[4:6], 1)
+    e32 = (torch.cat(p32[2:4], 1).double() - off64).abs().max().item()
+    d0 = (torch.cat(p32[4:6], 1).double() - var64).abs().max().item()
+    return off64, var64, e32, d0
+
+
+# the float32 kernel sums in another order and uses the hardware exponential: FINE_MULT times the error of torch's own
+# float32 forward, plus a floor of FINE_FLOOR_ULPS float32 ulps of the offset range W // 2 * scale (offsets) and of 1
+# (variances: sums of heat * g^2 <= 1)
+FINE_MULT = 4.0
+FINE_FLOOR_ULPS = 4
+F32_EPS = 2.0 ** -23
+
+
+FINE_CAP_PX = 1e-4        # up to gain 3 the offset bar never exceeds a tenth of the older tests' 1e-3 px
+
+
+def fine_bars(w: int, e32: float, d0: float, scale=FINE_SCALE, mult=FINE_MULT, cap_off=None):
+    """(offset bar in px, variance bar); cap_off: an upper limit of the offset bar (e32 is a float32 sum on the CPU and
+    moves with the number of threads torch sums with: the cap keeps the bar where the regime test promises it)"""
+    bar_off = mult * e32 + FINE_FLOOR_ULPS * F32_EPS * (w // 2) * scale
+    return (bar_off if cap_off is None else min(bar_off, cap_off)), mult * d0 + FINE_FLOOR_ULPS * F32_EPS
+
+
+def std_interval(var64, d):
+    """[M, 2] -> (lo, hi) [M]: the std a forward may give whose variances are within d of var64, sum over the axes of
+    sqrt(max(v -+ d, 1e-10))"""
+    lo = torch.sqrt(torch.clamp(var64 - d, min=1e-10)).sum(1)
+    hi = torch.sqrt(torch.clamp(var64 + d, min=1e-10)).sum(1)
+    return lo, hi
 
 
 def fine_backward(win0, win1, mix0, mix1, scale, d_out0, d_out1):

@@ -12,7 +12,7 @@ from featurematching_amd import modules, ops, synth
 from featurematching_amd.transformer import LocalFeatureTransformer
 from oracle import matcher_ref as orc
 
-from fine_grad_ref import crop_adjoint, fine_forward, grid
+from fine_grad_ref import crop_adjoint, fine_forward, grid, known_mix, one_hot_windows, regime_inputs
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -103,6 +103,80 @@ def test_fine_backward_against_float64(size, w, target):
     # the forward of the autograd path is fine_match itself
     ref0, ref1 = ops.fine_match(win0.to(DEV), win1.to(DEV), mix0.to(DEV), mix1.to(DEV), k0.to(DEV), k1.to(DEV), scale)
     assert torch.equal(ohip[0], ref0.double().cpu()) and torch.equal(ohip[1], ref1.double().cpu())
+
+
+@pytest.mark.parametrize("w", [5, 7])
+@pytest.mark.parametrize("direction", [0, 1, 2])
+def test_fine_backward_on_one_hot_heat_maps(w, direction):
+    """The one-hot inputs of tests/test_gpu_fine_forward.py (match r one-hot at window position r; direction 2: both
+    heat maps at once) with a random d_out whose std component is not zero.  The variance of a one-hot map is below the
+    clamp (0, or the -3e-9 the FMA leaves at W = 7), so the branch vx >= 1e-10f of fine_grad.hip decides here while
+    g[2] != 0: every gradient is finite, and where both heat maps are one-hot d_win0, d_win1 and d_mix are exactly
+    zero - a one-hot h gives ds = h (dh - sum h dh) = 0, and the clamp passes nothing back.  (With one direction
+    one-hot the other one's heat map is flat and has gradients of its own: finite is all that is asked there.)
+
+    This test found a defect, fixed with it.  fine_grad.hip formed sum h dh = dcx cx + dcy cy + ... and
+    dh = dcx gx + dcy gy + ... as two plain expressions, which the compiler contracted into FMAs in different orders.
+    At W = 5 every grid value is a power of two or 0 and the products are exact; at W = 7 (thirds) the two sums rounded
+    differently although cx == gx bit for bit, and with both heat maps one-hot d_win0 came out as 1.192e-07 (one
+    float32 ulp of dh, times t q = 0.125) instead of 0.  Both sums are now the same explicit fmaf chain, identical
+    operation for operation when cx == gx, cy == gy and dvx = dvy = 0; all six cases pass.
+
+    There is no std-gradient test against float64 on sharp heat maps: with a variance near 1e-7 the float32 variance -
+    a difference of two numbers near 1 - is 40 % rounding noise, its gradient 1 / (2 sqrt(var)) with it, and no
+    yardstick separates a right kernel from a wrong one there."""
+    ww = w * w
+    win0, win1 = one_hot_windows(w, direction, torch.float32)
+    mix = known_mix(ww, torch.float32)
+    g = torch.Generator().manual_seed(w)
+    d0, d1 = torch.randn(ww, 3, generator=g), torch.randn(ww, 3, generator=g)
+    assert (d0[:, 2] != 0).all() and (d1[:, 2] != 0).all()
+    leaves = [t.to(DEV).clone().requires_grad_(True) for t in (win0, win1, mix, mix)]
+    z = torch.zeros(ww, 2, device=DEV)
+    o0, o1 = ops.fine_match_grad(*leaves, z, z, 2.0)
+    ((o0 * d0.to(DEV)).sum() + (o1 * d1.to(DEV)).sum()).backward()
+    for name, t in zip(("d_win0", "d_win1", "d_mix0", "d_mix1"), leaves):
+        assert torch.isfinite(t.grad).all(), name
+        if direction == 2:
+            assert (t.grad == 0).all(), f"{name}: max |g| {t.grad.abs().max().item():.3e}"
+
+
+# (W, gain): the regimes of the forward test (tests/fine_grad_ref.py: regime_inputs).  Gain 0, 3 and 10 were asked for;
+# at W = 5, gain 10 torch's own float32 autograd is off by up to 5.6e-5 of max |g64| (CPU, 600 matches) - more than a
+# quarter of the bar, which then could not tell a right kernel from a wrong one - so that case runs at gain 5 (1.5e-5)
+XY_REGIMES = [(5, 0.0), (5, 3.0), (5, 5.0), (7, 0.0), (7, 3.0), (7, 10.0)]
+
+
+@pytest.mark.parametrize("w,gain", XY_REGIMES)
+def test_fine_backward_xy_target_by_regime(w, gain):
+    """the xy gradient on flat (gain 0), partly sharp (3) and mostly sharp (5 / 10) heat maps at the project's bar
+    1e-4 * max |g64|, kept only where torch float32's own error on the same data is at most a quarter of it (asserted
+    here from the CPU alone)"""
+    m = 600
+    win0, win1, mix0, mix1 = regime_inputs(w, gain, m=m)
+    g = torch.Generator().manual_seed(2)
+    wt0, wt1 = torch.randn(m, 3, generator=g), torch.randn(m, 3, generator=g)
+    wt0[:, 2] = 0
+    wt1[:, 2] = 0
+
+    def grads(dtype, fn, dev):
+        leaves = [t.detach().to(dev, dtype).clone().requires_grad_(True) for t in (win0, win1, mix0, mix1)]
+        z = torch.zeros(m, 2, device=dev, dtype=dtype)
+        o0, o1 = fn(*leaves, z, z, 2.0)
+        ((o0 * wt0.to(dev, dtype)).sum() + (o1 * wt1.to(dev, dtype)).sum()).backward()
+        return [t.grad.double().cpu() for t in leaves]
+
+    g64 = grads(torch.float64, fine_forward, "cpu")
+    g32 = grads(torch.float32, fine_forward, "cpu")
+    ghip = grads(torch.float32, ops.fine_match_grad, DEV)
+    for name, a, b, c in zip(("d_win0", "d_win1", "d_mix0", "d_mix1"), ghip, g64, g32):
+        scale_ = b.abs().max().item()
+        err, err32 = (a - b).abs().max().item(), (c - b).abs().max().item()
+        print(f"W={w} gain={gain:g} xy {name}: |hip - f64| {err:.3e}, |torch f32 - f64| {err32:.3e}, max|g| {scale_:.3e}")
+        assert scale_ > 0 or (gain == 0 and name.startswith("d_mix"))      # zero windows: d_mix is exactly zero
+        assert err32 <= 0.25e-4 * scale_, f"{name}: torch float32 is itself off by {err32 / scale_:.2e}"
+        assert torch.isfinite(a).all() and err <= 1e-4 * scale_, \
+            f"W={w} gain={gain} {name}: |hip - f64| {err:.3e}, |torch f32 - f64| {err32:.3e}, max|g| {scale_:.3e}"
 
 
 def test_fine_backward_rows_beyond_the_count_and_determinism():

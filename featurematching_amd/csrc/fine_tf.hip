@@ -32,6 +32,8 @@
 // pre-split and pre-permuted into operand fragments by fm_fine_tf_pack_weights: an accumulator-derived fragment of
 // k-step s holds k = 16 s + 8 (j >> 2) + 4 h + (j & 3) in element j of lane half h, so the weight fragments use the
 // same order.
+#include <cstdint>
+
 #include "fm_internal.h"
 
 namespace fm {
@@ -266,7 +268,12 @@ __device__ __forceinline__ void kv_phase(const float* src, const half8* lb, floa
       for (int g = 0; g < 16; ++g) {
         const bool tok_ok = 32 * ct + (g & 3) + 8 * (g >> 2) + 4 * h < WW;      // padded tokens stay out of the sums
         k[ot][g] = tok_ok ? elu1_scaled(k[ot][g] * (1.0f / kWgtScale), A) : 0.f;
-        v[ot][g] = v[ot][g] * (1.0f / kWgtScale) * (1.0f / (float)WW);          // values / S (attentions.py:41-42)
+        // (the values as they are: their / S (attentions.py:41-42) is applied to the KV sums below - divided first, the
+        // v / S of windows of magnitude 1e-3 sat 25..49x deeper among the operands whose lo half is a float16
+        // subnormal: tools/emulate_fine_tf_split.py puts the split's share of those matches' error at 1.1e-5 / 1.7e-5
+        // (W = 5 / 7) with v / S - the kernel measured 1.28e-5 at W = 5, profiles/ctx_layers_accuracy.txt - and at
+        // 5.0e-6 / 4.4e-6 with v)
+        v[ot][g] = v[ot][g] * (1.0f / kWgtScale);
         ks[ot] += k[ot][g];
       }
     // KV += K^T . V over this slice's tokens: only the two diagonal 32 x 32 tiles hold head blocks
@@ -290,7 +297,8 @@ __device__ __forceinline__ void kv_phase(const float* src, const half8* lb, floa
   for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
     for (int g = 0; g < 16; ++g)            // keep d / 8 == v / 8 (rows d = (g&3) + 8 (g>>2) + 4 h, column v = r)
-      kv[dt][g] = ((g >> 2) != (r >> 3)) ? 0.f : kv[dt][g] * A.inv;     // back to the operand scale
+      // (/ S; back to the operand scale)
+      kv[dt][g] = ((g >> 2) != (r >> 3)) ? 0.f : kv[dt][g] * (A.inv * (1.0f / (float)WW));
 #pragma unroll
   for (int s = 0; s < 4; ++s) split8(kv[s >> 1], s & 1, st.ah[s], st.al[s], amax);
 }
@@ -437,8 +445,9 @@ __global__ __launch_bounds__(NW * 64) void k_fine_tf(const float* win0, const fl
   float amax = 0.f;                     // largest magnitude that went into a float16 operand (operand scale)
   // A match whose operands leave float16 at the current activation scale starts again from its input windows with a
   // 16x smaller one (the calls read win0 / win1 first and run in place on the outputs afterwards, so a restart is
-  // clean).  The waves of a workgroup share the staged weights and their barriers: all of them repeat the pass when any
-  // of them has to, the ones that were inside the range with their own scale (and the same result).
+  // clean - as long as no output overlaps an input, which fm_fine_transformer_start refuses).  The waves of a
+  // workgroup share the staged weights and their barriers: all of them repeat the pass when any of them has to, the
+  // ones that were inside the range with their own scale (and the same result).
   // (the first attempt's scale: 2^8 unless the caller knows better - fm_fine_transformer_start: a module that saw its
   // matches lower the scale in the previous call starts there, and the repeated passes are gone)
   int e2 = start_e2;                    // (scalar registers: the exponent and the three floats made from it)
@@ -577,6 +586,16 @@ extern "C" int fm_fine_transformer_start(const float* win0, const float* win1, i
   if (!win0 || !win1 || !packed || !out0 || !out1) return FM_E_NULL;
   if (m_max < 0) return FM_E_SHAPE;
   if (Cf != 64 || (WW != 25 && WW != 49)) return FM_E_UNSUPPORTED;
+  {   // no output may overlap an input or the other output (byte ranges, not just equal pointers): a match that lowers
+      // its scale starts again from win0 / win1 and every wave of its workgroup repeats the pass with it, so the windows
+      // must still be the caller's after the first pass has stored; the inputs are only read and may be one buffer
+    const uintptr_t nb = (uintptr_t)m_max * WW * 64 * 4;
+    auto overlap = [nb](const void* a, const void* b) {
+      return (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + nb;
+    };
+    if (overlap(out0, out1) || overlap(out0, win0) || overlap(out0, win1) || overlap(out1, win0) || overlap(out1, win1))
+      return FM_E_UNSUPPORTED;
+  }
   const half8* frag = (const half8*)packed;
   const float* ln = (const float*)((const char*)packed + 2 * (size_t)kTfLayerHalf8 * 16);
   const int32_t* pstat = (const int32_t*)((const char*)packed + kTfPackStatusOff);

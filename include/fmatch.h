@@ -476,14 +476,18 @@ int fm_coarse_transformer_masked(const float* feat0, const float* feat1, const u
  * LocalFeatureTransformer (network/module/transformer.py:34-57,78-96, attentions.py:19-46) in its default fine
  * configuration - d_model 64, 8 heads, layer_names ['self', 'cross'], linear attention, no masks - as ONE kernel,
  * one wave per match working on 32-token slices kept in registers from their load to their store, float32-equivalent
- * products (hi/lo-split float16 MFMAs).  win0/win1, out0/out1 [dev] float32 [m_max, WW, 64], WW in {25, 49}; out may
- * alias win.  packed = fm_fine_tf_packed_bytes() bytes [dev] filled once per weight update by
+ * products (hi/lo-split float16 MFMAs).  win0/win1, out0/out1 [dev] float32 [m_max, WW, 64], WW in {25, 49}.  out0 /
+ * out1 must not overlap win0, win1 or each other, in any byte (FM_E_UNSUPPORTED, nothing is written): a match that
+ * lowers its scale is recomputed from its input windows, which the first pass would already have overwritten.  win0
+ * and win1 are only read and may be one buffer.  Rows at or beyond min(*d_count, m_max) are left untouched (d_count may
+ * be NULL; m_max = 0 writes nothing).  packed = fm_fine_tf_packed_bytes() bytes [dev] filled once per weight update by
  * fm_fine_tf_pack_weights(layer0, layer1, ...): each a HOST array of 10 DEVICE pointers in state-dict order -
  * q_proj, k_proj, v_proj, merge .weight [64,64]; mlp.0.weight [128,128]; mlp.2.weight [64,128]; norm1.weight,
  * norm1.bias, norm2.weight, norm2.bias [64] - of layers.0 ('self') and layers.1 ('cross').
  * Operand scales: weights x 2^12 (fixed: |w| < 16, checked by fm_fine_tf_pack_weights), activations x 2^8 and the
- * per-head sums of elu(k)+1 x 2^5 in float16 at the FIRST attempt - window values, their projections and the MLP's
- * hidden layer below 255.9 in magnitude, sum_s (elu(k)+1) of a head feature below 2047 (LayerNorm-ed activations of a
+ * per-head sums of elu(k)+1 x 2^5 in float16 at the FIRST attempt - window values, their projections, the entries of
+ * K^T V / S and the MLP's hidden layer below 255.9 in magnitude, sum_s (elu(k)+1) of a head feature below 2047
+ * (LayerNorm-ed activations of a
  * trained network are O(1)).  The kernel FOLLOWS the largest magnitude that enters a float16 operand, per match; a
  * match that left the range is recomputed inside the kernel from its input windows with activation (and sum) scales
  * 16x, 256x, 4096x smaller (elements below 2^-3 / scale then lose the lo half of their split: three orders of

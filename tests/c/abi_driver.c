@@ -269,6 +269,27 @@ int main(int argc, char** argv) {
   EXPECT(p_fm_fine_transformer_start(f, f, 4, NULL, 49, 64, (const void*)f, f, f, NULL, 6, NULL, NULL), FM_E_UNSUPPORTED);
   EXPECT(p_fm_fine_transformer_start(f, f, 0, NULL, 49, 64, (const void*)f, f, f, NULL, 4, NULL, NULL), FM_OK);      /* M == 0 */
   EXPECT(p_fm_fine_transformer_start(NULL, f, 4, NULL, 49, 64, (const void*)f, f, f, NULL, 4, NULL, NULL), FM_E_NULL);
+  {
+    /* no output may overlap an input or the other output: equal pointers (in place), crossed pointers, ranges that share
+     * one float, equal outputs - all refused before anything is launched; m_max = 4 windows of 49 x 64 floats */
+    float* w0 = (float*)(uintptr_t)(1u << 20);
+    float* w1 = (float*)(uintptr_t)(2u << 20);
+    float* o0 = (float*)(uintptr_t)(3u << 20);
+    float* o1 = (float*)(uintptr_t)(4u << 20);
+    const int nw = 4 * 49 * 64;
+    EXPECT(p_fm_fine_transformer_start(w0, w1, 4, NULL, 49, 64, (const void*)f, w0, w1, NULL, 8, NULL, NULL), FM_E_UNSUPPORTED);
+    EXPECT(p_fm_fine_transformer_start(w0, w1, 4, NULL, 49, 64, (const void*)f, w0, o1, NULL, 8, NULL, NULL), FM_E_UNSUPPORTED);
+    EXPECT(p_fm_fine_transformer_start(w0, w1, 4, NULL, 49, 64, (const void*)f, o0, w1, NULL, 8, NULL, NULL), FM_E_UNSUPPORTED);
+    EXPECT(p_fm_fine_transformer_start(w0, w1, 4, NULL, 49, 64, (const void*)f, w1, w0, NULL, 8, NULL, NULL), FM_E_UNSUPPORTED);
+    EXPECT(p_fm_fine_transformer_start(w0, w1, 4, NULL, 25, 64, (const void*)f, w1, o1, NULL, 8, NULL, NULL), FM_E_UNSUPPORTED);
+    EXPECT(p_fm_fine_transformer_start(w0, w1, 4, NULL, 49, 64, (const void*)f, o0, o0, NULL, 8, NULL, NULL), FM_E_UNSUPPORTED);
+    EXPECT(p_fm_fine_transformer_start(w0, w1, 4, NULL, 49, 64, (const void*)f, w0 + nw - 1, o1, NULL, 8, NULL, NULL), FM_E_UNSUPPORTED);
+    EXPECT(p_fm_fine_transformer_start(w0, w1, 4, NULL, 49, 64, (const void*)f, o0, w1 - nw + 1, NULL, 8, NULL, NULL), FM_E_UNSUPPORTED);
+    EXPECT(p_fm_fine_transformer_start(w0, w1, 4, NULL, 49, 64, (const void*)f, o0, o0 + nw - 1, NULL, 8, NULL, NULL), FM_E_UNSUPPORTED);
+    /* separate buffers pass the overlap check: what is left to refuse is the shape */
+    EXPECT(p_fm_fine_transformer_start(w0, w1, 4, NULL, 36, 64, (const void*)f, o0, o1, NULL, 8, NULL, NULL), FM_E_UNSUPPORTED);
+    EXPECT(p_fm_fine_transformer_start(w0, w1, 0, NULL, 49, 64, (const void*)f, w0, w1, NULL, 8, NULL, NULL), FM_OK);   /* M == 0 */
+  }
   /* training surface: argument checks of the dual-softmax entries */
   {
     const float* pr = NULL; const float* pc = NULL; const float* sr = NULL; const float* sc = NULL; int qr = 0, qc = 0;

@@ -468,7 +468,11 @@ extern "C" int fm_dual_softmax_conf_at(const float* feat0, const float* feat1, i
   if (!feat0 || !feat1 || !ofs_r || !ofs_c || !sum_r || !sum_c || !b_ids || !i_ids || !j_ids || !conf) return FM_E_NULL;
   if (!(N > 0 && L > 0 && S > 0) || K < 0 || pitch_r < L || pitch_c < S) return FM_E_SHAPE;
   if (!valid_channels(C) || !(temperature > 0.f)) return FM_E_UNSUPPORTED;
-  const float k2 = kLog2e / ((float)C * temperature);
+  // (the SAME two roundings as the k2 the statistics were formed with - inv_ct * kLog2e in every coarse launch: the
+  // stabilisers are -k2 x_max, and a k2 one ulp away leaves (k2 - k2') x in both exponents: 4.5e-5 of a conf near 1 at
+  // |sim| ~ 160 and C = 36 or 100, where kLog2e / (C T) and kLog2e * (1 / (C T)) round differently)
+  const float inv_ct = 1.0f / ((float)C * temperature);
+  const float k2 = inv_ct * kLog2e;
   hipLaunchKernelGGL(k_conf_at, dim3((K + 15) / 16), dim3(256), 0, (hipStream_t)stream, feat0, feat1, L, S, C, k2, ofs_r,
                      sum_r, pitch_r, ofs_c, sum_c, pitch_c, b_ids, i_ids, j_ids, K, conf, (float*)nullptr);
   return (int)hipGetLastError();

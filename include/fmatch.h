@@ -22,6 +22,9 @@
  *   - Data-dependent conditions discovered on the device (capacity overflow,
  *     candidate-slot overflow, non-finite / out-of-range descriptors) are
  *     reported through the status word next to the match count (fm_read_count).
+ *   - A workspace may hold anything on entry: no call relies on what an earlier call (or nobody) left in it, except where a
+ *     function is documented to read a previous call's results (fm_coarse_cell_maps, fm_coarse_softmax_stats, the resume
+ *     inside fm_coarse_match_auto, fm_coarse_loss_backward).
  */
 #ifndef FMATCH_H_
 #define FMATCH_H_
@@ -141,6 +144,19 @@ int fm_coarse_workspace_bytes_mode(int N, int L, int S, int C, int cand_slots, i
  *   and the entries with conf > 0.1 of a sample with flat similarity together with the denominators that contain them,
  *   come from exact float32 dot products; for that the candidate lists of such a sample go down to min(thr, 0.1) - up
  *   to ~10 candidates per row: pass cand_slots >= 16 on flat data (fm_coarse_match_auto does).
+ *   Shapes: any C % 4 == 0 in [4, 256] (the kernels work on planes zero-padded to 64, 128 or 256 channels; the workspace
+ *   is that of the padded count, sim is divided by the caller's C) and any L, S >= 1; L and S may differ, and one-cell
+ *   images are valid (the softmax over that image's side is then 1).  border_rm follows the reference's slicing
+ *   (:11-28): 0 removes nothing, a border of at least half a grid side of either image removes every cell: M = 0, FM_OK.
+ *   What the common path (mode 0) serves: its screening resolves at most 24 significant entries per 32 x 32 unit of the
+ *   matrix and cand_slots per row / column, which peaked similarity on grids of 9 x 11 cells and more stays far below
+ *   (a match per row: ~10 per unit at 99 cells, 0.2 at 4800).  It reports FM_E_DENSE, like any flat sample, for very
+ *   few channels (C = 4, 12: no peaks) and for SMALL pairs whose significant entries crowd one unit: roughly 25 to 45
+ *   cells per image with a partner for nearly every cell (the first unit then holds more than 24 matches), a one-cell
+ *   image against more than cand_slots cells, and grids of that size with partner-less cells (each owns a significant
+ *   entry, its maximum).  Larger grids with partner-less cells are not covered by this statement.  A call that wants every row's statistics (FM_MODE_STATS, a conf_matrix) of data with
+ *   textureless rows reports FM_E_CANDIDATES unless it runs with FM_MODE_EXACT_SCREENING (fm_coarse_match_auto adds
+ *   that bit to such requests itself).  tests/test_gpu_coarse_edges.py pins the cases of both answers.
  */
 int fm_coarse_match(const float* feat0, const float* feat1, int N, int L, int S, int C,
                     int h0c, int w0c, int h1c, int w1c,
@@ -536,6 +552,9 @@ int fm_epipolar_errors(const float* mkpts0, const float* mkpts1, int kpt_stride,
  *                               (or a conf_matrix request): softmax(sim, dim 2)[b,i,j] = exp2(k2 x + nm_r[b*pitch_r + i]) /
  *                               sum_r[b*pitch_r + i], softmax(sim, dim 1)[b,i,j] = exp2(k2 x + nm_c[b*pitch_c + j]) /
  *                               sum_c[b*pitch_c + j], x = feat0[b,i] . feat1[b,j], k2 = log2(e) / (C temperature)
+ *                               formed in float32 as (1.0f / ((float)C * temperature)) * 1.4426950408889634f - THESE
+ *                               roundings: the stabilisers are -k2 x_max, and log2(e) / (C temperature) in one division is
+ *                               one ulp away at C = 36 or 100, which leaves 4.6e-5 in a conf near 1 at |sim| ~ 160
  *                               (stabiliser and denominator kept apart: folded into one offset the float32 rounding
  *                               would cost 1e-5 of a conf near 1).  Valid while the workspace is.
  *   fm_dual_softmax_conf_at   : conf[e] = softmax(sim,1) * softmax(sim,2) at K entries (b_ids, i_ids, j_ids [dev] int64),

@@ -482,6 +482,42 @@ def kat_cases_round2():
     np.savez_compressed(os.path.join(HERE, "kats_r2.npz"), **cases)
 
 
+def kat_cases_round3():
+    """Known-answer cases below the padded channel counts (kats_r3.npz): 9x11 against 9x11 cells, N = 2, at C = 36 (per-sample
+    scale0 / scale1, non-integer), C = 100 (an exact tie: a matched column of image 1 duplicated bit for bit) and C = 192.
+    Inputs are stored with the reference's outputs, as in kat_cases; they are rounded to float16 BEFORE the reference sees
+    them and stored in that type (half the bytes; the reference ran on their float32 up-casts)."""
+    cases = {}
+    hw_i, hw_c = (72, 88), (9, 11)
+
+    def add(name, f0, f1, scale0=None, scale1=None, extra=None):
+        f0, f1 = f0.astype(np.float16), f1.astype(np.float16)
+        data = ref_coarse(f0.astype(np.float32), f1.astype(np.float32), hw_i, hw_i, hw_c, hw_c, None, scale0, scale1)
+        d = pack_coarse(data)
+        d.update(f0=f0, f1=f1, hw=np.array([*hw_i, *hw_i, *hw_c, *hw_c], np.int64),
+                 cfg=np.array([0.2, 2, 0.1], np.float64))
+        if scale0 is not None:
+            d.update(scale0=np.asarray(scale0, np.float32), scale1=np.asarray(scale1, np.float32))
+        d.update(extra or {})
+        for k, v in d.items():
+            cases[f"{name}/{k}"] = v
+        print(f"kat {name}: M={d['i_ids'].shape[0]}")
+
+    f0, f1 = synth.coarse_descriptors(936, 2, 99, 36, "borderline")
+    add("c36_scale", f0, f1, np.array([[1.25, 0.7], [0.3, 2.6]], np.float32), np.array([[0.9, 1.1], [3.3, 0.45]], np.float32))
+    f0, f1 = synth.coarse_descriptors(1000, 2, 99, 100, "peaky")
+    # the first match of sample 1 (both cells interior) gets a second, bit-identical partner in another interior column
+    base = ref_coarse(f0.astype(np.float16).astype(np.float32), f1.astype(np.float16).astype(np.float32), hw_i, hw_i, hw_c, hw_c)
+    pick = int(np.nonzero(base['b_ids'].numpy() == 1)[0][0])
+    i_t, j_t = int(base['i_ids'][pick]), int(base['j_ids'][pick])
+    j_2 = 49 if j_t != 49 else 50                            # (y 4, x 5) or (y 4, x 6) of the 9x11 grid
+    f1[1, j_2] = f1[1, j_t]
+    add("c100_tie", f0, f1, extra=dict(tie=np.array([1, i_t, j_t, j_2], np.int64)))
+    f0, f1 = synth.coarse_descriptors(1092, 2, 99, 192, "mixed")
+    add("c192", f0, f1)
+    np.savez_compressed(os.path.join(HERE, "kats_r3.npz"), **cases)
+
+
 def masked_coarse_transformer_case(name="tf_masked_coarse"):
     """The reference's LocalFeatureTransformer in its COARSE configuration (d_model 256, 8 heads, linear attention) WITH
     padding masks (transformer.py:78-96, attentions.py:35-40): N = 2, L = 77, S = 130, ['self', 'cross'] x 2, the tails of
@@ -555,6 +591,9 @@ if __name__ == "__main__":
         kat_cases_round2()
         net_tail_case()
         sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "kats_r3":   # only the partial-C known-answer cases
+        kat_cases_round3()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "net_tail":
         net_tail_case()
         sys.exit(0)
@@ -579,6 +618,7 @@ if __name__ == "__main__":
         sys.exit(0)
     kat_cases()
     kat_cases_round2()
+    kat_cases_round3()
     net_tail_case()
     epipolar_case()
     full_case("cfg1_peaky", "cfg1", "peaky")

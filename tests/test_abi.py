@@ -105,6 +105,42 @@ def test_workspace_query_and_argument_checks():
     assert lib.fm_merge_pack_weights(one, 32, one, null) == -3
 
 
+def test_coarse_channel_and_size_rules():
+    """Any C % 4 == 0 in [4, 256] (else FM_E_UNSUPPORTED); the workspace of a C is that of the padded count the kernels are
+    instantiated for (64 / 128 / 256); one-cell images are valid shapes."""
+    lib = _lib.load()
+    n, m = C.c_size_t(0), C.c_size_t(0)
+    one = C.c_void_p(256)        # a non-NULL address that is never dereferenced: every call returns before it launches
+    for c in (0, 2, 6, 258, 260):
+        assert lib.fm_coarse_workspace_bytes(2, 99, 99, c, 8, C.byref(n)) == -3
+        assert lib.fm_coarse_workspace_bytes_mode(2, 99, 99, c, 8, 0, 0, C.byref(n)) == -3
+        assert lib.fm_coarse_workspace_bytes_auto(2, 99, 99, c, 0, C.byref(n)) == -3
+        assert lib.fm_coarse_match_dtype(one, one, 0, 2, 99, 99, c, 9, 11, 9, 11, 0.1, 0.2, 2, 8.0, None, None, one, 1 << 30, 8, 0,
+                                         one, one, one, one, one, one, 64, one, None, None) == -3
+        assert lib.fm_dual_softmax_conf_at(one, one, 2, 99, 99, c, 0.1, one, one, 256, one, one, 128, one, one, one, 5, one,
+                                           None) == -3
+        assert lib.fm_dual_softmax_backward_workspace_bytes(2, 99, 99, c) == 0
+        assert lib.fm_coarse_loss_workspace_bytes(2, 99, 99, c, 5) == 0
+    padded = lambda c: 64 if c <= 64 else (128 if c <= 128 else 256)
+    for c in (4, 12, 36, 60, 64, 68, 100, 124, 128, 132, 192, 252, 256):
+        for slots in (8, 64):
+            assert lib.fm_coarse_workspace_bytes(2, 99, 143, c, slots, C.byref(n)) == 0
+            assert lib.fm_coarse_workspace_bytes(2, 99, 143, padded(c), slots, C.byref(m)) == 0 and n.value == m.value > 0
+            for mode, conf in ((0, 0), (2, 0), (16, 0), (0, 1), (32, 0)):
+                assert lib.fm_coarse_workspace_bytes_mode(2, 99, 143, c, slots, mode, conf, C.byref(n)) == 0
+                assert lib.fm_coarse_workspace_bytes_mode(2, 99, 143, padded(c), slots, mode, conf, C.byref(m)) == 0
+                assert n.value == m.value > 0
+        assert lib.fm_coarse_workspace_bytes_auto(2, 99, 143, c, 0, C.byref(n)) == 0
+        assert lib.fm_coarse_workspace_bytes_auto(2, 99, 143, padded(c), 0, C.byref(m)) == 0 and n.value == m.value > 0
+    for l, s in ((1, 1), (1, 35), (35, 1), (1, 4800)):
+        assert lib.fm_coarse_workspace_bytes_mode(1, l, s, 100, 8, 0, 0, C.byref(n)) == 0 and n.value > 0
+        assert lib.fm_coarse_workspace_bytes(1, l, s, 100, 8, C.byref(m)) == 0 and m.value > n.value
+        assert lib.fm_coarse_workspace_bytes_auto(1, l, s, 100, 0, C.byref(m)) == 0 and m.value > 0
+        assert lib.fm_dual_softmax_backward_workspace_bytes(1, l, s, 100) > 0
+        assert lib.fm_coarse_loss_workspace_bytes(1, l, s, 100, 1) > 0
+    assert lib.fm_coarse_workspace_bytes(1, 0, 35, 100, 8, C.byref(n)) == -2
+
+
 def test_crop_shape_limits():
     """What the window crops refuse, with pointers that are never dereferenced: every call returns before it launches.
     (The accepted side of the NCHW LDS limit - W = 15, Cf = 64, 58 500 bytes - launches: tests/test_gpu_crop_general.py.)"""

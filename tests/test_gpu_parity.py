@@ -479,7 +479,9 @@ def test_round2_kats_against_reference_fixture():
 @pytest.mark.parametrize("hc,wc,c,n,dist", [(7, 9, 64, 3, "peaky"), (15, 17, 128, 2, "borderline"),
                                             (33, 20, 256, 1, "borderline"), (16, 16, 256, 5, "peaky")])
 def test_coarse_ragged_shapes_vs_oracle(hc, wc, c, n, dist):
-    """L not a multiple of the 256-row panel, S not a multiple of the 64-column tile, every C."""
+    """L not a multiple of the 256-row panel, S not a multiple of the 64-column tile, each of the three channel counts
+    the kernels are instantiated for (64, 128, 256).  Channel counts below and between them, and grids down to one
+    cell: tests/test_gpu_coarse_edges.py."""
     f0, f1 = synth.coarse_descriptors(100 + hc, n, hc * wc, c, dist)
     ref = orc.coarse_match(f0, f1, (hc * 8, wc * 8), (hc, wc), (hc, wc), 0.2, 1, 0.1)
     out = _run_coarse(f0, f1, (hc * 8, wc * 8), (hc, wc), (hc, wc), border=1)

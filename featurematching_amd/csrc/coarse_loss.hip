@@ -14,13 +14,16 @@
 //
 //   forward : k_closs_entries (conf, l_pos, l_neg, g_e conf_e at P) -> k_dsm_uv -> k_closs_sweep<.., kSums> on side 0
 //             (sum of l_neg, v, u) -> k_closs_finish (the three numbers of loss_out, fixed order)
-//   backward: k_closs_sweep<.., kGrad> + k_closs_combine per side (the upstream gradient d_loss is read on the device by
-//             the combine) -> k_closs_scale + k_dsm_entries
-// k_closs_sweep is a sibling of k_dsm_bwd<C, kDsmDense> with G computed instead of loaded; that kernel is left as it is
-// (its three instantiations compile to the code they compiled to before - shared through inline functions, its tile
-// loads came out differently - so the tiling is repeated here).
+//   backward: k_closs_sweep<.., kGrad> + k_sweep_combine<true> per side (the upstream gradient d_loss is read on the
+//             device by the combine) -> k_closs_scale + k_dsm_entries
+// k_closs_sweep and k_dsm_bwd are the one tiled sweep of fm_sweep_device.h (LDS layout, tile loader, gradient phase, row /
+// column sums, partial store: there, once) under two policies that differ in three things: how a dot product is summed,
+// where g comes from (computed from conf here, loaded from G or folded into the weights there) and what is kept of an
+// entry (here also the sum of l_neg).  What guards a change to the shared code: the two kernels' arithmetic instructions,
+// registers and LDS, the entry points' bits and a training step's time against the parent build, as recorded in
+// profiles/sweep_shared_parent_vs_change.txt.
 //
-// Two things differ from that kernel because the loss is not linear in conf:
+// Two things differ from k_dsm_bwd because the loss is not linear in conf:
 //   * the clamp's gate [lo <= conf <= hi] decides whether an entry has a gradient at all, and a peaked entry (conf within
 //     1e-6 of 1) is only on the right side of hi when the entry and its two denominators hold the SAME dot product.  The
 //     denominators come from the coarse stage's exact phase, so the sweep takes that phase's summation order (k_conf_at:
@@ -29,9 +32,7 @@
 //     bit the term the sweep added;
 //   * the sum of l_neg mixes terms of 1e-6 with terms of 13.8 (a positive at the upper bound): it is kept in double from
 //     the first addition, so the subtraction above removes the positives' terms exactly.
-#include <utility>
-
-#include "fm_device.h"
+#include "fm_sweep_device.h"
 
 namespace fm {
 
@@ -79,7 +80,10 @@ __device__ __forceinline__ void dot_fold(int l, float s, float (&lv)[4], float& 
 }
 
 // conf = softmax over the rows * softmax over the columns, from the raw dot product and the statistics of its row (ox, isx =
-// 1 / denominator) and its column (oy, isy); the one expression the sweep and the entries kernel share
+// 1 / denominator) and its column (oy, isy).  The entries kernel's copy of the three expressions sweep_tiles
+// (fm_sweep_device.h) forms conf with; the two must stay the same, operation for operation, so that l_neg(c_e) is the term
+// the sweep added.  One function for both was tried: called from sweep_tiles it changes which products of
+// k_dsm_bwd<C, kDsmDense> the compiler packs and contracts, that is, that kernel's roundings.
 __device__ __forceinline__ float conf_from(float x, float k2, float ox, float isx, float oy, float isy, float& ar, float& br) {
   ar = __builtin_amdgcn_exp2f(__builtin_fmaf(x, k2, oy)) * isy;
   br = __builtin_amdgcn_exp2f(__builtin_fmaf(x, k2, ox)) * isx;
@@ -137,69 +141,23 @@ __global__ __launch_bounds__(256) void k_closs_entries(const float* __restrict__
   gc[e] = (conf >= p.lo && conf <= p.hi) ? (-p.wp * qp - p.wn * qn) * conf : 0.f;
 }
 
-// The tiled sweep (k_dsm_bwd's tiling: Xs / Ys [32][C + 4], D transposed with pitch 36; grid (ceil(R / 32), N, Z)).
+// The tiled sweep (fm_sweep_device.h; grid (ceil(R / 32), N, Z)) with g computed from conf.
 //   kSums : per entry gc = g conf with g the dense part of G; row sums into v_out, column sums into u_out (float atomics in
 //           arrival order, as kDsmStats), l_neg(c) into a per-thread sum (double), one partial per workgroup into loss_part in a
 //           fixed order.  Side 0 only.
 //   kGrad : D = 2 gc - A w_y - B w_x accumulated into the rows' gradient, partials per z into `part`.
-template <int C, int MODE, int KIND>
-__global__ __launch_bounds__(256) void k_closs_sweep(const float* __restrict__ X, const float* __restrict__ Y, int R, int T,
-                                                     int c_in, const float* __restrict__ ofs_x, const float* __restrict__ sum_x,
-                                                     int pitch_x, const float* __restrict__ ofs_y,
-                                                     const float* __restrict__ sum_y, int pitch_y,
-                                                     const float* __restrict__ w_x, const float* __restrict__ w_y, float k2,
-                                                     LossParams p, float* __restrict__ part, float* __restrict__ v_out,
-                                                     float* __restrict__ u_out, double* __restrict__ loss_part) {
-  constexpr int P = C + 4;                   // row pitch (floats): 16-byte reads of 16 consecutive rows hit all banks
-  extern __shared__ __attribute__((aligned(16))) float sm[];
-  float* Xs = sm;                            // [32][P]
-  float* Ys = sm + 32 * P;                   // [32][P]
-  float* Dt = sm + 64 * P;                   // [32 (l)][36]: D transposed
-  const int tid = threadIdx.x, b = blockIdx.y, k0 = blockIdx.x * 32;
-  const int ntiles = (T + 31) / 32, Z = gridDim.z, z = blockIdx.z;
-  const int t_lo = (int)((long)ntiles * z / Z), t_hi = (int)((long)ntiles * (z + 1) / Z);
-  const float* Xb = X + (long)b * R * c_in;
-  const float* Yb = Y + (long)b * T * c_in;
-  const int vpr = c_in >> 2;
-  auto load_tile = [&](float* dst, const float* src, int row0, int rows) {
-#pragma unroll
-    for (int q = 0; q < 32 * (C / 4) / 256; ++q) {
-      const int idx = q * 256 + tid, row = idx / (C / 4), v4 = idx % (C / 4);
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (row0 + row < rows && v4 < vpr) v = reinterpret_cast<const float4*>(src + (long)(row0 + row) * c_in)[v4];
-      *reinterpret_cast<float4*>(&dst[row * P + 4 * v4]) = v;
-    }
-  };
-  load_tile(Xs, Xb, k0, R);
-  const int tx = tid & 31, ty = tid >> 5;                 // similarity phase: column tx, rows ty + 8 q
-  float ox[4], wx[4], isx[4], vacc[4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int k = k0 + ty + 8 * q;
-    ox[q] = k < R ? ofs_x[(long)b * pitch_x + k] : 0.f;
-    isx[q] = k < R ? 1.0f / sum_x[(long)b * pitch_x + k] : 0.f;
-    wx[q] = (MODE == kGrad && k < R) ? w_x[(long)b * R + k] : 0.f;
-    vacc[q] = 0.f;
-  }
-  double lacc = 0.0;
-  const int c4 = tid & 63, rg = tid >> 6;                 // gradient phase: channels 4 c4 .. + 3, rows 8 rg .. + 7
-  float acc[8][4];
-#pragma unroll
-  for (int r = 0; r < 8; ++r)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) acc[r][e] = 0.f;
-  for (int t = t_lo; t < t_hi; ++t) {
-    const int l0 = t * 32;
-    __syncthreads();                                      // the previous tile's readers are done with Ys and Dt
-    load_tile(Ys, Yb, l0, T);
-    const int l = l0 + tx;
-    const float oy = l < T ? ofs_y[(long)b * pitch_y + l] : 0.f;
-    const float isy = l < T ? 1.0f / sum_y[(long)b * pitch_y + l] : 0.f;
-    const float wy = (MODE == kGrad && l < T) ? w_y[(long)b * T + l] : 0.f;
-    __syncthreads();
-    float sv[4] = {0.f, 0.f, 0.f, 0.f}, lv[4][4];
+template <int KIND>
+struct ClossSweepPolicy {
+  const LossParams& p;
+  double* __restrict__ loss_part;
+  double lacc;
+  float lv[4][4];            // dot_fold's counters (kept here, not in dots: per call they would be set up per tile)
+  // the exact phase's order: partial sum pl over the float4 groups pl, pl + 16, ... (see above), folded by dot_fold
+  template <int C>
+  __device__ __forceinline__ void dots(const float* Xs, const float* Ys, int tx, int ty, float (&sv)[4]) {
+    constexpr int P = sweep_pitch(C);
 #pragma unroll 1                                          // (unrolled, the loads of all 16 partial sums are hoisted: spills)
-    for (int pl = 0; pl < 16; ++pl) {                     // partial sum pl: the float4 groups pl, pl + 16, ... (see above)
+    for (int pl = 0; pl < 16; ++pl) {
       float sl[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int c = 4 * pl; c < C; c += 64) {
@@ -216,78 +174,36 @@ __global__ __launch_bounds__(256) void k_closs_sweep(const float* __restrict__ X
 #pragma unroll
       for (int q = 0; q < 4; ++q) dot_fold(pl, sl[q], lv[q], sv[q]);
     }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const bool ok = l < T && k0 + ty + 8 * q < R;
-      float ar, br, ln;
-      // (which image owns the rows does not matter to conf: the two factors commute)
-      const float conf = conf_from(sv[q], k2, ox[q], isx[q], oy, isy, ar, br);
-      const float gc = ok ? dense_gc<KIND>(conf, p, ln) : 0.f;
-      if (MODE == kSums) {
-        vacc[q] += gc;
-        lacc += ok ? (double)ln : 0.0;
-        Dt[tx * 36 + ty + 8 * q] = gc;
-      } else {
-        Dt[tx * 36 + ty + 8 * q] = ok ? 2.0f * gc - ar * wy - br * wx[q] : 0.f;
-      }
-    }
-    __syncthreads();
-    if (MODE == kSums) {
-      // column sums of this tile's g conf: 32 threads add the 32 owner rows of their column in a fixed order
-      if (tid < 32 && l0 + tid < T) {
-        float cs = 0.f;
-#pragma unroll 8
-        for (int rr = 0; rr < 32; ++rr) cs += Dt[tid * 36 + rr];
-        atomicAdd(&u_out[(long)b * T + l0 + tid], cs);
-      }
-      continue;
-    }
-    if (4 * c4 < C) {
-#pragma unroll 4
-      for (int ll = 0; ll < 32; ++ll) {
-        const float4 y = *reinterpret_cast<const float4*>(&Ys[ll * P + 4 * c4]);
-        const float4 d0 = *reinterpret_cast<const float4*>(&Dt[ll * 36 + 8 * rg]);
-        const float4 d1 = *reinterpret_cast<const float4*>(&Dt[ll * 36 + 8 * rg + 4]);
-        const float d[8] = {d0.x, d0.y, d0.z, d0.w, d1.x, d1.y, d1.z, d1.w};
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {
-          acc[r][0] = __builtin_fmaf(d[r], y.x, acc[r][0]);
-          acc[r][1] = __builtin_fmaf(d[r], y.y, acc[r][1]);
-          acc[r][2] = __builtin_fmaf(d[r], y.z, acc[r][2]);
-          acc[r][3] = __builtin_fmaf(d[r], y.w, acc[r][3]);
-        }
-      }
-    }
   }
-  if (MODE == kSums) {
-    // row sums: the 32 columns a row's partial sums sit in are the 32 lanes of a half wave
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      float t = vacc[q];
-#pragma unroll
-      for (int m = 16; m >= 1; m >>= 1) t += __shfl_xor(t, m);
-      const int k = k0 + ty + 8 * q;
-      if (tx == 0 && k < R) atomicAdd(&v_out[(long)b * R + k], t);
-    }
-    // the workgroup's sum of l_neg: butterfly within each wave, then the four waves in index order - the same bits
-    // every run
+  __device__ __forceinline__ void fetch_g(float (&)[4], int, int, int, int) const {}
+  __device__ __forceinline__ void g_from_lds(float (&)[4]) const {}
+  __device__ __forceinline__ float gc(float, float conf, float& ln) const { return dense_gc<KIND>(conf, p, ln); }
+  __device__ __forceinline__ void keep(bool ok, float ln) { lacc += ok ? (double)ln : 0.0; }
+  // the workgroup's sum of l_neg: butterfly within each wave, then the four waves in index order - the same bits
+  // every run
+  __device__ __forceinline__ void sums_done(float* Dt, long part_index) {
+    const int tid = threadIdx.x;
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) lacc += __shfl_xor(lacc, m);
     __syncthreads();                                      // the last tile's column sums are done with Dt
     double* red = reinterpret_cast<double*>(Dt);
     if ((tid & 63) == 0) red[tid >> 6] = lacc;
     __syncthreads();
-    if (tid == 0) loss_part[((long)z * gridDim.y + b) * gridDim.x + blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
-    return;
+    if (tid == 0) loss_part[part_index] = ((red[0] + red[1]) + red[2]) + red[3];
   }
-  if (c4 < vpr) {
-    float* out = part + (((long)z * gridDim.y + b) * R) * c_in;
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-      const int k = k0 + 8 * rg + r;
-      if (k < R) reinterpret_cast<float4*>(out + (long)k * c_in)[c4] = make_float4(acc[r][0], acc[r][1], acc[r][2], acc[r][3]);
-    }
-  }
+};
+
+template <int C, int MODE, int KIND>
+__global__ __launch_bounds__(256) void k_closs_sweep(const float* __restrict__ X, const float* __restrict__ Y, int R, int T,
+                                                     int c_in, const float* __restrict__ ofs_x, const float* __restrict__ sum_x,
+                                                     int pitch_x, const float* __restrict__ ofs_y,
+                                                     const float* __restrict__ sum_y, int pitch_y,
+                                                     const float* __restrict__ w_x, const float* __restrict__ w_y, float k2,
+                                                     LossParams p, float* __restrict__ part, float* __restrict__ v_out,
+                                                     float* __restrict__ u_out, double* __restrict__ loss_part) {
+  ClossSweepPolicy<KIND> pol = {p, loss_part, 0.0, {}};
+  sweep_tiles<C, MODE == kSums ? kDsmStats : kDsmDense>(X, Y, R, T, c_in, ofs_x, sum_x, pitch_x, ofs_y, sum_y, pitch_y, w_x,
+                                                          w_y, k2, part, v_out, u_out, pol);
 }
 
 // sum of n numbers in double, in an order that depends on n alone: thread t adds elements t, t + 256, ..., then a tree
@@ -321,20 +237,6 @@ __global__ __launch_bounds__(256) void k_closs_finish(const double* __restrict__
     loss_out[1] = (float)pos_mean;
     loss_out[2] = (float)neg_mean;
   }
-}
-
-// out = scale * d_loss * sum_z part[z]   (fixed order; d_loss [1] on the device: the upstream gradient of the scalar)
-__global__ __launch_bounds__(256) void k_closs_combine(const float4* __restrict__ part, long n4, int Z, float scale,
-                                                       const float* __restrict__ d_loss, float4* __restrict__ out) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n4) return;
-  const float f = scale * d_loss[0];
-  float4 s = part[i];
-  for (int z = 1; z < Z; ++z) {
-    const float4 v = part[(long)z * n4 + i];
-    s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-  }
-  out[i] = make_float4(s.x * f, s.y * f, s.z * f, s.w * f);
 }
 
 __global__ __launch_bounds__(256) void k_closs_scale(const float* __restrict__ gc, int K, const float* __restrict__ d_loss,
@@ -388,14 +290,10 @@ static int closs_begin(const float* feat0, const float* feat1, int N, int L, int
   c->w = closs_layout(N, L, S, C, K);
   if (workspace_bytes < c->w.total || ((uintptr_t)workspace & 255)) return FM_E_WORKSPACE;
   c->s = s;
-  if (forward) {
-    const int r = dsm_begin(feat0, feat1, N, L, S, C, temperature, s, workspace, workspace_bytes, st, &c->p);
-    if (r != FM_OK) return r;
-  } else {                                    // v and u are the forward call's
-    const float inv_ct = 1.0f / ((float)C * temperature);
-    c->p = {feat0, feat1, N, L, S, C, kLog2e * inv_ct, inv_ct, span_ptr<float>(workspace, c->w.dsm.v),
-            span_ptr<float>(workspace, c->w.dsm.u), span_ptr<float>(workspace, c->w.dsm.part)};
-  }
+  // (the backward's v and u are the forward call's)
+  const int r = forward ? dsm_begin(feat0, feat1, N, L, S, C, temperature, s, workspace, workspace_bytes, st, &c->p)
+                        : dsm_carve(feat0, feat1, N, L, S, C, temperature, s, workspace, workspace_bytes, &c->p);
+  if (r != FM_OK) return r;
   // loss.py:37-42: without a positive, entry (0, 0, 0) stands in with weight 0 - in pos_mask only: neg_mask was taken
   // before, so the entry stays among the negatives; without a negative the negatives' weight is 0
   c->stand_in = K == 0;
@@ -423,43 +321,30 @@ static hipError_t with_kind(int kind, F&& f) {
 // the tiled sweep of one side (0: owner = image 0, 1: owner = image 1), as dsm_sweep in dsm_grad.hip
 static int closs_sweep(int mode, int side, const ClossCall& c, void* workspace, const float* d_loss, float* d_out,
                        hipStream_t st) {
-  DsmProblem o = c.p;
-  DsmStats t = c.s;
-  if (side) {
-    std::swap(o.feat0, o.feat1); std::swap(o.L, o.S); std::swap(o.v, o.u);
-    t = {c.s.ofs_c, c.s.sum_c, c.s.pitch_c, c.s.ofs_r, c.s.sum_r, c.s.pitch_r};
-  }
-  const int Z = dsm_zsplit(c.p.N, o.L);
-  const dim3 grid((o.L + 31) / 32, c.p.N, Z);
+  const DsmSide o = dsm_side(c.p, c.s, side);
+  const dim3 grid = dsm_sweep_grid(o);
   double* loss_part = span_ptr<double>(workspace, c.w.loss_part);
   auto launch = [&](auto cc, auto mm, auto kk) -> hipError_t {
     constexpr int CC = decltype(cc)::value, MM = decltype(mm)::value, KK = decltype(kk)::value;
-    constexpr int smem = (64 * (CC + 4) + 32 * 36) * 4;
+    constexpr int smem = sweep_lds_bytes(CC, false);
     static unsigned long long lds_set = 0;      // (one per instantiation of this lambda, that is, per kernel)
     const hipError_t e = ensure_dynamic_lds(&k_closs_sweep<CC, MM, KK>, smem, &lds_set);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_closs_sweep<CC, MM, KK>), grid, dim3(256), smem, st, o.feat0, o.feat1, o.L, o.S, c.p.C, t.ofs_r,
-                       t.sum_r, t.pitch_r, t.ofs_c, t.sum_c, t.pitch_c, o.v, o.u, c.p.k2, c.lp, c.p.part, c.p.v, c.p.u,
-                       loss_part);
+    hipLaunchKernelGGL((k_closs_sweep<CC, MM, KK>), grid, dim3(256), smem, st, o.p.feat0, o.p.feat1, o.p.L, o.p.S, c.p.C,
+                       o.s.ofs_r, o.s.sum_r, o.s.pitch_r, o.s.ofs_c, o.s.sum_c, o.s.pitch_c, o.p.v, o.p.u, c.p.k2, c.lp,
+                       c.p.part, c.p.v, c.p.u, loss_part);
     return hipSuccess;
   };
-  auto with_mode = [&](auto cc) {
+  const hipError_t e = with_padded_channels(c.p.C, [&](auto cc) {
     return with_kind(c.kind, [&](auto kk) {
       return mode == kSums ? launch(cc, int_c<kSums>{}, kk) : launch(cc, int_c<kGrad>{}, kk);
     });
-  };
-  const int Cp = padded_channels(c.p.C);
-  const hipError_t e = Cp == 64 ? with_mode(int_c<64>{}) : Cp == 128 ? with_mode(int_c<128>{}) : with_mode(int_c<256>{});
+  });
   if (e != hipSuccess) return (int)e;
-  if (mode == kSums) {
-    hipLaunchKernelGGL(k_closs_finish, dim3(1), dim3(256), 0, st, (const double*)loss_part, (long)grid.x * grid.y * grid.z,
-                       span_ptr<const float>(workspace, c.w.l_pos), span_ptr<const float>(workspace, c.w.l_neg), c.w.Ke,
-                       c.inv_pos, c.inv_neg, c.pos_weight, c.neg_weight, c.stand_in ? 0 : 1, d_out);
-  } else {
-    const long n4 = (long)c.p.N * o.L * c.p.C / 4;
-    hipLaunchKernelGGL(k_closs_combine, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, (const float4*)c.p.part, n4, Z,
-                       c.p.inv_ct, d_loss, (float4*)d_out);
-  }
+  if (mode != kSums) return (int)launch_sweep_combine(o, grid.z, d_loss, d_out, st);
+  hipLaunchKernelGGL(k_closs_finish, dim3(1), dim3(256), 0, st, (const double*)loss_part, (long)grid.x * grid.y * grid.z,
+                     span_ptr<const float>(workspace, c.w.l_pos), span_ptr<const float>(workspace, c.w.l_neg), c.w.Ke,
+                     c.inv_pos, c.inv_neg, c.pos_weight, c.neg_weight, c.stand_in ? 0 : 1, d_out);
   return (int)hipGetLastError();
 }
 

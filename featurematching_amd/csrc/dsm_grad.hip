@@ -17,9 +17,7 @@
 // gradient - the dense matrix never exists.  The supervised entries' own term 2 g c is K rows: a third, tiny kernel.
 // float32 vector arithmetic on purpose: a training-only path whose bar is the agreement with float64 autograd
 // (tests), not the matrix cores.
-#include <utility>
-
-#include "fm_device.h"
+#include "fm_sweep_device.h"
 
 namespace fm {
 
@@ -84,10 +82,10 @@ __global__ __launch_bounds__(256) void k_dsm_uv(const int64_t* __restrict__ b_id
 
 // dX[k, :] = sum_l D_kl Y[l, :],  D_kl = -(exp2(k2 x_kl + nm_y[l]) w_y[l] / sum_y[l] + exp2(k2 x_kl + nm_x[k]) w_x[k] / sum_x[k]),
 // x = X_k . Y_l
-// grid (ceil(R / 32), N, Z): workgroup = 32 owner rows x the z-th share of the other image's 32-descriptor tiles.
-// C = padded channel count (64 / 128 / 256), c_in <= C the rows' real length.  Partial gradients (one per z) go to
-// part[z][b][row][c_in]; k_dsm_combine adds them up and scales.
-// MODE (round 5: a DENSE dL/dconf = G [N, L, S], what the reference's loss over all negatives hands back - losses/loss.py:44-50,
+// The tiled sweep of fm_sweep_device.h (grid, LDS, phases: there) with the dot products summed in channel order and G,
+// where there is one, loaded.  Partial gradients (one per z) go to part[z][b][row][c_in]; k_sweep_combine adds them up
+// and scales.
+// MODE (a DENSE dL/dconf = G [N, L, S], what the reference's loss over all negatives hands back - losses/loss.py:44-50,
 // 62-65 - without any [N, L, S] temporary):
 //   kDsmSparse : as above (G lives in w_x / w_y and the entries' own kernel).
 //   kDsmStats  : v_k = sum_l G_kl conf_kl and u_l = sum_k G_kl conf_kl with conf recomputed tile by tile from exact float32
@@ -95,90 +93,19 @@ __global__ __launch_bounds__(256) void k_dsm_uv(const int64_t* __restrict__ b_id
 //                v takes one add per z slice (<= 4), a COLUMN's u one add per 32-row tile of the owner image (150 at
 //                640x480) in arrival order - the dense backward's gradients are therefore reproducible to float32
 //                rounding of those sums (~1e-7 relative), not bit for bit; every other reduction of this file is
-//                order-fixed (k_fix_sums, k_dsm_combine).
+//                order-fixed (k_fix_sums, k_sweep_combine).
 //   kDsmDense  : D_kl = 2 G_kl conf_kl - A_kl u_l - B_kl v_k, the whole of dL/dsim, accumulated into the rows' gradient.
 // G is read through a transposing LDS tile when the owner image is image 1 (g_t: element (owner row, other row) lives at
 // G[other][owner]): both sides read 128-byte row segments of G.  G is read three times in all (92 MB per 640x480 pair
 // each), nothing of its size is written.
-enum { kDsmSparse = 0, kDsmStats = 1, kDsmDense = 2 };
-template <int C, int MODE>
-__global__ __launch_bounds__(256) void k_dsm_bwd(const float* __restrict__ X, const float* __restrict__ Y, int R, int T, int c_in,
-                                                 const float* __restrict__ ofs_x, const float* __restrict__ sum_x, int pitch_x,
-                                                 const float* __restrict__ ofs_y, const float* __restrict__ sum_y,
-                                                 int pitch_y, const float* __restrict__ w_x, const float* __restrict__ w_y,
-                                                 float k2, float* __restrict__ part, const float* __restrict__ G, int g_t,
-                                                 float* __restrict__ v_out, float* __restrict__ u_out) {
-  constexpr int P = C + 4;                   // row pitch (floats): 16-byte reads of 16 consecutive rows hit all banks
-  extern __shared__ __attribute__((aligned(16))) float sm[];
-  float* Xs = sm;                            // [32][P]
-  float* Ys = sm + 32 * P;                   // [32][P]
-  float* Dt = sm + 64 * P;                   // [32 (l)][36]: D transposed
-  const int tid = threadIdx.x, b = blockIdx.y, k0 = blockIdx.x * 32;
-  const int ntiles = (T + 31) / 32, Z = gridDim.z, z = blockIdx.z;
-  const int t_lo = (int)((long)ntiles * z / Z), t_hi = (int)((long)ntiles * (z + 1) / Z);
-  const float* Xb = X + (long)b * R * c_in;
-  const float* Yb = Y + (long)b * T * c_in;
-  const int vpr = c_in >> 2;
-  auto load_tile = [&](float* dst, const float* src, int row0, int rows) {
-#pragma unroll
-    for (int p = 0; p < 32 * (C / 4) / 256; ++p) {
-      const int idx = p * 256 + tid, row = idx / (C / 4), v4 = idx % (C / 4);
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (row0 + row < rows && v4 < vpr) v = reinterpret_cast<const float4*>(src + (long)(row0 + row) * c_in)[v4];
-      *reinterpret_cast<float4*>(&dst[row * P + 4 * v4]) = v;
-    }
-  };
-  load_tile(Xs, Xb, k0, R);
-  const int tx = tid & 31, ty = tid >> 5;                 // similarity phase: column tx, rows ty + 8 q
-  float ox[4], wx[4], isx[4], vacc[4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int k = k0 + ty + 8 * q;
-    ox[q] = k < R ? ofs_x[(long)b * pitch_x + k] : 0.f;
-    isx[q] = k < R ? 1.0f / sum_x[(long)b * pitch_x + k] : 0.f;
-    if (MODE == kDsmSparse) wx[q] = k < R ? w_x[(long)b * R + k] / sum_x[(long)b * pitch_x + k] : 0.f;
-    else wx[q] = (MODE == kDsmDense && k < R) ? w_x[(long)b * R + k] : 0.f;
-    vacc[q] = 0.f;
-  }
-  float* Gs = Dt + 32 * 36;                  // [32][33]: the tile of G (MODE != kDsmSparse)
-  const float* Gb = G ? G + (long)b * (g_t ? (long)T * R : (long)R * T) : nullptr;
-  const int c4 = tid & 63, rg = tid >> 6;                 // gradient phase: channels 4 c4 .. + 3, rows 8 rg .. + 7
-  float acc[8][4];
-#pragma unroll
-  for (int r = 0; r < 8; ++r)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) acc[r][e] = 0.f;
-  for (int t = t_lo; t < t_hi; ++t) {
-    const int l0 = t * 32;
-    __syncthreads();                                      // the previous tile's readers are done with Ys and Dt
-    load_tile(Ys, Yb, l0, T);
-    const int l = l0 + tx;
-    const float oy = l < T ? ofs_y[(long)b * pitch_y + l] : 0.f;
-    const float isy = l < T ? 1.0f / sum_y[(long)b * pitch_y + l] : 0.f;
-    float wy;
-    if (MODE == kDsmSparse) wy = l < T ? w_y[(long)b * T + l] / sum_y[(long)b * pitch_y + l] : 0.f;
-    else wy = (MODE == kDsmDense && l < T) ? w_y[(long)b * T + l] : 0.f;
-    float gq[4] = {0.f, 0.f, 0.f, 0.f};
-    if (MODE != kDsmSparse) {
-      // 128-byte row segments of G either way: g_t = 0 -> G[owner k0 + ty + 8q][other l0 + tx] straight into registers;
-      // g_t = 1 -> G[other l0 + ty + 8q][owner k0 + tx] into the LDS tile, read back transposed behind the barrier
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        if (!g_t) {
-          const int k = k0 + ty + 8 * q;
-          gq[q] = (k < R && l < T) ? Gb[(long)k * T + l] : 0.f;
-        } else {
-          const int lo = l0 + ty + 8 * q, ko = k0 + tx;
-          Gs[(ty + 8 * q) * 33 + tx] = (lo < T && ko < R) ? Gb[(long)lo * R + ko] : 0.f;
-        }
-      }
-    }
-    __syncthreads();
-    if (MODE != kDsmSparse && g_t) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) gq[q] = Gs[tx * 33 + ty + 8 * q];
-    }
-    float sv[4] = {0.f, 0.f, 0.f, 0.f};
+struct DsmSweepPolicy {
+  const float* Gb;           // this sample's G
+  int g_t;
+  float* Gs;                 // [32][33]: the tile of G
+  // exact products, fused multiply-adds in channel order
+  template <int C>
+  static __device__ __forceinline__ void dots(const float* Xs, const float* Ys, int tx, int ty, float (&sv)[4]) {
+    constexpr int P = sweep_pitch(C);
 #pragma unroll 4
     for (int c = 0; c < C; c += 4) {
       const float4 y = *reinterpret_cast<const float4*>(&Ys[tx * P + c]);
@@ -191,82 +118,60 @@ __global__ __launch_bounds__(256) void k_dsm_bwd(const float* __restrict__ X, co
         sv[q] = __builtin_fmaf(x.w, y.w, sv[q]);
       }
     }
+  }
+  // 128-byte row segments of G either way: g_t = 0 -> G[owner k0 + ty + 8q][other l0 + tx] straight into registers;
+  // g_t = 1 -> G[other l0 + ty + 8q][owner k0 + tx] into the LDS tile, read back transposed behind the barrier
+  __device__ __forceinline__ void fetch_g(float (&gq)[4], int k0, int l0, int R, int T) const {
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5, l = l0 + tx;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      const bool ok = l < T && k0 + ty + 8 * q < R;
-      if (MODE == kDsmSparse) {
-        const float a = __builtin_amdgcn_exp2f(__builtin_fmaf(sv[q], k2, oy)) * wy;
-        const float bt = __builtin_amdgcn_exp2f(__builtin_fmaf(sv[q], k2, ox[q])) * wx[q];
-        Dt[tx * 36 + ty + 8 * q] = ok ? -(a + bt) : 0.f;
+      if (!g_t) {
+        const int k = k0 + ty + 8 * q;
+        gq[q] = (k < R && l < T) ? Gb[(long)k * T + l] : 0.f;
       } else {
-        const float ar = __builtin_amdgcn_exp2f(__builtin_fmaf(sv[q], k2, oy)) * isy;       // softmax over the owner's rows
-        const float br = __builtin_amdgcn_exp2f(__builtin_fmaf(sv[q], k2, ox[q])) * isx[q]; // ... over the other image's
-        const float gc = ok ? gq[q] * (ar * br) : 0.f;
-        if (MODE == kDsmStats) { vacc[q] += gc; Dt[tx * 36 + ty + 8 * q] = gc; }
-        else Dt[tx * 36 + ty + 8 * q] = ok ? 2.0f * gc - ar * wy - br * wx[q] : 0.f;
-      }
-    }
-    __syncthreads();
-    if (MODE == kDsmStats) {
-      // column sums of this tile's G conf: 32 threads add the 32 owner rows of their column in a fixed order
-      if (tid < 32 && l0 + tid < T) {
-        float cs = 0.f;
-#pragma unroll 8
-        for (int rr = 0; rr < 32; ++rr) cs += Dt[tid * 36 + rr];
-        atomicAdd(&u_out[(long)b * T + l0 + tid], cs);
-      }
-      continue;
-    }
-    if (4 * c4 < C) {
-#pragma unroll 4
-      for (int ll = 0; ll < 32; ++ll) {
-        const float4 y = *reinterpret_cast<const float4*>(&Ys[ll * P + 4 * c4]);
-        const float4 d0 = *reinterpret_cast<const float4*>(&Dt[ll * 36 + 8 * rg]);
-        const float4 d1 = *reinterpret_cast<const float4*>(&Dt[ll * 36 + 8 * rg + 4]);
-        const float d[8] = {d0.x, d0.y, d0.z, d0.w, d1.x, d1.y, d1.z, d1.w};
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {
-          acc[r][0] = __builtin_fmaf(d[r], y.x, acc[r][0]);
-          acc[r][1] = __builtin_fmaf(d[r], y.y, acc[r][1]);
-          acc[r][2] = __builtin_fmaf(d[r], y.z, acc[r][2]);
-          acc[r][3] = __builtin_fmaf(d[r], y.w, acc[r][3]);
-        }
+        const int lo = l0 + ty + 8 * q, ko = k0 + tx;
+        Gs[(ty + 8 * q) * kSweepGsPitch + tx] = (lo < T && ko < R) ? Gb[(long)lo * R + ko] : 0.f;
       }
     }
   }
-  if (MODE == kDsmStats) {
-    // row sums: the 32 columns a row's partial sums sit in are the 32 lanes of a half wave
+  __device__ __forceinline__ void g_from_lds(float (&gq)[4]) const {
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    if (g_t) {
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      float t = vacc[q];
-#pragma unroll
-      for (int m = 16; m >= 1; m >>= 1) t += __shfl_xor(t, m);
-      const int k = k0 + ty + 8 * q;
-      if (tx == 0 && k < R) atomicAdd(&v_out[(long)b * R + k], t);
-    }
-    return;
-  }
-  if (c4 < vpr) {
-    float* out = part + (((long)z * gridDim.y + b) * R) * c_in;
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-      const int k = k0 + 8 * rg + r;
-      if (k < R) reinterpret_cast<float4*>(out + (long)k * c_in)[c4] = make_float4(acc[r][0], acc[r][1], acc[r][2], acc[r][3]);
+      for (int q = 0; q < 4; ++q) gq[q] = Gs[tx * kSweepGsPitch + ty + 8 * q];
     }
   }
+  __device__ __forceinline__ float gc(float g, float conf, float&) const { return g * conf; }
+  __device__ __forceinline__ void keep(bool, float) const {}
+  __device__ __forceinline__ void sums_done(float*, long) const {}
+};
+
+template <int C, int MODE>
+__global__ __launch_bounds__(256) void k_dsm_bwd(const float* __restrict__ X, const float* __restrict__ Y, int R, int T, int c_in,
+                                                 const float* __restrict__ ofs_x, const float* __restrict__ sum_x, int pitch_x,
+                                                 const float* __restrict__ ofs_y, const float* __restrict__ sum_y,
+                                                 int pitch_y, const float* __restrict__ w_x, const float* __restrict__ w_y,
+                                                 float k2, float* __restrict__ part, const float* __restrict__ G, int g_t,
+                                                 float* __restrict__ v_out, float* __restrict__ u_out) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  DsmSweepPolicy pol = {G ? G + (long)blockIdx.y * (g_t ? (long)T * R : (long)R * T) : nullptr, g_t, sm + sweep_gs_at(C)};
+  sweep_tiles<C, MODE>(X, Y, R, T, c_in, ofs_x, sum_x, pitch_x, ofs_y, sum_y, pitch_y, w_x, w_y, k2, part, v_out, u_out, pol);
 }
 
-// out = scale * sum_z part[z]   (fixed order)
-__global__ __launch_bounds__(256) void k_dsm_combine(const float4* __restrict__ part, long n4, int Z, float scale,
-                                                     float4* __restrict__ out) {
+// out = scale * sum_z part[z]   (fixed order), D_LOSS: scale * d_loss * sum_z part[z] with d_loss [1] on the device, the
+// upstream gradient of the coarse loss's scalar
+template <bool D_LOSS>
+__global__ __launch_bounds__(256) void k_sweep_combine(const float4* __restrict__ part, long n4, int Z, float scale,
+                                                       const float* __restrict__ d_loss, float4* __restrict__ out) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= n4) return;
+  const float f = D_LOSS ? scale * d_loss[0] : scale;
   float4 s = part[i];
   for (int z = 1; z < Z; ++z) {
     const float4 v = part[(long)z * n4 + i];
     s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
   }
-  out[i] = make_float4(s.x * scale, s.y * scale, s.z * scale, s.w * scale);
+  out[i] = make_float4(s.x * f, s.y * f, s.z * f, s.w * f);
 }
 
 // the supervised entries' own term: d0[b, i, :] += 2 g c / (C T) f1[b, j, :],  d1[b, j, :] += 2 g c / (C T) f0[b, i, :]
@@ -482,9 +387,9 @@ extern "C" size_t fm_dual_softmax_backward_workspace_bytes(int N, int L, int S, 
   return N > 0 && L > 0 && S > 0 && valid_channels(C) ? dsm_bwd_layout(N, L, S, C).total : 0;
 }
 
-// what both backward entry points do after their NULL checks: the remaining argument checks, then *p with v and u zeroed
-int fm::dsm_begin(const float* feat0, const float* feat1, int N, int L, int S, int C, float temperature, const DsmStats& s,
-                     void* workspace, size_t workspace_bytes, hipStream_t st, DsmProblem* p) {
+// what every backward entry point does after its NULL checks: the remaining argument checks and the carved workspace ...
+int fm::dsm_carve(const float* feat0, const float* feat1, int N, int L, int S, int C, float temperature, const DsmStats& s,
+                  void* workspace, size_t workspace_bytes, DsmProblem* p) {
   if (!(N > 0 && L > 0 && S > 0) || s.pitch_r < L || s.pitch_c < S) return FM_E_SHAPE;
   if (!valid_channels(C) || !(temperature > 0.f)) return FM_E_UNSUPPORTED;
   const DsmBwdWs w = dsm_bwd_layout(N, L, S, C);
@@ -492,40 +397,45 @@ int fm::dsm_begin(const float* feat0, const float* feat1, int N, int L, int S, i
   const float inv_ct = 1.0f / ((float)C * temperature);
   *p = {feat0, feat1, N, L, S, C, kLog2e * inv_ct, inv_ct, span_ptr<float>(workspace, w.v), span_ptr<float>(workspace, w.u),
         span_ptr<float>(workspace, w.part)};
+  return FM_OK;
+}
+
+// ... and, for a call that forms v and u itself, the two zeroed
+int fm::dsm_begin(const float* feat0, const float* feat1, int N, int L, int S, int C, float temperature, const DsmStats& s,
+                  void* workspace, size_t workspace_bytes, hipStream_t st, DsmProblem* p) {
+  const int r = dsm_carve(feat0, feat1, N, L, S, C, temperature, s, workspace, workspace_bytes, p);
+  if (r != FM_OK) return r;
+  const DsmBwdWs w = dsm_bwd_layout(N, L, S, C);
   return (int)hipMemsetAsync(span_ptr<char>(workspace, w.sums), 0, w.sums.bytes, st);
+}
+
+hipError_t fm::launch_sweep_combine(const DsmSide& o, int Z, const float* d_loss, float* d_out, hipStream_t st) {
+  const long n4 = (long)o.p.N * o.p.L * o.p.C / 4;
+  const dim3 grid((unsigned)((n4 + 255) / 256));
+  auto* combine = d_loss ? k_sweep_combine<true> : k_sweep_combine<false>;
+  hipLaunchKernelGGL(combine, grid, dim3(256), 0, st, (const float4*)o.p.part, n4, Z, o.p.inv_ct, d_loss, (float4*)d_out);
+  return hipGetLastError();
 }
 
 // the tiled sweep of one side (0: owner = image 0, 1: owner = image 1) in one of its three modes + the combine of its partials
 static int dsm_sweep(int mode, int side, const DsmProblem& p, const DsmStats& s, const float* G, float* d_out, hipStream_t st) {
-  DsmProblem o = p;          // as the owner sees it: its own descriptors, length, statistics and sums come first
-  DsmStats t = s;
-  if (side) {
-    std::swap(o.feat0, o.feat1); std::swap(o.L, o.S); std::swap(o.v, o.u);
-    t = {s.ofs_c, s.sum_c, s.pitch_c, s.ofs_r, s.sum_r, s.pitch_r};
-  }
-  const int Z = dsm_zsplit(p.N, o.L);
-  const dim3 grid((o.L + 31) / 32, p.N, Z);
+  const DsmSide o = dsm_side(p, s, side);
+  const dim3 grid = dsm_sweep_grid(o);
   auto launch = [&](auto cc, auto mm) -> hipError_t {
-    constexpr int CC = decltype(cc)::value, MM = decltype(mm)::value, smem = (64 * (CC + 4) + 32 * 36 + 32 * 33) * 4;
+    constexpr int CC = decltype(cc)::value, MM = decltype(mm)::value, smem = sweep_lds_bytes(CC, true);
     static unsigned long long lds_set = 0;      // (one per instantiation of this lambda, that is, per kernel)
     const hipError_t e = ensure_dynamic_lds(&k_dsm_bwd<CC, MM>, smem, &lds_set);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_dsm_bwd<CC, MM>), grid, dim3(256), smem, st, o.feat0, o.feat1, o.L, o.S, p.C, t.ofs_r, t.sum_r,
-                       t.pitch_r, t.ofs_c, t.sum_c, t.pitch_c, o.v, o.u, p.k2, p.part, G, side, p.v, p.u);
+    hipLaunchKernelGGL((k_dsm_bwd<CC, MM>), grid, dim3(256), smem, st, o.p.feat0, o.p.feat1, o.p.L, o.p.S, p.C, o.s.ofs_r,
+                       o.s.sum_r, o.s.pitch_r, o.s.ofs_c, o.s.sum_c, o.s.pitch_c, o.p.v, o.p.u, p.k2, p.part, G, side, p.v, p.u);
     return hipSuccess;
   };
-  auto with_mode = [&](auto cc) {
+  const hipError_t e = with_padded_channels(p.C, [&](auto cc) {
     if (mode == kDsmSparse) return launch(cc, int_c<kDsmSparse>{});
     return mode == kDsmStats ? launch(cc, int_c<kDsmStats>{}) : launch(cc, int_c<kDsmDense>{});
-  };
-  const int Cp = padded_channels(p.C);
-  const hipError_t e = Cp == 64 ? with_mode(int_c<64>{}) : Cp == 128 ? with_mode(int_c<128>{}) : with_mode(int_c<256>{});
+  });
   if (e != hipSuccess) return (int)e;
-  if (mode != kDsmStats) {
-    const long n4 = (long)p.N * o.L * p.C / 4;
-    hipLaunchKernelGGL(k_dsm_combine, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, (const float4*)p.part, n4, Z,
-                       p.inv_ct, (float4*)d_out);
-  }
+  if (mode != kDsmStats) return (int)launch_sweep_combine(o, grid.z, nullptr, d_out, st);
   return (int)hipGetLastError();
 }
 

@@ -173,10 +173,30 @@ struct DsmProblem {
   float k2, inv_ct;
   float *v, *u, *part;
 };
-// what every backward entry point does after its NULL checks: the remaining argument checks, then *p with v and u zeroed
+// what every backward entry point does after its NULL checks: dsm_carve = the remaining argument checks, then *p;
+// dsm_begin = dsm_carve, then v and u zeroed (the coarse loss's backward takes v and u from its forward call)
+int dsm_carve(const float* feat0, const float* feat1, int N, int L, int S, int C, float temperature, const DsmStats& s,
+              void* workspace, size_t workspace_bytes, DsmProblem* p);
 int dsm_begin(const float* feat0, const float* feat1, int N, int L, int S, int C, float temperature, const DsmStats& s,
               void* workspace, size_t workspace_bytes, hipStream_t st, DsmProblem* p);
 int dsm_zsplit(int N, int R);      // z slices of a sweep's column range, so that N * ceil(R / 32) * z fills the chip
+// the problem as the owner image of side `side` sees it (0: image 0, 1: image 1): its own descriptors, length, statistics
+// and sums come first; part is shared
+struct DsmSide { DsmProblem p; DsmStats s; };
+inline DsmSide dsm_side(const DsmProblem& p, const DsmStats& s, int side) {
+  if (!side) return {p, s};
+  return {{p.feat1, p.feat0, p.N, p.S, p.L, p.C, p.k2, p.inv_ct, p.u, p.v, p.part},
+          {s.ofs_c, s.sum_c, s.pitch_c, s.ofs_r, s.sum_r, s.pitch_r}};
+}
+inline dim3 dsm_sweep_grid(const DsmSide& o) { return dim3((o.p.L + 31) / 32, o.p.N, dsm_zsplit(o.p.N, o.p.L)); }
+// f(int_c<padded C>): the channel counts the sweeps are instantiated for
+template <typename F>
+inline hipError_t with_padded_channels(int C, F&& f) {
+  const int Cp = padded_channels(C);
+  return Cp == 64 ? f(int_c<64>{}) : Cp == 128 ? f(int_c<128>{}) : f(int_c<256>{});
+}
+// d_out [N][o.p.L][C] = inv_ct (* d_loss[0], if given: on the device) * sum over the Z partials of a gradient sweep
+hipError_t launch_sweep_combine(const DsmSide& o, int Z, const float* d_loss, float* d_out, hipStream_t st);
 // v / u contributions and own term 2 g c of K listed entries (k_dsm_uv, k_dsm_entries), gc[e] = g_e conf_e
 hipError_t launch_dsm_uv(const int64_t* b_ids, const int64_t* i_ids, const int64_t* j_ids, const float* gc, int K, int L, int S,
                          float* v, float* u, hipStream_t st);

@@ -366,6 +366,17 @@ def coarse_match(feat_c0, feat_c1, hw0_c, hw1_c, scale_px, thr=0.2, border_rm=2,
     raise RuntimeError("coarse_match: overflow persisted after retries")
 
 
+def _aligned_workspace(nbytes: int, device):
+    """(buffer, 256-byte aligned address) of at least nbytes of device memory"""
+    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
+    return ws, C.c_void_p(ws.data_ptr() + (-ws.data_ptr()) % 256)
+
+
+def _i64c(t: torch.Tensor) -> torch.Tensor:
+    """an id list as the library reads it: int64, contiguous"""
+    return t.to(torch.int64).contiguous()
+
+
 def _dsm_backward(f0, f1, temperature, buffers, b_ids, i_ids, j_ids, gc):
     """(dL/df0, dL/df1) of sum_e g_e conf_e from gc = g * conf at the entries (fm_dual_softmax_backward): two launches of
     one tiled kernel that recomputes the similarities tile by tile - no [N, L, S] array."""
@@ -375,15 +386,13 @@ def _dsm_backward(f0, f1, temperature, buffers, b_ids, i_ids, j_ids, gc):
     s = x1.shape[1]
     stats = buffers.softmax_stats()
     need = int(lib.fm_dual_softmax_backward_workspace_bytes(n, l, s, c))
-    ws = torch.empty(need + 256, dtype=torch.uint8, device=x0.device)
-    off = (-ws.data_ptr()) % 256
+    ws, wsp = _aligned_workspace(need, x0.device)
     d0, d1 = torch.empty_like(x0), torch.empty_like(x1)
     k = int(b_ids.shape[0])
-    b64 = lambda t: t.to(torch.int64).contiguous()
-    bb, ii, jj, g = b64(b_ids), b64(i_ids), b64(j_ids), _f32c(gc, "gc")
+    bb, ii, jj, g = _i64c(b_ids), _i64c(i_ids), _i64c(j_ids), _f32c(gc, "gc")
     _lib.check(lib.fm_dual_softmax_backward(_ptr(x0), _ptr(x1), n, l, s, c, float(temperature), *stats,
                                             _ptr(bb), _ptr(ii), _ptr(jj), _ptr(g), k,
-                                            C.c_void_p(ws.data_ptr() + off), need, _ptr(d0), _ptr(d1), _stream(x0.device)),
+                                            wsp, need, _ptr(d0), _ptr(d1), _stream(x0.device)),
                "fm_dual_softmax_backward")
     d0._keep = (ws, bb, ii, jj, g, buffers)
     return d0.to(f0.dtype), d1.to(f1.dtype)
@@ -398,8 +407,7 @@ class _DualSoftmaxAt(torch.autograd.Function):
         s = x1.shape[1]
         stats = buffers.softmax_stats()
         k = int(b_ids.shape[0])
-        b64 = lambda t: t.to(torch.int64).contiguous()
-        bb, ii, jj = b64(b_ids), b64(i_ids), b64(j_ids)
+        bb, ii, jj = _i64c(b_ids), _i64c(i_ids), _i64c(j_ids)
         conf = torch.empty(k, dtype=torch.float32, device=x0.device)
         _lib.check(lib.fm_dual_softmax_conf_at(_ptr(x0), _ptr(x1), n, l, s, c, float(temperature), *stats,
                                                _ptr(bb), _ptr(ii), _ptr(jj), k, _ptr(conf),
@@ -433,11 +441,10 @@ def _dsm_backward_dense(f0, f1, temperature, buffers, grad):
     g = _f32c(grad, "grad")
     stats = buffers.softmax_stats()
     need = int(lib.fm_dual_softmax_backward_workspace_bytes(n, l, s, c))
-    ws = torch.empty(need + 256, dtype=torch.uint8, device=x0.device)
-    off = (-ws.data_ptr()) % 256
+    ws, wsp = _aligned_workspace(need, x0.device)
     d0, d1 = torch.empty_like(x0), torch.empty_like(x1)
     _lib.check(lib.fm_dual_softmax_backward_dense(_ptr(x0), _ptr(x1), n, l, s, c, float(temperature), *stats, _ptr(g),
-                                                  C.c_void_p(ws.data_ptr() + off), need, _ptr(d0), _ptr(d1), _stream(x0.device)),
+                                                  wsp, need, _ptr(d0), _ptr(d1), _stream(x0.device)),
                "fm_dual_softmax_backward_dense")
     d0._keep = (ws, g, buffers)
     return d0.to(f0.dtype), d1.to(f1.dtype)
@@ -534,12 +541,11 @@ class _CoarseLoss(torch.autograd.Function):
         s = x1.shape[1]
         k = int(bb.shape[0])
         need = int(lib.fm_coarse_loss_workspace_bytes(n, l, s, c, k))
-        ws = torch.empty(need + 256, dtype=torch.uint8, device=x0.device)
+        ws, wsp = _aligned_workspace(need, x0.device)
         out = torch.empty(3, dtype=torch.float32, device=x0.device)
         ids = (_ptr(bb), _ptr(ii), _ptr(jj)) if k else (None, None, None)
         problem = (_ptr(x0), _ptr(x1), n, l, s, c, float(buffers._temperature), *buffers.softmax_stats(), kind, float(alpha),
-                   float(gamma), float(pos_weight), float(neg_weight), *ids, k,
-                   C.c_void_p(ws.data_ptr() + (-ws.data_ptr()) % 256), need)
+                   float(gamma), float(pos_weight), float(neg_weight), *ids, k, wsp, need)
         _lib.check(lib.fm_coarse_loss_forward(*problem, _ptr(out), _stream(x0.device)), "fm_coarse_loss_forward")
         ctx.problem, ctx.keep = problem, (x0, x1, bb, ii, jj, ws, buffers)
         ctx.dtypes = (feat_c0.dtype, feat_c1.dtype)
@@ -753,12 +759,6 @@ def fine_match(win0: torch.Tensor, win1: torch.Tensor, mix0: torch.Tensor, mix1:
     return out0, out1
 
 
-def _aligned_workspace(nbytes: int, device):
-    """(buffer, 256-byte aligned address) of at least nbytes of device memory"""
-    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
-    return ws, C.c_void_p(ws.data_ptr() + (-ws.data_ptr()) % 256)
-
-
 class _FineMatch(torch.autograd.Function):
     @staticmethod
     def forward(ctx, win0, win1, mix0, mix1, mkpts0_c, mkpts1_c, scale_f):
@@ -822,8 +822,7 @@ def gather_windows_backward(d_win: torch.Tensor, b_ids: torch.Tensor, ids: torch
     if m_max == 0:
         return d_feat.zero_()
     g = _f32c(d_win, "d_win")
-    b64 = lambda t: t.to(torch.int64).contiguous()
-    bb, ii = b64(b_ids), b64(ids)
+    bb, ii = _i64c(b_ids), _i64c(ids)
     need = int(lib.fm_gather_windows_backward_workspace_bytes(n, int(h_c), int(w_c), m_max))
     ws, wsp = _aligned_workspace(need, dev)
     _lib.check(lib.fm_gather_windows_backward(_ptr(g), _ptr(bb), _ptr(ii), _ptr(count), m_max, n, cf, hf, wf, layout, w,

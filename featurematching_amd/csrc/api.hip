@@ -8,6 +8,8 @@
 
 namespace fm {
 
+int g_unit_cert = 0;
+
 int choose_splits(int N, int panels, int tiles, int target) {
   // One workgroup per (sample, panel, split); aim at one full round of the 256 CUs when the
   // batch alone cannot fill them (a split shorter than 2 tiles is not worth its prologue).
@@ -66,6 +68,11 @@ CoarseWs coarse_layout(int N, int L, int S, int C, int slots, bool alone) {
     // 91 / 77 / 88 us; 640x960 (25 tiles per workgroup) keeps 256: 12 949 against 12 792 pairs/s)
     if (target == kMaxPassTarget && w.tiles / choose_splits(N, w.panels, w.tiles, kMaxPassTarget) >= 32) target = kMaxPassSlots;
     w.splits0 = choose_splits(N, w.panels, w.tiles, target);
+    // The top-2 epilogue of the max pass (and the screening that reads it) where a launch cannot fill the chip and its
+    // workgroups are short: the rule that picks kMaxPassTarget above, and FM_MODE_ALONE launches of the same shapes (the
+    // answer must not depend on `alone`: the diagnostic entry points lay a workspace out without it).  A batch is bound
+    // by the max pass's epilogue and a 1024x1024 pair by its matrix cores: they keep the plain epilogue.
+    w.top2 = N * w.panels < kMaxPassSlots && w.tiles / choose_splits(N, w.panels, w.tiles, kMaxPassTarget) < 32;
   }
 #ifdef FM_TUNE_ENV
   if (const char* e = getenv("FM_TARGET_WGS0")) w.splits0 = choose_splits(N, w.panels, w.tiles, atoi(e) > 0 ? atoi(e) : kMaxPassTarget);
@@ -109,6 +116,9 @@ CoarseWs coarse_layout(int N, int L, int S, int C, int slots, bool alone) {
   w.ccand_i = take(cols * slots * 4); w.ccand_x = take(cols * slots * 4);
   w.thr_r = take(rows * 4); w.thr_c = take(cols * 4);
   w.wmaxb = take(rows / 32 * 4); w.cmaxu = take(cols / 32 * 4);
+  w.tmin_r = take(rows / 32 * 4); w.tmin_c = take(cols / 32 * 4);
+  w.umax2 = take(rows / 32 * (cols / N / 32) * 4);
+  w.upos = take(rows / 32 * (cols / N / 32) * 4);
   w.common_total = o;
   // ---- FM_MODE_DENSE / FM_MODE_EXACT_SCREENING / conf_matrix ----
   w.hi0 = take(rows * C * 2); w.lo0 = take(rows * C * 2);
@@ -309,7 +319,7 @@ static int coarse_match_impl(const void* feat0, const void* feat1, int in_dtype,
     // prep: clear the per-call counters, quantise both images (one int8 step per image), L1 norms
     FM_TRY(launch_prep(feat0, feat1, in_dtype, C, w, base, p.exact_step, p.flat, st));
     // max pass: row / column / unit maxima of the integer screening product (atomicMax: no partials, no reduction kernel)
-    FM_TRY(launch_max_i8(w, base, st));
+    FM_TRY(launch_max_i8(w, base, unit_cert_on(w, !p.dense), st));
     // sparse sum kernel: stabilisers, live units, exact terms of the few significant entries, candidates (listed per row
     // and per column); flags the samples with too many significant entries per unit (flat similarity).  FM_MODE_FLAT:
     // the sweep would only find that out again - a small kernel forms the stabilisers and flags every sample
@@ -507,7 +517,7 @@ extern "C" int fm_debug_launch_corr(void* workspace, int N, int L, int S, int C,
   if (const int bad = checked_layout(workspace, N, L, S, C, cand_slots, &w)) return bad;
   if (mode < 0 || mode > 2) return FM_E_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
-  if (mode == 0) return (int)launch_max_i8(w, (char*)workspace, st);
+  if (mode == 0) return (int)launch_max_i8(w, (char*)workspace, unit_cert_on(w), st);
   if (mode == 1) return (int)launch_dense(w, (char*)workspace, 1.0f / ((float)C * temperature), thr, st);
   return (int)launch_dense(w, (char*)workspace, 1.0f / ((float)C * temperature), thr, st, nullptr, 1);      // mode 2: the re-screening
 }
@@ -556,6 +566,26 @@ extern "C" int fm_debug_reset_counters(void* workspace, int N, int L, int S, int
   CoarseWs w;
   if (const int bad = checked_layout(workspace, N, L, S, C, cand_slots, &w)) return bad;
   return (int)clear_spans((char*)workspace, w.counters, (hipStream_t)stream);
+}
+
+// Test-only switch of the unit certificate (process-global; returns the previous value, mode outside 0..2 only reads).
+extern "C" int fm_debug_unit_cert(int mode) {
+  const int prev = g_unit_cert;
+  if (mode >= 0 && mode <= 2) g_unit_cert = mode;
+  return prev;
+}
+
+// Diagnostic: where the certificate's arrays live (byte offsets: umax, umax2, upos, thr_r, thr_c, tmin_r, tmin_c, the
+// counter of certified units) and whether the launch plan of this shape uses them (out[8]).
+extern "C" int fm_debug_unit_cert_layout(int N, int L, int S, int C, int cand_slots, int64_t* out, int n_out) {
+  if (!out) return FM_E_NULL;
+  if (n_out < 9) return FM_E_SHAPE;
+  CoarseWs w;
+  if (const int bad = checked_layout(true, N, L, S, C, cand_slots, &w)) return bad;
+  const int64_t v[9] = {(int64_t)w.umax, (int64_t)w.umax2, (int64_t)w.upos, (int64_t)w.thr_r, (int64_t)w.thr_c,
+                        (int64_t)w.tmin_r, (int64_t)w.tmin_c, (int64_t)(w.scalars + offsetof(Scalars, cert_units)), w.top2};
+  for (int i = 0; i < 9; ++i) out[i] = v[i];
+  return FM_OK;
 }
 
 extern "C" int fm_read_count(const int32_t* d_count, int cap, int32_t* m_out, void* stream) {

@@ -32,6 +32,7 @@ typedef int v16i __attribute__((ext_vector_type(16)));
 struct MaxArgs {
   const signed char* q0; const signed char* q1;
   unsigned* rowmax_u; unsigned* colmax_u; float* umax;
+  int* umax2; int* upos;  // TOP2: runner-up of every unit and the place of its maximum (fm_internal.h)
   const float4* bstat0; const float4* bstat1; float* imgstat;   // block statistics of k_prep_split -> per-sample maxima
   float* diag;            // diagnostic build: stamp buffer
   int L, S, Lp, Sp, panels, tiles, splits, tiles_per_split, pgroup;
@@ -73,7 +74,15 @@ __device__ __forceinline__ int halves_max_i(int v) {
 #define FM_MAX_EPI 3           // experiments: bit 0 = row maxima, bit 1 = column / unit maxima
 #endif
 
-template <int C>
+// TOP2 (launches that cannot fill the chip: CoarseWs::top2): the column-maximum trees and the unit maximum's DPP chain
+// give way to a top-2 with position.  Every accumulator register becomes the key (value << 4) | register (|value| < 2^23:
+// 28 bits; padded entries -2^26), a lane keeps the two largest keys of its 16 per row block (v_max + v_med3 per key), the
+// two halves and then the 32 columns merge their pairs (largest = max, runner-up = max3(min, runner-ups)), so that lane
+// 31 / 63 ends with the unit's largest key and its second-largest WITH multiplicity (a tie repeats the value; keys of one
+// lane differ in the register bits, which the value comparison downstream drops).  The lane that owns the largest key
+// is found by comparing every lane's own best key against it (one ballot per row block).  About 150 more vector
+// instructions per 64 x 32 unit pair than the plain epilogue: only where the matrix cores are not what the launch waits for.
+template <int C, bool TOP2>
 __global__ __launch_bounds__(256, 2) void k_max_i8(MaxArgs a) {
   constexpr int KS8 = C / 32;                       // k-steps of 32 channels
   constexpr int TILE_BYTES = kTileCols * C;         // 64 columns x C bytes
@@ -237,13 +246,15 @@ __global__ __launch_bounds__(256, 2) void k_max_i8(MaxArgs a) {
       asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(bq_[ks % RING]) : "v"(base_), "n"(ks * 1024));
     };
 #define issue(...) issue_(__VA_ARGS__, bq, base)
+    // (TOP2: a masked entry must survive the key's shift by 4; still below every real product, |q . q| < 2^23)
+    constexpr int kMasked = TOP2 ? -(1 << 26) : kQMasked;
     auto mask_edge = [&](v16i& ac, bool row_edge, int row00) {
       const int ucol0 = uc * 32;
       if (row_edge || ucol0 + 32 > a.S) {              // padded rows (>= L) / columns (>= S) never count
         const bool cok = ucol0 + r < a.S;
 #pragma unroll
         for (int g = 0; g < 16; ++g)
-          if (!cok || row00 + (g & 3) + 8 * (g >> 2) + 4 * h >= a.L) ac[g] = kQMasked;
+          if (!cok || row00 + (g & 3) + 8 * (g >> 2) + 4 * h >= a.L) ac[g] = kMasked;
       }
     };
     // The epilogue of a unit as 16 instruction groups, one behind each MFMA of a C = 256 unit (C = 128 / 64: two / four
@@ -279,7 +290,79 @@ __global__ __launch_bounds__(256, 2) void k_max_i8(MaxArgs a) {
     using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>;
     using I2 = std::integral_constant<int, 2>; using I3 = std::integral_constant<int, 3>;
     using I4 = std::integral_constant<int, 4>;
+    // ---- TOP2: keys, lane top-2 (E: three keys per group, groups 0..10), halves (6, 11), columns (12..14), store (15) ----
+    int m1a = 0, m2a = 0, m1b = 0, m2b = 0;        // this lane's two largest keys of row block 0 / 1
+    int n1a = 0, n2a = 0, n1b = 0, n2b = 0;        // ... of its column over both halves
+    int um2 = 0;
+    auto E = [&](int e) {
+      if (e >= 32) return;
+      const int g = e & 15;
+      int& m1 = e < 16 ? m1a : m1b;
+      int& m2 = e < 16 ? m2a : m2b;
+      const int v = e < 16 ? ac0[g] : ac1[g];
+      if (g == 0) {
+        asm volatile("v_lshlrev_b32 %0, 4, %2\n\tv_mov_b32 %1, %3" : "=&v"(m1), "=&v"(m2) : "v"(v), "v"(kQMasked));
+      } else {
+        int key;
+        asm volatile("v_lshl_or_b32 %2, %3, 4, %4\n\tv_med3_i32 %1, %0, %1, %2\n\tv_max_i32 %0, %0, %2"
+                     : "+v"(m1), "+v"(m2), "=&v"(key) : "v"(v), "n"(g));
+      }
+    };
+    auto halves2 = [&](int m1, int m2, int& n1, int& n2) {
+      int p1 = m1, q1 = m1, p2 = m2, q2 = m2, t;
+      asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\tv_permlane32_swap_b32 %2, %3"
+                   : "+v"(p1), "+v"(q1), "+v"(p2), "+v"(q2));
+      asm volatile("v_min_i32 %0, %2, %3\n\tv_max_i32 %1, %2, %3" : "=&v"(t), "=&v"(n1) : "v"(p1), "v"(q1));
+      asm volatile("v_max3_i32 %0, %1, %2, %3" : "=v"(n2) : "v"(t), "v"(p2), "v"(q2));
+    };
+    // one step of the merge over the columns: (um, um2) with the pair of the lane the DPP control names
+#define FM_TOP2_STEP(CTRL)                                                                                              \
+    { int t, b2;                                                                                                          \
+      asm volatile("s_nop 1\n\tv_min_i32_dpp %2, %0, %0 " CTRL "\n\tv_mov_b32_dpp %3, %1 " CTRL "\n\t"                     \
+                   "v_max_i32_dpp %0, %0, %0 " CTRL "\n\tv_max3_i32 %1, %2, %1, %3"                                       \
+                   : "+v"(um), "+v"(um2), "=&v"(t), "=&v"(b2)); }
+    auto dpp2 = [&](auto step) {
+      constexpr int st = decltype(step)::value;
+      if (st == 0) FM_TOP2_STEP("quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf")
+      else if (st == 1) FM_TOP2_STEP("quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf")
+      else if (st == 2) FM_TOP2_STEP("row_half_mirror row_mask:0xf bank_mask:0xf")
+      else if (st == 3) FM_TOP2_STEP("row_mirror row_mask:0xf bank_mask:0xf")
+      else FM_TOP2_STEP("row_bcast:15 row_mask:0xa bank_mask:0xf")
+    };
+#undef FM_TOP2_STEP
+    auto group2 = [&](int s) {
+      if (s == 0) { mask_edge(ac0, row_edge0, wrow0); mask_edge(ac1, row_edge1, wrow0 + 32); }
+      R(2 * s); R(2 * s + 1);
+      if (s < 11) { E(3 * s); E(3 * s + 1); E(3 * s + 2); }
+      if (s == 6) halves2(m1a, m2a, n1a, n2a);
+      if (s == 11) halves2(m1b, m2b, n1b, n2b);
+      if (s == 12) {
+        // (a key orders like its value: the column maximum over both row blocks is the larger key's value)
+        asm volatile("ds_max_u32 %0, %1" ::"v"(colmax_a + ((((uc >> 1) - t0) % 3) * 64 + (uc & 1) * 32 + r) * 4),
+                     "v"(q_encode(max(n1a, n1b) >> 4)) : "memory");
+        um = h ? n1b : n1a;                                           // block 0 in lanes 0..31, block 1 in 32..63
+        um2 = h ? n2b : n2a;
+        asm volatile("s_nop 1" : "+v"(um), "+v"(um2));
+        dpp2(I0{});
+      }
+      if (s == 13) { dpp2(I1{}); dpp2(I2{}); }
+      if (s == 14) { dpp2(I3{}); dpp2(I4{}); }
+      if (s == 15) {
+        asm volatile("s_nop 1" : "+v"(um));
+        const int k0 = __builtin_amdgcn_readlane(um, 31), k1 = __builtin_amdgcn_readlane(um, 63);
+        const unsigned long long w0 = __ballot(m1a == k0), w1 = __ballot(m1b == k1);
+        const int lw = h ? __builtin_ctzll(w1) : __builtin_ctzll(w0);      // a lane that holds the unit's largest key
+        if (r == 31) {
+          const long at = ((long)b * (a.Lp / 32) + wrow0 / 32 + h) * nunits + uc;
+          const int v1 = um >> 4, v2 = um2 >> 4;
+          a.umax[at] = (float)(v1 <= kMasked ? kQMasked : v1);
+          a.umax2[at] = v2 <= kMasked ? kQMasked : v2;
+          a.upos[at] = (lw << 4) | (um & 15);
+        }
+      }
+    };
     auto group = [&](int s) {
+      if constexpr (TOP2) { group2(s); return; }
       if (s == 0) { mask_edge(ac0, row_edge0, wrow0); mask_edge(ac1, row_edge1, wrow0 + 32); }
       R(2 * s); R(2 * s + 1);
       if (s < 8) T(ac0, ta, s);
@@ -385,6 +468,7 @@ __global__ __launch_bounds__(256, 2) void k_max_i8(MaxArgs a) {
     fold_columns(t1 - 1);
   }
   if (stat_wg && tid < 6) a.imgstat[(long)b * 8 + tid] = __uint_as_float(s_colmax[192 + tid]);
+  if (stat_wg && tid == 6) a.imgstat[(long)b * 8 + 6] = TOP2 ? 1.f : 0.f;      // (the screening looks at umax2 / upos only then)
 
 #ifdef FM_DIAG_CLOCK
   const unsigned long long dg_tail0 = __builtin_amdgcn_s_memtime();
@@ -453,11 +537,12 @@ __global__ __launch_bounds__(256, 2) void k_max_i8(MaxArgs a) {
 #endif
 }
 
-hipError_t launch_max_i8(const CoarseWs& w, char* base, hipStream_t st) {
+hipError_t launch_max_i8(const CoarseWs& w, char* base, bool top2, hipStream_t st) {
   MaxArgs a;
   a.q0 = (const signed char*)(base + w.q0); a.q1 = (const signed char*)(base + w.q1);
   a.rowmax_u = (unsigned*)(base + w.rowmax_u); a.colmax_u = (unsigned*)(base + w.colmax_u);
   a.umax = (float*)(base + w.umax);
+  a.umax2 = (int*)(base + w.umax2); a.upos = (int*)(base + w.upos);
   a.bstat0 = (const float4*)(base + w.bstat0); a.bstat1 = (const float4*)(base + w.bstat1);
   a.imgstat = (float*)(base + w.imgstat);
   a.diag = (float*)(base + w.rowB);      // (diagnostic builds run on a full-size workspace)
@@ -476,10 +561,16 @@ hipError_t launch_max_i8(const CoarseWs& w, char* base, hipStream_t st) {
   hipError_t e = hipSuccess;
 #define FM_MAX_CASE(CC)                                                                        \
   case CC: {                                                                                   \
-    static unsigned long long lds_set = 0;                                                     \
-    e = ensure_dynamic_lds(&k_max_i8<CC>, 4 * kTileCols * CC, &lds_set);                       \
-    if (e != hipSuccess) return e;                                                             \
-    hipLaunchKernelGGL(k_max_i8<CC>, dim3(blocks), dim3(256), 4 * kTileCols * CC, st, a);      \
+    static unsigned long long lds_set[2] = {0, 0};                                             \
+    if (top2) {                                                                                \
+      e = ensure_dynamic_lds(&k_max_i8<CC, true>, 4 * kTileCols * CC, &lds_set[1]);            \
+      if (e != hipSuccess) return e;                                                           \
+      hipLaunchKernelGGL((k_max_i8<CC, true>), dim3(blocks), dim3(256), 4 * kTileCols * CC, st, a);  \
+    } else {                                                                                   \
+      e = ensure_dynamic_lds(&k_max_i8<CC, false>, 4 * kTileCols * CC, &lds_set[0]);           \
+      if (e != hipSuccess) return e;                                                           \
+      hipLaunchKernelGGL((k_max_i8<CC, false>), dim3(blocks), dim3(256), 4 * kTileCols * CC, st, a); \
+    }                                                                                          \
     break;                                                                                     \
   }
   switch (w.C) {

@@ -30,6 +30,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <type_traits>
+
 #include "fm_device.h"
 
 namespace fm {
@@ -74,6 +76,20 @@ __device__ __forceinline__ float half_reduce32_max(float v) {
   { float t = dpp_mov_s<0x104, 0x5>(v, v); t = dpp_mov_s<0x114, 0xA>(t, v); v = fmaxf(v, t); }   // lane ^ 4
   v = fmaxf(v, dpp_mov_s<0x128, 0xf>(v, v));                                                      // lane ^ 8
   { float p = v, q = v; asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(p), "+v"(q)); v = fmaxf(p, q); }
+  return v;
+}
+// minimum over the 32 lanes that share lane >> 5, integers (the same steps)
+__device__ __forceinline__ int half_reduce32_min_i(int v) {
+  auto mv = [](auto ctrl, auto bank, int old, int x) {
+    return __builtin_amdgcn_update_dpp(old, x, decltype(ctrl)::value, 0xf, decltype(bank)::value, false);
+  };
+  using std::integral_constant;
+  v = min(v, mv(integral_constant<int, 0xB1>{}, integral_constant<int, 0xf>{}, v, v));
+  v = min(v, mv(integral_constant<int, 0x4E>{}, integral_constant<int, 0xf>{}, v, v));
+  { int t = mv(integral_constant<int, 0x104>{}, integral_constant<int, 0x5>{}, v, v);
+    t = mv(integral_constant<int, 0x114>{}, integral_constant<int, 0xA>{}, t, v); v = min(v, t); }
+  v = min(v, mv(integral_constant<int, 0x128>{}, integral_constant<int, 0xf>{}, v, v));
+  { int p = v, q = v; asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(p), "+v"(q)); v = min(p, q); }
   return v;
 }
 // sum over the 16 lanes of a DPP row, in a fixed order (every lane of the row ends with the same bits)
@@ -162,6 +178,10 @@ __global__ __launch_bounds__(256) void k_stab(ScreenArgs a, float* f16inv) {
 // ---------------------------------------------------------------------------------------------------------------------
 struct RowsExtra {
   int* thr_r; int* thr_c; float* wmaxb; float* cmaxu;
+  int* tmin_r; int* tmin_c;              // k_thresh: smallest integer threshold of every 32-row block / 32-column unit
+  const int* umax2; const int* upos;     // max pass with the top-2 epilogue (valid when imgstat[b][6] != 0; fm_internal.h)
+  int look;                              // 0: fm_debug_unit_cert(1), never look
+  int count_cert;                        // fm_debug_unit_cert(2): count the certified live units
   int nchunks, chunk_units, items;       // chunk_units <= 64 units per item (one ballot covers a chunk)
 };
 
@@ -208,9 +228,14 @@ __global__ __launch_bounds__(256) void k_thresh(ScreenArgs a, RowsExtra x) {
                            : q8_margin_raw(sig0, bl1, clipA, sig1, l1B_max, clipB, a.cpad), a.inv_ct);
   }
   (side ? a.nmc : a.nmr)[g] = nm;
-  (side ? x.thr_c : x.thr_r)[g] = idx < len ? sig_threshold(nm, emu, inv_kss) : 0x3fffffff;
+  const int thr = idx < len ? sig_threshold(nm, emu, inv_kss) : 0x3fffffff;
+  (side ? x.thr_c : x.thr_r)[g] = thr;
   const float bm = half_reduce32_max(nm);
-  if ((lane & 31) == 0) (side ? x.cmaxu : x.wmaxb)[(long)b * nblk + blk] = bm;
+  const int tm = half_reduce32_min_i(thr);
+  if ((lane & 31) == 0) {
+    (side ? x.cmaxu : x.wmaxb)[(long)b * nblk + blk] = bm;
+    (side ? x.tmin_c : x.tmin_r)[(long)b * nblk + blk] = tm;
+  }
 }
 
 template <int C>
@@ -250,6 +275,12 @@ __global__ __launch_bounds__(256, 3) void k_screen_rows(ScreenArgs a, RowsExtra 
   const float um = a.umax[((long)b * nrb + rb) * nunits + u0 + ul_c];
   const float cm = x.cmaxu[(long)b * nunits + u0 + ul_c];
   const float bl1B = a.bstat1[(long)b * nunits + u0 + ul_c].x;
+  // the unit certificate (lane = unit): the unit's runner-up against the smallest threshold any of its entries can meet
+  // (loaded in the same round trip whether or not the max pass wrote them - ist[6] says so: the values are used only then)
+  const bool look = x.look && ist[6] != 0.f;
+  const int um2 = x.umax2[((long)b * nrb + rb) * nunits + u0 + ul_c];
+  const int upos = x.upos[((long)b * nrb + rb) * nunits + u0 + ul_c];
+  const int tmin = min(x.tmin_r[(long)b * nrb + rb], x.tmin_c[(long)b * nunits + u0 + ul_c]);
   int trr[16];
   {
     const int* tp = x.thr_r + (long)b * a.Lp + wrow0 + 4 * h;
@@ -277,6 +308,12 @@ __global__ __launch_bounds__(256, 3) void k_screen_rows(ScreenArgs a, RowsExtra 
     const bool hot = lane < U && (!screen_ok || !((top + wmax < -kSkipLog2) && (top + cm < -kSkipLog2)));
     live = __ballot(hot);
   }
+  // Certified units: every entry but the one at upos is <= um2 <= tmin <= min(thr_r[i], thr_c[j]), so the unit parks
+  // exactly that entry if the unit's maximum passes ITS two thresholds, and nothing otherwise - the same integers on
+  // both sides as in screen_unit below, without the unit's B fragments and MFMAs.  A tie (um2 == the maximum) passes only
+  // when nothing of the unit is significant.
+  const unsigned long long cert = look ? (live & __ballot(um2 <= tmin)) : 0ull;
+  live &= ~cert;
   // A unit with more significant entries than the exact phase resolves (flat similarity) sends its whole SAMPLE to the
   // dense sum kernel, and from then on every list of the sample is dead weight: a wave stops at its first such unit, and
   // does not start when the sample is flagged already (a plain, possibly stale load: only an optimisation).
@@ -286,6 +323,14 @@ __global__ __launch_bounds__(256, 3) void k_screen_rows(ScreenArgs a, RowsExtra 
 #ifdef FM_ABL_ROWS          // ablation builds (tools/): 1 = no sweep, 2 = no exact phase
   if (FM_ABL_ROWS & 1) live = 0;
 #endif
+  int cert_thr = 0x3fffffff, cert_key = 0;
+  if (!flat && ((cert >> lane) & 1)) {
+    const int g = upos & 15, lw = (upos >> 4) & 63;
+    const int rl = (g & 3) + 8 * (g >> 2) + 4 * (lw >> 5), cl = lw & 31;
+    cert_thr = min(x.thr_r[(long)b * a.Lp + wrow0 + rl], x.thr_c[(long)b * a.Sp + (u0 + lane) * 32 + cl]);
+    cert_key = (lane << 10) | (rl << 5) | cl;
+  }
+  if (x.count_cert && cert && lane == 0) atomicAdd(&a.scal->cert_units, __builtin_popcountll(cert));
   if (!flat && live) {
     const bool row_edge = (wrow0 + 32 > a.L);
     const signed char* q1b = a.q1 + ((long)b * nunits + u0) * KS8 * 1024 + lane * 16;
@@ -349,8 +394,19 @@ __global__ __launch_bounds__(256, 3) void k_screen_rows(ScreenArgs a, RowsExtra 
       screen_unit(ulB, bB, tcB);
       if (ulA < 0 || nd_units) break;
     }
-    if (nd_units) nlist = 0;           // the sample goes to the dense kernel: its lists are not read
   }
+  if (!flat && cert && !nd_units) {
+    // (the lists are unordered: k_select sorts by key.  Certified units hold <= 1 entry each, so the only limit they can
+    // meet is LIST, and the wave's total decides that in either order)
+    const unsigned long long hits = __ballot((int)um > cert_thr);
+    const int nh = __builtin_popcountll(hits);
+    if (nlist + nh > LIST) ++nd_units;
+    else {
+      if ((hits >> lane) & 1) s_list[wv][nlist + __builtin_popcountll(hits & ((1ull << lane) - 1ull))] = cert_key;
+      nlist += nh;
+    }
+  }
+  if (nd_units) nlist = 0;             // the sample goes to the dense kernel: its lists are not read
 
   // ---- the parked entries: exact float32 dot products (as in k_screen; stabilisers from k_thresh's arrays) ----
   int overflow = 0;
@@ -480,6 +536,10 @@ hipError_t launch_screen(const void* feat0, const void* feat1, int in_dtype, int
   RowsExtra x;
   x.thr_r = (int*)(base + w.thr_r); x.thr_c = (int*)(base + w.thr_c);
   x.wmaxb = (float*)(base + w.wmaxb); x.cmaxu = (float*)(base + w.cmaxu);
+  x.tmin_r = (int*)(base + w.tmin_r); x.tmin_c = (int*)(base + w.tmin_c);
+  x.umax2 = (const int*)(base + w.umax2); x.upos = (const int*)(base + w.upos);
+  x.look = g_unit_cert != 1;
+  x.count_cert = g_unit_cert == 2;
   x.chunk_units = w.units_s;
   x.nchunks = w.splits_s;
 #ifdef FM_TUNE_ENV

@@ -37,6 +37,16 @@ int fm_debug_reset_counters(void* workspace, int N, int L, int S, int C, int can
  * like fm_debug_launch_prep), which = 1 the stabiliser kernel k_stab.  Full-size workspace. */
 int fm_debug_launch_flat(void* workspace, const float* feat0, const float* feat1, int N, int L, int S, int C,
                          int cand_slots, float temperature, float thr, int which, void* stream);
+/* Test-only, process-global: the unit certificate of the screening (the max pass publishes every 32 x 32 unit's
+ * runner-up and the place of its maximum; k_screen_rows resolves the units they certify without sweeping them).
+ * mode 0 = the launch plan decides (default), 1 = off, 2 = on for every shape (and k_screen_rows counts the live units
+ * it certified); any other value only reads.  Returns the previous mode.  Set it between complete calls only.
+ * (The plan takes the certificate on the common path only - not with FM_MODE_DENSE / FM_MODE_FLAT / statistics of every
+ * row; fm_debug_launch_corr, which knows no mode, follows the shape's rule alone.) */
+int fm_debug_unit_cert(int mode);
+/* Byte offsets in the coarse workspace of umax, umax2, upos, thr_r, thr_c, tmin_r, tmin_c and the counter of certified
+ * units (int32, zeroed per call), then whether the launch plan of this shape uses the certificate (9 values). */
+int fm_debug_unit_cert_layout(int N, int L, int S, int C, int cand_slots, int64_t* out, int n_out);
 
 #ifdef __cplusplus
 }

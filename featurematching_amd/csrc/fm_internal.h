@@ -58,6 +58,9 @@ struct CoarseWs {
   int N, L, S, C, Lp, Sp, panels, tiles, splits, slots;
   int splits0;                                // column splits of the max pass (its own grid size)
   int splits_s, units_s;                      // screening kernel: column chunks per row block and 32-column units per chunk (<= 64)
+  int top2;                                   // the launch plan's choice: the max pass also publishes every unit's runner-up and
+                                              // the place of its maximum (k_max_i8<C, true>), and the screening resolves the
+                                              // units they certify without sweeping them (a function of the shape alone)
   Span prep_zero;                             // zeroed by k_prep_split on every call: the (zeroed) fields below
   Span reassign[3];                           // zeroed before the assignment runs again on a call's results: its cell
                                               // maps and tie lists, its look-back totals, the status word
@@ -78,7 +81,8 @@ struct CoarseWs {
   size_t q0, q1;                              // int8 screening planes
   size_t sigimg;                              // [N][2] the int8 step of image 0 / image 1 of every sample
   size_t imgstat;                             // [N][8] per sample {largest L1 norm, largest clipped mass, largest |x|} of
-                                              // image 0, then of image 1 (max pass: the block statistics folded once)
+                                              // image 0, then of image 1 (max pass: the block statistics folded once);
+                                              // [6]: 1 when that max pass wrote umax2 / upos, else 0
   size_t l1_0, l1_1;                          // L1 norm per descriptor
   size_t bstat0, bstat1;                      // float4 per 32-row block: {largest L1 norm (+inf: a bad value), largest
                                               // clipped L1 mass sum_k max(|x_k| - 127 sigma, 0), largest |x|, 0}
@@ -92,6 +96,10 @@ struct CoarseWs {
   size_t ccand_i, ccand_x;                    // ... of a column (row, exact dot product)
   size_t thr_r, thr_c;                        // k_thresh (batched screening): integer significance threshold per row / column
   size_t wmaxb, cmaxu;                        // ... largest -stabiliser*log2e of every 32-row block / 32-column unit
+  size_t tmin_r, tmin_c;                      // ... smallest integer threshold of every 32-row block / 32-column unit
+  size_t umax2, upos;                         // k_max_i8<C, true>, [N][Lp/32][Sp/32] ints: the unit's second-largest valid entry
+                                              // (with multiplicity; kQMasked: none) and where one entry equal to its maximum
+                                              // sits: (lane of the accumulator << 4) | register, lane = 32 (row bit 2) + column
   size_t common_total;
   // ---- dense / exact-screening / conf_matrix only ----
   size_t hi0, lo0, hi1, lo1;                  // float16 planes
@@ -112,8 +120,19 @@ CoarseWs coarse_layout(int N, int L, int S, int C, int slots, bool alone = false
 struct Scalars {          // lives at ws.scalars (zeroed per call)
   unsigned flags;         // FM_DEV_* bits
   int dense_units;        // 32x32 units the sparse sum kernel left to the dense one (0: that kernel exits at once)
-  int reserved;
+  int cert_units;         // live units k_screen_rows resolved from the max pass's certificate (counted only while
+                          // fm_debug_unit_cert forces the certificate on)
 };
+
+// fm_debug_unit_cert: 0 = the launch plan decides, 1 = never, 2 = always.  The plan takes the top-2 epilogue where the
+// shape allows it (CoarseWs::top2) and the call runs the common path: with FM_MODE_DENSE / FM_MODE_FLAT / every row's
+// statistics the caller expects flat similarity, where the screening stops at its first dense unit or does not run at
+// all and the epilogue would only cost ('mixed' / 'borderline' pairs: -1.4 % / -2.6 %).  Every max pass records in
+// imgstat[b][6] whether it wrote umax2 / upos, and the screening looks only then - whatever ran on the workspace last.
+extern int g_unit_cert;
+inline bool unit_cert_on(const CoarseWs& w, bool common_path = true) {
+  return g_unit_cert == 2 || (g_unit_cert == 0 && w.top2 != 0 && common_path);
+}
 
 // ---- launchers (each enqueues on `st`, returns hipGetLastError()) ----
 hipError_t launch_prep(const void* feat0, const void* feat1, int in_dtype, int c_in, const CoarseWs& w, char* base,
@@ -123,7 +142,7 @@ hipError_t launch_prep(const void* feat0, const void* feat1, int in_dtype, int c
 hipError_t launch_stab(const CoarseWs& w, char* base, float inv_ct, float thr, int allow_dead, hipStream_t st);
 hipError_t launch_prep_f16(const void* feat0, const void* feat1, int in_dtype, int c_in, const CoarseWs& w, char* base,
                            int force, hipStream_t st);
-hipError_t launch_max_i8(const CoarseWs& w, char* base, hipStream_t st);
+hipError_t launch_max_i8(const CoarseWs& w, char* base, bool top2, hipStream_t st);
 // (conf != NULL: the CONF variant - writes the dense conf_matrix of every sample from the log-softmax offsets;
 // rescreen: the exact re-screening of FM_MODE_EXACT_SCREENING with the same offsets)
 hipError_t launch_dense(const CoarseWs& w, char* base, float inv_ct, float thr, hipStream_t st, float* conf = nullptr,

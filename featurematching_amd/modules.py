@@ -8,6 +8,10 @@
         (network/utils/fine_matching_new.py:22)
     CoarseLoss.forward(data) -> Tensor
         (Loss.compute_coarse_loss, losses/loss.py:27, from the supervision ids instead of two [N,L,S] arrays)
+    FineLoss.forward(data) -> Tensor
+        (Loss.compute_fine_loss, losses/loss.py:70)
+    Loss.forward(data) -> None
+        (losses/loss.py:116)
 
 Constructors take the same lower-cased config sub-dicts as network/net.py:29-32.  The
 computation runs in the HIP kernels of libfmatch_hip.so (see ops.py); only the learned
@@ -132,6 +136,101 @@ class CoarseLoss(nn.Module):
         buffers, feat_c0, feat_c1 = data['_fm_coarse_loss']
         return ops.coarse_loss(feat_c0, feat_c1, data['spv_b_ids'], data['spv_i_ids'], data['spv_j_ids'], buffers,
                                self.coarse_type, self.alpha, self.gamma, self.pos_weight, self.neg_weight, self.sparse_spvs)
+
+
+def _fine_term(expec, gt):
+    """one image's share of the fine loss: squared offset in units of the 7-pixel window, weighted by the inverse std
+    (normalised to mean 1 over ALL rows and detached: a larger std must not pay), averaged over the rows whose ground
+    truth is set (gt x != 0); without such a row the mean of nothing, NaN"""
+    inv = expec[:, 2].clamp(min=1e-10).reciprocal()
+    weight = (inv / inv.mean()).detach()
+    sq = (expec[:, :2] - gt).square().sum(-1) / 49
+    return (sq * weight)[gt[:, 0] != 0].mean()
+
+
+def fine_loss_torch(expec0, expec1, gt0, gt1):
+    """The fine loss of the reference's training mode (Loss.compute_fine_loss, losses/loss.py:70-98) in torch ops, on
+    any device and dtype: what FineLoss computes on CPU tensors and, evaluated in float64 / float32, the yardstick of the
+    HIP kernels (pinned to the reference's own numbers by tests/test_supervision_ref.py).  Syncs the host twice."""
+    if expec0.sum() == 0:            # the reference's stand-in loss for a step without fine predictions
+        return torch.zeros((), dtype=expec0.dtype, device=expec0.device)
+    return _fine_term(expec0, gt0) + _fine_term(expec1, gt1)
+
+
+def coarse_loss_torch(conf, conf_gt, coarse_type, alpha, gamma, pos_weight, neg_weight, sparse_spvs):
+    """The coarse loss of the reference (Loss.compute_coarse_loss, losses/loss.py:27-67) on the dense conf_matrix and its
+    0 / 1 ground truth: pos_weight * mean over the positives + neg_weight * mean over the negatives of the focal
+    (-alpha (1 - p)^gamma log p, p the clamped probability of the right answer) or cross-entropy (-log p) term; focal
+    with sparse_spvs keeps the positives only.  A side without entries contributes 0 (the reference lets entry
+    (0, 0, 0) stand in with weight 0)."""
+    if coarse_type not in ('focal', 'cross_entropy'):
+        raise ValueError(f"coarse_type {coarse_type!r}: 'focal' or 'cross_entropy'")
+    c = conf.clamp(1e-6, 1 - 1e-6)
+
+    def side(mask, p, weight):
+        if not bool(mask.any()):
+            return conf.new_zeros(())
+        p = p[mask]
+        term = -p.log() if coarse_type == 'cross_entropy' else -alpha * (1 - p).pow(gamma) * p.log()
+        return weight * term.mean()
+
+    loss = side(conf_gt == 1, c, pos_weight)
+    if coarse_type == 'focal' and sparse_spvs:
+        return loss
+    return loss + side(conf_gt == 0, 1 - c, neg_weight)
+
+
+class FineLoss(nn.Module):
+    """Loss.compute_fine_loss (losses/loss.py:70-98): forward(data) reads mkpts0_f / mkpts1_f [M, 3] = (x, y, std) and
+    expec_f_gt_0 / expec_f_gt_1 [M, 2] (compute_supervision_fine) and returns the training-mode loss.  On the GPU it is
+    ops.fine_loss (HIP forward and backward, no host sync); CPU tensors evaluate the same loss in torch ops (fine_loss_torch)."""
+
+    def forward(self, data):
+        e0, e1, g0, g1 = data['mkpts0_f'], data['mkpts1_f'], data['expec_f_gt_0'], data['expec_f_gt_1']
+        if e0.is_cuda:
+            return ops.fine_loss(e0, e1, g0, g1)
+        return fine_loss_torch(e0, e1, g0, g1)
+
+
+class Loss(nn.Module):
+    """The reference's Loss (losses/loss.py:9-172) with its constructor and data-dict protocol: `config` is the
+    reference's dict (config['module']['loss'][...], config['module']['match_coarse']['sparse_spvs']); forward(data)
+    writes data['loss'] = coarse_weight * loss_c + fine_weight * loss_f and data['loss_scalars'] = {loss_c, loss_f,
+    loss_pose, loss}: 0-dim CPU tensors, fetched by ONE copy of one small device tensor (the reference calls .cpu() per
+    scalar).  The coarse term is CoarseLoss when CoarseMatching(loss_stats=True) left data['_fm_coarse_loss'], else the
+    reference's dense expression on data['conf_matrix'] / data['conf_matrix_gt'].  In eval mode loss_scalars['loss_f']
+    reads tensor(1.) (:137-141).  loss_pose is 0 and not part of the loss (the reference's `loss += loss_pose` is
+    commented out); the pose losses ('old' / 'new') are not implemented."""
+
+    def __init__(self, config):
+        super().__init__()
+        self.config = config
+        self.loss_config = config['module']['loss']
+        self.sparse_spvs = config['module']['match_coarse']['sparse_spvs']
+        self.pose_loss_cal_flag = self.loss_config.get('pose_loss_cal_flag', False)
+        if self.pose_loss_cal_flag in ('old', 'new'):
+            raise NotImplementedError(f"pose_loss_cal_flag {self.pose_loss_cal_flag!r}: the pose losses are not implemented")
+        self.coarse_loss = CoarseLoss(self.loss_config, sparse_spvs=self.sparse_spvs)
+        self.fine_loss = FineLoss()
+
+    def compute_coarse_loss(self, data):
+        if '_fm_coarse_loss' in data:
+            return self.coarse_loss(data)
+        c = self.coarse_loss
+        return coarse_loss_torch(data['conf_matrix'], data['conf_matrix_gt'], c.coarse_type, c.alpha, c.gamma, c.pos_weight,
+                                 c.neg_weight, self.sparse_spvs)
+
+    def forward(self, data):
+        loss_c = self.compute_coarse_loss(data)
+        loss_f = self.fine_loss(data)
+        loss = loss_c * self.loss_config['coarse_weight'] + loss_f * self.loss_config['fine_weight']
+        loss_pose = torch.zeros((), dtype=loss.dtype, device=loss.device)
+        names = ('loss_c', 'loss_f', 'loss_pose', 'loss')
+        vals = torch.stack([v.detach().reshape(()).to(loss.dtype) for v in (loss_c, loss_f, loss_pose, loss)]).cpu()
+        loss_scalars = {k: v.clone() for k, v in zip(names, vals.unbind(0))}
+        if self.training is False:
+            loss_scalars['loss_f'] = torch.tensor(1.)
+        data.update({"loss": loss, "loss_scalars": loss_scalars})
 
 
 class FinePreprocess(nn.Module):

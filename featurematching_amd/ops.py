@@ -594,6 +594,99 @@ def coarse_loss(feat_c0: torch.Tensor, feat_c1: torch.Tensor, b_ids, i_ids, j_id
     return loss
 
 
+def supervise_matches(kp0: torch.Tensor, kp1: torch.Tensor, hw0_c, hw1_c, cell: float = 8) -> dict:
+    """Ground-truth supervision of one image pair from K correspondences kp0 / kp1 [K, 2] = (x, y) in pixels: what the
+    reference's data_preprocess computes on the host with two np.unique calls (datasets/data_preprocessing.py:9-64), in
+    five small HIP launches (fm_supervise_matches).  Per image-1 cell the correspondence with the smallest index
+    survives; the K' survivors come sorted by (cx1, cy1).  Returns i_ids, j_ids (int64 [K']), coarse_kp0/1, fine_kp0/1
+    (float32 [K', 2]), lists_f0/1 (float32 [K']: the ids as the reference keeps them) and the per-cell tables fine_mtx_0
+    [L, 2] / fine_mtx_1 [S, 2] (zero where no survivor lands; of several survivors in one image-0 cell the last wins).
+    One host read: K'.  A point outside its grid (negative, too large, NaN) raises FMatchError (FM_E_RANGE)."""
+    lib = _lib.load()
+    kp0, kp1 = _f32c(kp0, "kp0"), _f32c(kp1, "kp1")
+    if kp0.dim() != 2 or kp0.shape[1] != 2 or kp0.shape != kp1.shape:
+        raise ValueError(f"kp0 / kp1 must both be [K, 2], got {tuple(kp0.shape)} and {tuple(kp1.shape)}")
+    (h0c, w0c), (h1c, w1c) = (int(v) for v in hw0_c), (int(v) for v in hw1_c)
+    dev = kp0.device
+    k = int(kp0.shape[0])
+    cap = max(0, min(k, h1c * w1c))
+    need = int(lib.fm_supervise_workspace_bytes(h0c, w0c, h1c, w1c))
+    if need == 0:
+        raise ValueError(f"coarse grids {hw0_c} / {hw1_c}: positive, at most 2^24 cells each")
+    ws, wsp = _aligned_workspace(need, dev)
+    ids = torch.empty(2, cap, dtype=torch.int64, device=dev)
+    pts = torch.empty(4, cap, 2, dtype=torch.float32, device=dev)
+    lists = torch.empty(2, cap, dtype=torch.float32, device=dev)
+    mtx0 = torch.empty(h0c * w0c, 2, dtype=torch.float32, device=dev)
+    mtx1 = torch.empty(h1c * w1c, 2, dtype=torch.float32, device=dev)
+    count = torch.empty(2, dtype=torch.int32, device=dev)
+    stream = _stream(dev)
+    _lib.check(lib.fm_supervise_matches(_ptr(kp0), _ptr(kp1), k, h0c, w0c, h1c, w1c, float(cell), wsp, need, _ptr(ids[0]),
+                                        _ptr(ids[1]), _ptr(pts[0]), _ptr(pts[1]), _ptr(pts[2]), _ptr(pts[3]),
+                                        _ptr(lists[0]), _ptr(lists[1]), _ptr(mtx0), _ptr(mtx1), cap, _ptr(count), stream),
+               "fm_supervise_matches")
+    m = C.c_int32(0)
+    _lib.check(lib.fm_read_count(_ptr(count), cap, C.byref(m), stream), "fm_supervise_matches")
+    n = m.value
+    return {'i_ids': ids[0, :n], 'j_ids': ids[1, :n], 'coarse_kp0': pts[0, :n], 'coarse_kp1': pts[1, :n],
+            'fine_kp0': pts[2, :n], 'fine_kp1': pts[3, :n], 'lists_f0': lists[0, :n], 'lists_f1': lists[1, :n],
+            'fine_mtx_0': mtx0, 'fine_mtx_1': mtx1}
+
+
+class _FineLoss(torch.autograd.Function):
+    """fm_fine_loss_forward / fm_fine_loss_backward: the forward call's workspace (the reduced scalars) stays on ctx for
+    the backward call."""
+
+    @staticmethod
+    def forward(ctx, expec0, expec1, gt0, gt1, count):
+        lib = _lib.load()
+        e0, e1 = _f32c(expec0, "expec0"), _f32c(expec1, "expec1")
+        g0, g1 = _f32c(gt0, "gt0"), _f32c(gt1, "gt1")
+        m_max, dev = int(e0.shape[0]), e0.device
+        need = int(lib.fm_fine_loss_workspace_bytes(m_max))
+        ws, wsp = _aligned_workspace(need, dev)
+        out = torch.empty(3, dtype=torch.float32, device=dev)
+        _lib.check(lib.fm_fine_loss_forward(_ptr(e0), _ptr(e1), 3, _ptr(g0), _ptr(g1), m_max, _ptr(count), wsp, need,
+                                            _ptr(out), _stream(dev)), "fm_fine_loss_forward")
+        ctx.problem, ctx.keep = (_ptr(e0), _ptr(e1), 3, _ptr(g0), _ptr(g1), m_max, wsp, need), (e0, e1, g0, g1, ws, count)
+        ctx.dtypes = (expec0.dtype, expec1.dtype)
+        ctx.mark_non_differentiable(out)
+        return out[0].clone(), out
+
+    @staticmethod
+    def backward(ctx, grad, _):
+        lib = _lib.load()
+        e0 = ctx.keep[0]
+        d_loss = grad.detach().to(torch.float32).reshape(1).contiguous()
+        d0, d1 = torch.empty_like(e0), torch.empty_like(e0)
+        _lib.check(lib.fm_fine_loss_backward(*ctx.problem, _ptr(d_loss), _ptr(d0), _ptr(d1), _stream(e0.device)),
+                   "fm_fine_loss_backward")
+        d0._keep = (ctx.keep, d_loss)
+        return d0.to(ctx.dtypes[0]), d1.to(ctx.dtypes[1]), None, None, None
+
+
+def fine_loss(expec0: torch.Tensor, expec1: torch.Tensor, gt0: torch.Tensor, gt1: torch.Tensor,
+              count: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """What the reference's Loss.compute_fine_loss(expec_f_0, expec_f_1, expec_f_gt_0, expec_f_gt_1) returns in training
+    mode (losses/loss.py:70-98), as a differentiable function of expec0 / expec1 [M, 3] = (x, y, std); gt0 / gt1 [M, 2].
+    No host sync: whether expec0 sums to exactly 0 (then the loss is 0 with zero gradients) and which rows have gt x != 0
+    are decided on the device; when no row has, the loss is NaN as in the reference.  The std column gets zero gradient
+    (the weights are detached).  M = 0 returns 0 without a HIP launch (a zero that still has both inputs' graph).  `count`: optional device int32 row count (rows at or
+    beyond min(count, M) are ignored and get zero gradients).  The returned scalar carries `.terms` = (loss_0, loss_1)."""
+    if expec0.dim() != 2 or expec0.shape[1] != 3 or expec1.shape != expec0.shape:
+        raise ValueError(f"expec0 / expec1 must both be [M, 3], got {tuple(expec0.shape)} and {tuple(expec1.shape)}")
+    m = expec0.shape[0]
+    if tuple(gt0.shape) != (m, 2) or tuple(gt1.shape) != (m, 2):
+        raise ValueError(f"gt0 / gt1 must be [{m}, 2], got {tuple(gt0.shape)} and {tuple(gt1.shape)}")
+    if m == 0:
+        if not expec0.is_cuda:
+            raise RuntimeError("expec0 must live on the GPU: the HIP path has no CPU fallback")
+        return (expec0.sum() + expec1.sum()).float() * 0         # 0, attached to the graph of both inputs; no HIP launch
+    loss, out = _FineLoss.apply(expec0, expec1, gt0, gt1, count)
+    loss.terms = out[1:]
+    return loss
+
+
 def gather_windows(feat_f: torch.Tensor, b_ids: torch.Tensor, ids: torch.Tensor, w: int, stride: int,
                    w_c: int, pad: int = 2, count: Optional[torch.Tensor] = None,
                    out: Optional[torch.Tensor] = None, cells=None, h_c: Optional[int] = None) -> torch.Tensor:

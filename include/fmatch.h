@@ -621,6 +621,61 @@ int fm_coarse_loss_backward(const float* feat0, const float* feat1, int N, int L
                             const int64_t* b_ids, const int64_t* i_ids, const int64_t* j_ids, int K, void* workspace,
                             size_t workspace_bytes, const float* d_loss, float* d_feat0, float* d_feat1, void* stream);
 
+/*
+ * Ground-truth supervision from K correspondences (the reference's data_preprocess, datasets/data_preprocessing.py:9-64,
+ * without its two host round trips).  kp0 / kp1 [dev] float32 [K, 2] = (x, y) in pixels, 8-byte aligned; the coarse grids
+ * (h0c, w0c), (h1c, w1c); `cell` the cell size in pixels (8 in the reference).  Cell = floor(coord / cell) per axis.
+ *   - Of all correspondences in one image-1 cell the one with the SMALLEST input index survives.
+ *   - Survivors are emitted sorted by (cx1, cy1), cx1 the major key (np.unique(axis=0)'s order - not the order of j).
+ *   - Survivor t: i_ids[t] = cx0 + cy0 w0c, j_ids[t] = cx1 + cy1 w1c (int64); coarse_kp0/1[t] = cell index * cell;
+ *     fine_kp0/1[t] = the original points; lists_f0/1[t] = i, j as float32 (exact: a grid has at most 2^24 cells).  All
+ *     [dev], `cap` rows, cap >= min(K, S).
+ *   - fine_mtx_0 [L, 2], fine_mtx_1 [S, 2] (L = h0c w0c, S = h1c w1c): zero, then fine_mtx_1[j_t] = fine_kp1[t] (the j are
+ *     distinct) and fine_mtx_0[i_t] = fine_kp0[t]; where several survivors share an i, the one with the LARGEST t wins.
+ *   - d_count [dev] int32 [2] = {K', status} as fm_coarse_match leaves it: read it with fm_read_count.  A point whose cell
+ *     lies outside its grid (negative, too large, NaN) sets FM_DEV_RANGE (fm_read_count: FM_E_RANGE) and is left out;
+ *     nothing is wrapped or clamped.
+ * Integer atomics only (min of the input index per image-1 cell, max of t per image-0 cell): every output is the same
+ * bits on every run.  workspace: fm_supervise_workspace_bytes bytes [dev], 256-byte aligned (0 for an invalid grid).  No
+ * host synchronisation.  K = 0 is valid (kp0 / kp1 and, with cap = 0, the per-survivor outputs may be NULL): K' = 0 and zero tables.
+ * Statuses: FM_E_NULL, FM_E_SHAPE (K < 0, non-positive grid, cap < min(K, S)), FM_E_UNSUPPORTED (a grid of more than
+ * 2^24 cells, cell <= 0 or not finite), FM_E_WORKSPACE, a hipError_t.
+ */
+size_t fm_supervise_workspace_bytes(int h0c, int w0c, int h1c, int w1c);
+int fm_supervise_matches(const float* kp0, const float* kp1, int K, int h0c, int w0c, int h1c, int w1c, float cell,
+                         void* workspace, size_t workspace_bytes, int64_t* i_ids, int64_t* j_ids, float* coarse_kp0,
+                         float* coarse_kp1, float* fine_kp0, float* fine_kp1, float* lists_f0, float* lists_f1,
+                         float* fine_mtx_0, float* fine_mtx_1, int cap, int32_t* d_count, void* stream);
+
+/*
+ * The reference's fine loss (Loss.compute_fine_loss, losses/loss.py:70-98) and its gradient.  expec0 / expec1 [dev]
+ * float32, row m at expec + m * row_stride = (x, y, std) (row_stride >= 3 floats); gt0 / gt1 [dev] float32 [m_max, 2],
+ * 8-byte aligned; d_count [dev] may be NULL as in fm_fine_match: rows at or beyond min(*d_count, m_max) are not read.
+ * Per image, inv_m = 1 / max(std_m, 1e-10), nz = {m : gt[m, 0] != 0}, M = the rows counted:
+ *     loss_d = sum_{m in nz} (|xy_m - gt_m|^2 / 49) inv_m / ((sum_all inv / M) |nz|),     loss_f = loss_0 + loss_1
+ * If the sum of ALL entries of expec0 is exactly 0 (loss.py:72-75; decided on the device), loss_f = 0 with zero
+ * gradients.  The sum is taken in double, the reference's in float32: entries that are not all zero and cancel only
+ * through float32 rounding make the reference return 0 where this call computes the loss (entries that cancel exactly,
+ * +a and -a, give 0 in both).  An empty nz gives NaN, as the reference's mean of an empty set; m_max = 0 gives 0
+ * without a launch.
+ *   fm_fine_loss_forward  : loss_out [dev] float32 [3] = {loss_f, loss_0, loss_1}.  Per-workgroup sums in double from
+ *                           the first addition, folded in a fixed order: the same bits on every run.  Two launches.
+ *   fm_fine_loss_backward : d_expec0 / d_expec1 [dev] float32 [m_max, 3], EVERY row written:
+ *                             d expec[m, :2] = d_loss[0] 2 (xy_m - gt_m) / 49 inv_m / ((sum_all inv / M) |nz|) for m in nz,
+ *                           0 for every other row and, the weights being detached, exactly 0 in the std column.  d_loss
+ *                           [dev] float32 [1] is read on the device.  Same arguments as the forward call and ITS
+ *                           workspace, untouched since (the reduced scalars and the row count are read from it).  One launch.
+ * workspace: fm_fine_loss_workspace_bytes(m_max) bytes [dev], 256-byte aligned (0 for m_max < 0).  No atomics, no host
+ * synchronisation.  Statuses: FM_E_NULL, FM_E_SHAPE (m_max < 0, row_stride < 3), FM_E_WORKSPACE, a hipError_t.
+ */
+size_t fm_fine_loss_workspace_bytes(int m_max);
+int fm_fine_loss_forward(const float* expec0, const float* expec1, int row_stride, const float* gt0, const float* gt1,
+                         int m_max, const int32_t* d_count, void* workspace, size_t workspace_bytes, float* loss_out,
+                         void* stream);
+int fm_fine_loss_backward(const float* expec0, const float* expec1, int row_stride, const float* gt0, const float* gt1,
+                          int m_max, void* workspace, size_t workspace_bytes, const float* d_loss, float* d_expec0,
+                          float* d_expec1, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,11 +23,9 @@
 #include <type_traits>
 
 #include "fm_device.h"
+#include "fm_wave_device.h"
 
 namespace fm {
-
-typedef _Float16 half8d __attribute__((ext_vector_type(8)));
-typedef float f32x16d __attribute__((ext_vector_type(16)));
 
 constexpr int kDenseQueue = 64;       // candidates a wave parks in LDS (one per lane at the hand-over)
 constexpr int kDenseRing = 4;         // units of the LDS ring
@@ -44,32 +42,6 @@ struct DenseArgs {
   int L, S, Lp, Sp, panels, units, splits, units_per_split, slots, pgroup;
   float k, lt;
 };
-
-__device__ __forceinline__ int xcd_remap_d(int bid, int n) {
-  const int q = n >> 3, rem = n & 7, x = bid & 7, y = bid >> 3;
-  return (x < rem ? x * (q + 1) : rem * (q + 1) + (x - rem) * q) + y;
-}
-template <int CTRL, int BANK>
-__device__ __forceinline__ float dpp_mov_d(float old, float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, old), __builtin_bit_cast(int, v),
-                                                               CTRL, 0xf, BANK, false));
-}
-// sum over the 32 lanes that share lane >> 5, result in every lane of the half; DPP only (fixed order)
-__device__ __forceinline__ float half_sum32_d(float v) {
-  v = v + dpp_mov_d<0xB1, 0xf>(v, v);
-  v = v + dpp_mov_d<0x4E, 0xf>(v, v);
-  { float t = dpp_mov_d<0x104, 0x5>(v, v); t = dpp_mov_d<0x114, 0xA>(t, v); v = v + t; }
-  v = v + dpp_mov_d<0x128, 0xf>(v, v);
-  { float p = v, q = v; asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(p), "+v"(q)); v = p + q; }
-  return v;
-}
-__device__ __forceinline__ float halves_sum_d(float v) {      // lane l + lane l ^ 32
-  float p = v, q = v;
-  asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(p), "+v"(q));
-  return p + q;
-}
-template <typename T>
-__device__ __forceinline__ unsigned lds_addr_d(T* p) { return (unsigned)(size_t)(__attribute__((address_space(3))) T*)p; }
 
 // CONF (round 4): the same sweep writes data['conf_matrix'] (coarse_matching_new.py:68,70) for EVERY sample instead of
 // forming sums and candidates - conf = exp2(k x + nmr2_i) * exp2(k x + nmc2_j) with the log-softmax offsets of
@@ -120,7 +92,7 @@ __global__ __launch_bounds__(512) void k_dense(DenseArgs a) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = lane & 31, h = lane >> 5;
-  int kk = xcd_remap_d(blockIdx.x, gridDim.x);
+  int kk = xcd_contiguous(blockIdx.x, gridDim.x);
   const int per_sample = a.panels * a.splits;
   const int b = kk / per_sample;
   kk -= b * per_sample;
@@ -137,8 +109,8 @@ __global__ __launch_bounds__(512) void k_dense(DenseArgs a) {
   const float kq = a.k * inv_sc;                    // accumulator -> log2-domain similarity
   const char* plane_hi = reinterpret_cast<const char*>(a.hi1 + (long)b * a.Sp * C);
   const char* plane_lo = reinterpret_cast<const char*>(a.lo1 + (long)b * a.Sp * C);
-  const unsigned ring_a = lds_addr_d(smem), meta_a = lds_addr_d(s_meta), colred_a = lds_addr_d(s_colred);
-  const unsigned qkey_a = lds_addr_d(s_qkey + wv * kDenseQueue), qx_a = lds_addr_d(s_qx + wv * kDenseQueue);
+  const unsigned ring_a = lds_addr(smem), meta_a = lds_addr(s_meta), colred_a = lds_addr(s_colred);
+  const unsigned qkey_a = lds_addr(s_qkey + wv * kDenseQueue), qx_a = lds_addr(s_qx + wv * kDenseQueue);
 
   // one unit = 2 * KSTEPS pieces of 1 KiB ((plane, k-step): the 64 lanes of an MFMA operand fragment), contiguous in
   // the fragment-major planes; the waves take the pieces round robin; wave 0 also brings the unit's 32 column stabilisers
@@ -165,13 +137,13 @@ __global__ __launch_bounds__(512) void k_dense(DenseArgs a) {
   // -stabiliser*log2e of row wrow0 + (lane & 31) (both halves hold it), requested AHEAD of the A fragments: older in the
   // vmcnt order, so picking the rows' values out of it below does not wait for them
   const float nv = a.nmr[(long)b * a.Lp + wrow0 + r];
-  half8d ahi[KSTEPS], alo[KSTEPS];
+  half8 ahi[KSTEPS], alo[KSTEPS];
   {
     const long off = (((long)b * a.Lp + wrow0) / 32 * KSTEPS * 64 + lane) * 8;
 #pragma unroll
     for (int ks = 0; ks < KSTEPS; ++ks) {
-      ahi[ks] = *reinterpret_cast<const half8d*>(a.hi0 + off + ks * 512);
-      if constexpr (!LITE) alo[ks] = *reinterpret_cast<const half8d*>(a.lo0 + off + ks * 512);
+      ahi[ks] = *reinterpret_cast<const half8*>(a.hi0 + off + ks * 512);
+      if constexpr (!LITE) alo[ks] = *reinterpret_cast<const half8*>(a.lo0 + off + ks * 512);
     }
   }
   float nmsel[16];                                  // ... of this lane's 16 rows (accumulator register g: row (g&3) + 8 (g>>2) + 4 h)
@@ -219,7 +191,7 @@ __global__ __launch_bounds__(512) void k_dense(DenseArgs a) {
     colout[u * 32 + lane] = cv;
   };
 
-  f32x16d accC;                                     // the accumulators of the unit whose epilogue is due
+  f32x16 accC;                                      // the accumulators of the unit whose epilogue is due
   float nmc_c = 0.f;                                // its column stabiliser (this lane's column)
 #pragma unroll
   for (int g = 0; g < 16; ++g) accC[g] = 0.f;
@@ -227,7 +199,7 @@ __global__ __launch_bounds__(512) void k_dense(DenseArgs a) {
   // one pass: the MFMA chain of unit `un` (when DN) with the epilogue of unit `uc` (when DC) sliced between its k-steps
   auto pass = [&](auto dn, auto dc, int un, int uc) {
     constexpr bool DN = decltype(dn)::value, DC = decltype(dc)::value;
-    f32x16d accN;
+    f32x16 accN;
     float nmc_n = 0.f;
     float cstat = 0.f;
     unsigned bm = 0;                                  // this lane's candidate registers of unit uc: bit 15 - g
@@ -254,10 +226,10 @@ __global__ __launch_bounds__(512) void k_dense(DenseArgs a) {
     const unsigned base = ring_a + ((un - u0) % kDenseRing) * UNIT_BYTES + lane * 16;
     constexpr int PF = KSTEPS < 3 ? KSTEPS - 1 : 2;      // B-fragment read-ahead (k-steps): LDS latency under 8 waves' reads
     constexpr int RING = PF + 1;                         // is ~300 cycles, a k-step of this wave ~150
-    half8d bh[RING], bl[RING];
+    half8 bh[RING], bl[RING];
     // (a capture-less lambda with explicit operands: hipcc does not let a generic lambda nested in a generic lambda
     // capture the enclosing one's arrays)
-    auto issue_ = [](auto ksc, half8d (&bh_)[RING], half8d (&bl_)[RING], unsigned base_) {
+    auto issue_ = [](auto ksc, half8 (&bh_)[RING], half8 (&bl_)[RING], unsigned base_) {
       constexpr int ks = decltype(ksc)::value;
       asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(bh_[ks % RING]) : "v"(base_), "i"(ks * 1024));
       if constexpr (!LITE) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(bl_[ks % RING]) : "v"(base_), "i"(PLANE + ks * 1024));
@@ -278,7 +250,7 @@ __global__ __launch_bounds__(512) void k_dense(DenseArgs a) {
         if (ks == 0) {
           // The accumulator starts at 0, or at -inf for padded rows (>= L) / padded columns (>= S): such entries stay
           // -inf through the whole chain, so the epilogue needs no masks (exp2 gives 0, the candidate test fails)
-          f32x16d z;
+          f32x16 z;
 #pragma unroll
           for (int g = 0; g < 16; ++g) z[g] = 0.f;
           if (row_edge || un * 32 + 32 > a.S) {
@@ -399,7 +371,7 @@ __global__ __launch_bounds__(512) void k_dense(DenseArgs a) {
     }
     if (DC && !CONF) {
       if constexpr (SUMS) {
-        cstat = halves_sum_d(cstat);                // this wave's 32 rows of column r
+        cstat = pair_op<32, OpAdd>(cstat);          // lane l + lane l ^ 32: this wave's 32 rows of column r
         if (h == 0) asm volatile("ds_write_b32 %0, %1" ::"v"(colred_a + ((((uc - u0) % 3) * 8 + wv) * 32 + r) * 4), "v"(cstat) : "memory");
       }
       {
@@ -507,7 +479,7 @@ __global__ __launch_bounds__(512) void k_dense(DenseArgs a) {
   // ---- row sums of this workgroup's column range: reduce over the 32 lanes of each half ----
   if constexpr (SUMS) {
 #pragma unroll
-    for (int g = 0; g < 16; ++g) rstat[g] = half_sum32_d(rstat[g]);
+    for (int g = 0; g < 16; ++g) rstat[g] = half_all<OpAdd>(rstat[g]);
     if (r == 0) {
       float* out = a.rowpart + ((long)b * a.splits + split) * a.Lp + wrow0 + 4 * h;
 #pragma unroll

@@ -65,7 +65,7 @@ __device__ __forceinline__ void loss_term(float a, float b, const LossParams& p,
   }
 }
 
-// Folds the 16 partial sums of a dot product as row_sum16_g (dsm_grad.hip) does across 16 lanes - pairs, quads, halves,
+// Folds the 16 partial sums of a dot product as row_sum16 (fm_wave_device.h) does across 16 lanes - pairs, quads, halves,
 // all: a balanced tree, every level commutative - when they arrive one after the other: lv is a binary counter of
 // finished subtrees, x the result after l = 15.  (l is uniform: scalar branches, lv stays in registers.)
 __device__ __forceinline__ void dot_fold(int l, float s, float (&lv)[4], float& x) {

@@ -23,11 +23,9 @@
 #include <type_traits>
 
 #include "fm_device.h"
+#include "fm_wave_device.h"
 
 namespace fm {
-
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v16i __attribute__((ext_vector_type(16)));
 
 struct MaxArgs {
   const signed char* q0; const signed char* q1;
@@ -38,13 +36,10 @@ struct MaxArgs {
   int L, S, Lp, Sp, panels, tiles, splits, tiles_per_split, pgroup;
 };
 
-__device__ __forceinline__ int xcd_remap_m(int bid, int n) {
-  const int q = n >> 3, rem = n & 7, x = bid & 7, y = bid >> 3;
-  return (x < rem ? x * (q + 1) : rem * (q + 1) + (x - rem) * q) + y;
-}
-// max over the 32 lanes that share lane>>5; valid in lanes 16..31 / 48..63.  One v_max_i32 with a DPP operand per
-// step (hipcc keeps v_mov_b32_dpp + v_max apart when written with the update_dpp builtin): xor 1, xor 2, half mirror
-// and mirror reduce every row of 16 lanes, row_bcast:15 hands row 0's result to row 1 (and row 2's to row 3).
+// max over the 32 lanes that share lane>>5; valid in lanes 16..31 / 48..63.  Not the shared half_all<OpMax>: a
+// hand-scheduled chain whose result only the upper rows need.  One v_max_i32 with a DPP operand per step (hipcc
+// keeps v_mov_b32_dpp + v_max apart when written with the update_dpp builtin): xor 1, xor 2, half mirror and mirror
+// reduce every row of 16 lanes, row_bcast:15 hands row 0's result to row 1 (and row 2's to row 3).
 // s_nop 1: the two wait states between a VALU write and a DPP read of the same register.
 __device__ __forceinline__ int half_max32_hi_i(int v) {
   asm volatile("s_nop 1\n\tv_max_i32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
@@ -63,11 +58,6 @@ __device__ __forceinline__ int vmax3_i(int x, int y, int z) {
   int d;
   asm volatile("v_max3_i32 %0, %1, %2, %3" : "=v"(d) : "v"(x), "v"(y), "v"(z));
   return d;
-}
-__device__ __forceinline__ int halves_max_i(int v) {
-  int p = v, q = v;
-  asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(p), "+v"(q));
-  return max(p, q);
 }
 
 #ifndef FM_MAX_EPI
@@ -111,7 +101,7 @@ __global__ __launch_bounds__(256, 2) void k_max_i8(MaxArgs a) {
 
   // workgroup order: sample, groups of a.pgroup panels, split-major inside a group, through the bijective XCD
   // remap - one XCD's share is a compact (panels x splits) block (speed only)
-  int kk = xcd_remap_m(blockIdx.x, gridDim.x);
+  int kk = xcd_contiguous(blockIdx.x, gridDim.x);
   const int per_sample = a.panels * a.splits;
   const int b = kk / per_sample;
   kk -= b * per_sample;
@@ -368,8 +358,8 @@ __global__ __launch_bounds__(256, 2) void k_max_i8(MaxArgs a) {
       if (s < 8) T(ac0, ta, s);
       if (s >= 4 && s < 12) T(ac1, tb, s - 4);
       if (!(FM_MAX_EPI & 2)) { if (s == 15) { vmax_i(rstat0[1], ta[7]); vmax_i(rstat1[1], tb[7]); } return; }
-      if (s == 8) c0 = halves_max_i(ta[7]);                           // this lane's column over row block 0
-      if (s == 12) c1 = halves_max_i(tb[7]);                          // ... over row block 1
+      if (s == 8) c0 = pair_op<32, OpMax>(ta[7]);                     // this lane's column over row block 0
+      if (s == 12) c1 = pair_op<32, OpMax>(tb[7]);                    // ... over row block 1
       if (s == 13) {
         // the 4 waves' maxima of a column meet in LDS (both halves of the wave hold the same value: no lane mask)
         asm volatile("ds_max_u32 %0, %1" ::"v"(colmax_a + ((((uc >> 1) - t0) % 3) * 64 + (uc & 1) * 32 + r) * 4),

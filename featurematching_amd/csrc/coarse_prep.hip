@@ -11,10 +11,9 @@
 // MFMA rate (dense sum kernel).  Screening (row / column / unit maxima, which units and entries matter) runs on
 // the int8 plane at twice that rate and half the bytes, with the rigorous quantisation margin of fm_device.h.
 #include "fm_device.h"
+#include "fm_wave_device.h"
 
 namespace fm {
-
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 
 struct PrepArgs {
   const void* src0; const void* src1; int in_dtype;      // FM_F32 / FM_F16 / FM_BF16 rows [N, rows, c_in]
@@ -234,18 +233,13 @@ __global__ __launch_bounds__(256) void k_prep_split(PrepArgs a) {
     *reinterpret_cast<int4*>(qp + off) = make_int4(wq[0], wq[1], wq[2], wq[3]);
     if (PLANES) {      // the two 8-channel chunks of this 16-channel chunk, in k_prep_f16's layout and arithmetic
       constexpr int KSTEPS = C / 16;
-      typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 #pragma unroll
       for (int c8 = 0; c8 < 2; ++c8) {
         const float x[8] = {v[2 * c8].x, v[2 * c8].y, v[2 * c8].z, v[2 * c8].w,
                             v[2 * c8 + 1].x, v[2 * c8 + 1].y, v[2 * c8 + 1].z, v[2 * c8 + 1].w};
         half8 hh, ll;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float xs = x[e] * sc16;
-          hh[e] = (_Float16)xs;
-          ll[e] = (_Float16)(xs - (float)hh[e]);
-        }
+        for (int e = 0; e < 8; ++e) split_f16(x[e] * sc16, hh, ll, e);
         const int q8 = 2 * q16 + c8;
         const int h2 = q8 / KSTEPS, ks2 = q8 - h2 * KSTEPS;
         const long off2 = (((rb * KSTEPS + ks2) * 2 + h2) * 32 + r) * 8;
@@ -372,14 +366,9 @@ __global__ __launch_bounds__(256) void k_prep_f16(PrepArgs a) {
       }
     }
     const float x[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-    typedef _Float16 half8 __attribute__((ext_vector_type(8)));
     half8 hh, ll;
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const float xs = x[e] * sc;
-      hh[e] = (_Float16)xs;
-      ll[e] = (_Float16)(xs - (float)hh[e]);
-    }
+    for (int e = 0; e < 8; ++e) split_f16(x[e] * sc, hh, ll, e);
     const int h = q / KSTEPS, ks = q - h * KSTEPS;
     const long off = (((rb * KSTEPS + ks) * 2 + h) * 32 + r) * 8;
     *reinterpret_cast<half8*>(hi + off) = hh;

@@ -33,11 +33,9 @@
 #include <type_traits>
 
 #include "fm_device.h"
+#include "fm_wave_device.h"
 
 namespace fm {
-
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v16i __attribute__((ext_vector_type(16)));
 
 constexpr int kMaxExact = 24;         // significant entries of a unit resolved by exact dot products; more -> dense kernel
 
@@ -58,48 +56,6 @@ struct ScreenArgs {
   int allow_dead;                                      // 0: every row / column keeps its stabiliser and its full sum (conf_matrix)
   float k, lt, inv_ct, cpad;
 };
-
-__device__ __forceinline__ int xcd_remap_s(int bid, int n) {
-  const int q = n >> 3, rem = n & 7, x = bid & 7, y = bid >> 3;
-  return (x < rem ? x * (q + 1) : rem * (q + 1) + (x - rem) * q) + y;
-}
-
-template <int CTRL, int BANK>
-__device__ __forceinline__ float dpp_mov_s(float old, float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, old), __builtin_bit_cast(int, v),
-                                                               CTRL, 0xf, BANK, false));
-}
-// maximum over the 32 lanes that share lane >> 5 (every lane of the half ends with it)
-__device__ __forceinline__ float half_reduce32_max(float v) {
-  v = fmaxf(v, dpp_mov_s<0xB1, 0xf>(v, v));                                                       // lane ^ 1
-  v = fmaxf(v, dpp_mov_s<0x4E, 0xf>(v, v));                                                       // lane ^ 2
-  { float t = dpp_mov_s<0x104, 0x5>(v, v); t = dpp_mov_s<0x114, 0xA>(t, v); v = fmaxf(v, t); }   // lane ^ 4
-  v = fmaxf(v, dpp_mov_s<0x128, 0xf>(v, v));                                                      // lane ^ 8
-  { float p = v, q = v; asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(p), "+v"(q)); v = fmaxf(p, q); }
-  return v;
-}
-// minimum over the 32 lanes that share lane >> 5, integers (the same steps)
-__device__ __forceinline__ int half_reduce32_min_i(int v) {
-  auto mv = [](auto ctrl, auto bank, int old, int x) {
-    return __builtin_amdgcn_update_dpp(old, x, decltype(ctrl)::value, 0xf, decltype(bank)::value, false);
-  };
-  using std::integral_constant;
-  v = min(v, mv(integral_constant<int, 0xB1>{}, integral_constant<int, 0xf>{}, v, v));
-  v = min(v, mv(integral_constant<int, 0x4E>{}, integral_constant<int, 0xf>{}, v, v));
-  { int t = mv(integral_constant<int, 0x104>{}, integral_constant<int, 0x5>{}, v, v);
-    t = mv(integral_constant<int, 0x114>{}, integral_constant<int, 0xA>{}, t, v); v = min(v, t); }
-  v = min(v, mv(integral_constant<int, 0x128>{}, integral_constant<int, 0xf>{}, v, v));
-  { int p = v, q = v; asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(p), "+v"(q)); v = min(p, q); }
-  return v;
-}
-// sum over the 16 lanes of a DPP row, in a fixed order (every lane of the row ends with the same bits)
-__device__ __forceinline__ float row_sum16(float v) {
-  v = v + dpp_mov_s<0xB1, 0xf>(v, v);            // quad_perm [1,0,3,2]
-  v = v + dpp_mov_s<0x4E, 0xf>(v, v);            // quad_perm [2,3,0,1]
-  v = v + dpp_mov_s<0x141, 0xf>(v, v);           // row_half_mirror
-  v = v + dpp_mov_s<0x140, 0xf>(v, v);           // row_mirror
-  return v;
-}
 
 // Integer significance threshold: an entry with integer screening product q can matter for a row / column whose
 // -stabiliser*log2e is nm iff  kss q + emu + nm > -kSkipLog2  <=>  q > (-kSkipLog2 - emu - nm) / kss.
@@ -230,8 +186,8 @@ __global__ __launch_bounds__(256) void k_thresh(ScreenArgs a, RowsExtra x) {
   (side ? a.nmc : a.nmr)[g] = nm;
   const int thr = idx < len ? sig_threshold(nm, emu, inv_kss) : 0x3fffffff;
   (side ? x.thr_c : x.thr_r)[g] = thr;
-  const float bm = half_reduce32_max(nm);
-  const int tm = half_reduce32_min_i(thr);
+  const float bm = half_all<OpMax>(nm);
+  const int tm = half_all<OpMin>(thr);
   if ((lane & 31) == 0) {
     (side ? x.cmaxu : x.wmaxb)[(long)b * nblk + blk] = bm;
     (side ? x.tmin_c : x.tmin_r)[(long)b * nblk + blk] = tm;
@@ -252,7 +208,7 @@ __global__ __launch_bounds__(256, 3) void k_screen_rows(ScreenArgs a, RowsExtra 
   // chunk: their live units overlap (L1 / L2 hits on the B fragments); through the bijective XCD remap one XCD's share
   // is a contiguous range of items, i.e. one or two samples at a time
   const int nrb = a.Lp / 32, nunits = a.Sp / 32;
-  const int item = xcd_remap_s(blockIdx.x, gridDim.x) * 4 + wv;
+  const int item = xcd_contiguous(blockIdx.x, gridDim.x) * 4 + wv;
   if (item >= x.items) return;                      // (wave-uniform; the kernel has no barrier)
   const int per_sample = nrb * x.nchunks;
   const int b = item / per_sample;

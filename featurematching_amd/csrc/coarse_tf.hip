@@ -39,6 +39,7 @@
 #include <type_traits>
 
 #include "fm_internal.h"
+#include "fm_wave_device.h"
 #include "fmatch.h"
 
 namespace {
@@ -59,11 +60,6 @@ constexpr size_t kFragQ = 0, kFragK = 65536 * 4, kFragV = 2 * 65536 * 4, kFragM 
 constexpr int kHdrLn = 0, kHdrWinv = 4 * kD, kHdrMsgBound = kHdrWinv + 6, kHdrAbsmax = kHdrMsgBound + 1, kHdrFloats = kHdrAbsmax + 6 + 3;
 constexpr size_t kLayerBytes = kFragEnd + (size_t)kHdrFloats * 4;
 static_assert(kLayerBytes % 16 == 0, "layer stride keeps the fragments 16-byte aligned");
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 
 struct Seg {
   const float* x;        // [N, L, 256] tokens this launch reads (k_ctx_kv: the SOURCE; k_ctx_layer: the image updated)
@@ -126,11 +122,7 @@ __global__ void k_ctx_pack16(const float* __restrict__ w, int n_out, int K, cons
   const float* row = w + (size_t)(32 * rb + (lane & 31)) * K + 16 * c + 8 * (lane >> 5);
   half8 hi, lo;
 #pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const float v = row[e] * s;
-    hi[e] = (_Float16)v;
-    lo[e] = (_Float16)(v - (float)hi[e]);
-  }
+  for (int e = 0; e < 8; ++e) split_f16(row[e] * s, hi, lo, e);
   half8* o = dst + (size_t)(i >> 6) * 128 + lane;
   o[0] = hi;
   o[64] = lo;
@@ -154,6 +146,7 @@ __global__ void k_ctx_pack_ln(const float* g1, const float* b1, const float* g2,
 }
 
 __device__ __forceinline__ float elu1(float x) { return x > 0.f ? x + 1.0f : __expf(x); }     // elu(x) + 1
+// v(lane ^ 32) by ds_bpermute (what __shfl_xor compiles to), not by pair_op<32>'s permlane swap as in fine_tf.hip
 __device__ __forceinline__ float other_half(float v) { return __shfl_xor(v, 32); }
 
 // ------------------------------------------------------------------------------------------------ the split product
@@ -261,10 +254,7 @@ __device__ __forceinline__ void store_planes(char* hi, int lo_off, int rbg, cons
   for (int q = 0; q < 4; ++q) {
     half4 h4, l4;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      h4[e] = (_Float16)v[4 * q + e];
-      l4[e] = (_Float16)(v[4 * q + e] - (float)h4[e]);
-    }
+    for (int e = 0; e < 4; ++e) split_f16(v[4 * q + e], h4, l4, e);
     char* o = p + (q >> 1) * 1024 + (q & 1) * 512;
     *reinterpret_cast<half4*>(o) = h4;
     *reinterpret_cast<half4*>(o + lo_off) = l4;
@@ -307,11 +297,7 @@ __device__ __forceinline__ void load_tile(const float* __restrict__ x, int tok0,
     const int j = g + NG * i;                 // channels 8j .. 8j+7 = k-step j >> 1, half j & 1: one 16-byte slot
     half8 h8, l8;
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const float xs = (e < 4 ? v[i][0][e] : v[i][1][e - 4]) * s;
-      h8[e] = (_Float16)xs;
-      l8[e] = (_Float16)(xs - (float)h8[e]);
-    }
+    for (int e = 0; e < 8; ++e) split_f16((e < 4 ? v[i][0][e] : v[i][1][e - 4]) * s, h8, l8, e);
     char* o = hi + (size_t)(j >> 1) * 1024 + (j & 1) * 512 + tok * 16;
     *reinterpret_cast<half8*>(o) = h8;
     *reinterpret_cast<half8*>(o + lo_off) = l8;

@@ -18,21 +18,9 @@
 // float32 vector arithmetic on purpose: a training-only path whose bar is the agreement with float64 autograd
 // (tests), not the matrix cores.
 #include "fm_sweep_device.h"
+#include "fm_wave_device.h"
 
 namespace fm {
-
-template <int CTRL, int BANK>
-__device__ __forceinline__ float dpp_mov_g(float old, float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, old), __builtin_bit_cast(int, v),
-                                                               CTRL, 0xf, BANK, false));
-}
-__device__ __forceinline__ float row_sum16_g(float v) {      // sum over the 16 lanes of a DPP row, fixed order
-  v = v + dpp_mov_g<0xB1, 0xf>(v, v);
-  v = v + dpp_mov_g<0x4E, 0xf>(v, v);
-  v = v + dpp_mov_g<0x141, 0xf>(v, v);
-  v = v + dpp_mov_g<0x140, 0xf>(v, v);
-  return v;
-}
 
 // conf at K entries: 16 lanes per entry (16 channels per lane, four 16-byte loads per row), the exact float32 dot
 // product in a fixed order - the arithmetic of k_screen's exact phase.
@@ -61,7 +49,7 @@ __global__ __launch_bounds__(256) void k_conf_at(const float* __restrict__ f0, c
     s = __builtin_fmaf(az.z, bb.z, s);
     s = __builtin_fmaf(az.w, bb.w, s);
   }
-  const float x = row_sum16_g(s);
+  const float x = row_sum16(s);
   if (l16 == 0 && e < K) {
     conf[e] = (__builtin_amdgcn_exp2f(__builtin_fmaf(x, k2, nm_r[b * pitch_r + i])) / sum_r[b * pitch_r + i]) *
               (__builtin_amdgcn_exp2f(__builtin_fmaf(x, k2, nm_c[b * pitch_c + j])) / sum_c[b * pitch_c + j]);
@@ -273,7 +261,7 @@ __global__ __launch_bounds__(256) void k_exact_lists(const void* __restrict__ f0
       s = __builtin_fmaf(a.z, bb.z, s);
       s = __builtin_fmaf(a.w, bb.w, s);
     }
-    const float x = row_sum16_g(s);
+    const float x = row_sum16(s);
     if (l16 == 0) {
       float* xs = side ? cx : rx;
       const float nm = (side ? nm_c : nm_r)[gl];

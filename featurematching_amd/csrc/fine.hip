@@ -6,14 +6,6 @@
 
 namespace fm {
 
-// Workgroups are dealt round-robin over the 8 XCDs (private L2s).  Give each XCD a contiguous range
-// of windows: matches are sorted by coarse cell, so neighbouring windows share cache lines of the
-// fine map and one XCD then pulls only its part of the map over the fabric (speed only).
-__device__ __forceinline__ int xcd_contiguous(int bid, int n) {
-  const int q = n >> 3, rem = n & 7, x = bid & 7, y = bid >> 3;
-  return (x < rem ? x * (q + 1) : rem * (q + 1) + (x - rem) * q) + y;
-}
-
 // ----------------------------------------------------------------------------------------
 // Window crop for NCHW maps with Cf = 64 (W compile-time): ONE WAVE PER WINDOW, four windows per
 // workgroup, no workgroup barrier.
@@ -29,9 +21,6 @@ __device__ __forceinline__ int xcd_contiguous(int bid, int n) {
 // (One workgroup per window, 3776 four-wave workgroups at 640x480, was bound by workgroup launch
 // rate: its time followed the number of workgroups, not the bytes.)
 // ----------------------------------------------------------------------------------------
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 // In-place context merge of one window tile in LDS (fine_preprocess.py:56-59, the window half of
 // merge_feat): tile[r][n] <- sum_k W_w[n][k] * tile[r][k] + ctx[n], r = window position, k/n = channels.
 // (The context half W_c . down_proj(feat_c) + bias does not depend on the position: it arrives as ctx, one
@@ -98,12 +87,7 @@ __device__ __forceinline__ void wave_merge_tile(float* tile, int lane, const hal
       const float4 q = *reinterpret_cast<const float4*>(tile + row * PITCH + ks * 16 + 8 * h + 4);
       const float x[8] = {p.x, p.y, p.z, p.w, q.x, q.y, q.z, q.w};
 #pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float xs = x[e] * act_scale;
-        const _Float16 hh = (_Float16)xs;
-        ahi[mt][ks][e] = hh;
-        alo[mt][ks][e] = (_Float16)(xs - (float)hh);
-      }
+      for (int e = 0; e < 8; ++e) split_f16(x[e] * act_scale, ahi[mt][ks], alo[mt][ks], e);
     }
   }
   __builtin_amdgcn_wave_barrier();
@@ -116,7 +100,7 @@ __device__ __forceinline__ void wave_merge_tile(float* tile, int lane, const hal
 #pragma unroll
       for (int g = 0; g < 16; ++g) acc[g] = (nt ? c1 : c0) * (act_scale * kMergeWgtScale);   // column n = 32*nt + r
 #pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
+      for (int ks = 0; ks < 4; ++ks) {      // mma3, written out: called, k_gather_merge_nhwc64<5>'s registers come out renamed
         acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ahi[mt][ks], bhi[nt][ks], acc, 0, 0, 0);
         acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(alo[mt][ks], bhi[nt][ks], acc, 0, 0, 0);
         acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ahi[mt][ks], blo[nt][ks], acc, 0, 0, 0);
@@ -199,6 +183,17 @@ __device__ __forceinline__ void wave_copy_window64(const float* src, int Hf, int
 
 constexpr int kGatherTileFloats(int W) { return W * W * 68; }
 
+// List order: the M = min(*d_count, m_max) live windows of the match list (not the m_max launched ones) are spread
+// contiguously over the XCDs - 8 ranges of ceil(M / 8) windows, four windows (waves) per workgroup.  m = the window of
+// wave wv of this workgroup; false = it has none.
+__device__ __forceinline__ bool list_window(const int32_t* d_count, int m_max, int wv, int& m) {
+  const int M = d_count ? min(d_count[0], m_max) : m_max;
+  const int per = (M + 7) >> 3;
+  const int slot = (int)(blockIdx.x >> 3) * 4 + wv;
+  m = (blockIdx.x & 7) * per + slot;
+  return slot < per && m < M;
+}
+
 // list order: window m of the match list (any ids; the generic entry point)
 template <int W, bool MERGE>
 __global__ __launch_bounds__(256) void k_gather_nchw64(const float* __restrict__ feat, int Hf, int Wf, int stride,
@@ -210,12 +205,8 @@ __global__ __launch_bounds__(256) void k_gather_nchw64(const float* __restrict__
   constexpr int CF = 64, TOTAL = CF * W * W;
   __shared__ __attribute__((aligned(16))) float tile[4 * kGatherTileFloats(W)];
   const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int M = d_count ? min(d_count[0], m_max) : m_max;
-  // spread the M live windows (not the m_max launched ones) contiguously over the XCDs
-  const int per = (M + 7) >> 3;
-  const int slot = (int)(blockIdx.x >> 3) * 4 + wv;
-  const int m = (blockIdx.x & 7) * per + slot;
-  if (slot >= per || m >= M) return;
+  int m;
+  if (!list_window(d_count, m_max, wv, m)) return;
   const int b = __builtin_amdgcn_readfirstlane((int)b_ids[m]);       // wave-uniform values into scalars
   const int id = __builtin_amdgcn_readfirstlane((int)ids[m]);
   const int cy = id / w_c;
@@ -484,11 +475,8 @@ __global__ __launch_bounds__(256) void k_gather_nhwc64(const float* __restrict__
   constexpr int TOTAL16 = W * ROW16;         // ... per window: 400 / 784
   constexpr int NIT = (TOTAL16 + 63) / 64;
   const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int M = d_count ? min(d_count[0], m_max) : m_max;
-  const int per = (M + 7) >> 3;
-  const int slot = (int)(blockIdx.x >> 3) * 4 + wv;
-  const int m = (blockIdx.x & 7) * per + slot;
-  if (slot >= per || m >= M) return;
+  int m;
+  if (!list_window(d_count, m_max, wv, m)) return;
   const int b = __builtin_amdgcn_readfirstlane((int)b_ids[m]);
   const int id = __builtin_amdgcn_readfirstlane((int)ids[m]);
   const int cy = id / w_c;
@@ -542,6 +530,7 @@ __global__ __launch_bounds__(256) void k_gather_merge_nhwc64(MergeNhwcArgs a) {
   const MergeNhwcImage& I = a.im[blockIdx.y];
   const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   float* tile = tile_all + wv * kGatherTileFloats(W);
+  // list_window, written out: a.m_max is then loaded only on the side of the branch that needs it
   const int M = a.d_count ? min(a.d_count[0], a.m_max) : a.m_max;
   const int per = (M + 7) >> 3;
   const int slot = (int)(blockIdx.x >> 3) * 4 + wv;
@@ -594,7 +583,7 @@ __global__ __launch_bounds__(256) void k_fine_maps(const float* __restrict__ map
   constexpr int WW = W * W;
   const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int M = d_count ? min(d_count[0], m_max) : m_max;
-  const int per = (M + 7) >> 3;
+  const int per = (M + 7) >> 3;      // list_window's order, written out: M and per stay outside the loop over slots
   __shared__ __attribute__((aligned(16))) float tile_all[NCHW0 ? 4 * kGatherTileFloats(W) : 4];
   // (a grid smaller than the match list walks it in strides: fm_fine_match_maps may cap the grid so that the kernel's
   // workgroups do not fill every wave slot of the chip while another pair's coarse kernels wait for theirs)
@@ -798,8 +787,7 @@ __global__ __launch_bounds__(256) void k_merge_pack(const float* __restrict__ me
     // a weight beyond the fixed scale (|w| >= 16) would turn into +-inf here and into a wrong finite number or NaN
     // somewhere downstream: make it NaN for certain - every output that touches it then says so
     if (!(fabsf(x) <= 65504.f)) x = __builtin_nanf("");
-    hh[j] = (_Float16)x;
-    ll[j] = (_Float16)(x - (float)hh[j]);
+    split_f16(x, hh, ll, j);
   }
   packed[((nt * 4 + ks) * 2 + 0) * 64 + lane] = hh;
   packed[((nt * 4 + ks) * 2 + 1) * 64 + lane] = ll;

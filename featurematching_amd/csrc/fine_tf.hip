@@ -35,11 +35,9 @@
 #include <cstdint>
 
 #include "fm_internal.h"
+#include "fm_wave_device.h"
 
 namespace fm {
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // packed weights of one layer, in half8 fragments [plane hi/lo][out tile][k-step][lane]
 constexpr int kTfFragQ = 0;                    // q_proj  [64 x 64]: 2 out tiles x 4 k-steps
@@ -74,9 +72,9 @@ struct ActScale {
 typedef __fp16 fp16x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
-// x = hi + lo in float16 (round-toward-zero packs: the remainder x - hi is exact in float32, and the scheme only
-// needs hi + lo = x to 22 bits, not nearest rounding): 3 VALU operations per element.  The tile is ALREADY in the
-// operand scale (see above), so there is no multiply here.
+// x = hi + lo in float16.  Not the shared split_f16: round-toward-zero PACKS of two elements on purpose (the remainder
+// x - hi is exact in float32, and the scheme only needs hi + lo = x to 22 bits, not nearest rounding): 3 VALU
+// operations per element.  The tile is ALREADY in the operand scale (see above), so there is no multiply here.
 // RANGE: a value beyond float16 at the wave's scale (|x| * scale > 65504: a window value, a projection or a
 // hidden-layer value above 255.9) would be clamped silently by the round-toward-zero pack.  `amax` follows the largest
 // magnitude that ever went into an operand (one v_max3 per pair of elements); the kernel reports FM_DEV_RANGE through
@@ -95,12 +93,6 @@ __device__ __forceinline__ void split8(const f32x16& a, int half, half8& hi, hal
   hi = __builtin_bit_cast(half8, uh);
   lo = __builtin_bit_cast(half8, ul);
 }
-// acc += A.B with both operands split (float32-equivalent product)
-__device__ __forceinline__ void mma3(f32x16& acc, const half8& ah, const half8& al, const half8& bh, const half8& bl) {
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc, 0, 0, 0);
-}
 __device__ __forceinline__ void rescale(f32x16& a, float f) {
 #pragma unroll
   for (int g = 0; g < 16; ++g) a[g] *= f;
@@ -109,16 +101,9 @@ __device__ __forceinline__ void zero(f32x16& a) {
 #pragma unroll
   for (int g = 0; g < 16; ++g) a[g] = 0.f;
 }
-__device__ __forceinline__ float swap_halves_add(float v) {       // v(lane) + v(lane ^ 32)
-  float p = v, q = v;
-  asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(p), "+v"(q));
-  return p + q;
-}
-__device__ __forceinline__ float other_half(float v) {            // v(lane ^ 32)
-  float p = v, q = v;
-  asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(p), "+v"(q));
-  return (threadIdx.x & 32) ? p : q;
-}
+// v(lane ^ 32): pair_op hands over {lower half's, upper half's} value, a lane picks the one that is not its own
+struct OpOther { static __device__ __forceinline__ float f(float lo, float hi) { return (threadIdx.x & 32) ? lo : hi; } };
+__device__ __forceinline__ float other_half(float v) { return pair_op<32, OpOther>(v); }
 
 // elu(x) + 1 of a tile in the operand scale, result in the operand scale: xs = A x -> A (x > 0 ? x + 1 : exp(x))
 __device__ __forceinline__ float elu1_scaled(float xs, const ActScale& A) {
@@ -152,9 +137,7 @@ __device__ __forceinline__ void kd_fragment(const float* ksum_lds, int s, int r,
     // a match whose activations forced a smaller scale gets room for its sums as well)
     const float val = (r == (d >> 3)) ? ksum_lds[d] * (kSumScale / 256.f) : 0.f;
     amax = fmaxf(amax, val);                  // sum_s (elu(k) + 1) of a head feature must stay below 2047 at scale 2^8
-    const _Float16 hh = (_Float16)val;
-    dh[j] = hh;
-    dl[j] = (_Float16)(val - (float)hh);
+    split_f16(val, dh, dl, j);
   }
 }
 
@@ -185,13 +168,13 @@ __device__ __forceinline__ void layer_norm_T1(f32x16 (&y)[2], const float* __res
   for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
     for (int g = 0; g < 16; ++g) s += y[rt][g];
-  const float mean = swap_halves_add(s) * (1.0f / 64.0f);
+  const float mean = pair_op<32, OpAdd>(s) * (1.0f / 64.0f);
   float v = 0.f;
 #pragma unroll
   for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
     for (int g = 0; g < 16; ++g) { const float d = y[rt][g] - mean; v += d * d; }
-  const float rstd = A.a / sqrtf(swap_halves_add(v) * (1.0f / 64.0f) + 1e-5f * A.a * A.a);   // scaled eps; x the output's scale
+  const float rstd = A.a / sqrtf(pair_op<32, OpAdd>(v) * (1.0f / 64.0f) + 1e-5f * A.a * A.a);   // scaled eps; x the output's scale
 #pragma unroll
   for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
@@ -289,7 +272,7 @@ __device__ __forceinline__ void kv_phase(const float* src, const half8* lb, floa
   }
 #pragma unroll
   for (int ot = 0; ot < 2; ++ot) {
-    const float t = swap_halves_add(ks[ot]);
+    const float t = pair_op<32, OpAdd>(ks[ot]);
     if (h == 0) ksum_lds[32 * ot + r] = t;
   }
   __builtin_amdgcn_wave_barrier();
@@ -523,9 +506,7 @@ __global__ __launch_bounds__(256) void k_tf_pack(const float* __restrict__ w, in
   for (int j = 0; j < 8; ++j) {
     const float x = w[(long)(32 * ot + r) * in_f + 16 * s + 8 * (j >> 2) + 4 * h + (j & 3)] * kWgtScale;
     if (!(fabsf(x) <= 65504.f)) *pack_status = 1;        // |w| >= 16 (or not finite): beyond the fixed weight scale
-    const _Float16 hh = (_Float16)x;
-    hi[j] = hh;
-    lo[j] = (_Float16)(x - (float)hh);
+    split_f16(x, hi, lo, j);
   }
   dst[idx] = hi;
   dst[kTfFrags * 64 + idx] = lo;

@@ -1,113 +1,10 @@
-// Cross-lane helpers of the fine stage, shared by its forward (fine.hip) and its backward (fine_grad.hip): the
+// Device helpers of the fine stage, shared by its forward (fine.hip) and its backward (fine_grad.hip): the
 // backward recomputes the forward's similarities and heat maps with these very instructions.
 #pragma once
 #include "fm_device.h"
+#include "fm_wave_device.h"
 
 namespace fm {
-
-// Cross-lane exchange without LDS: v[lane ^ MASK] via DPP (1, 2, 4, 8) or the gfx950 permlane swaps
-// (16, 32), folded straight into the reduction operator.
-template <int CTRL, int BANK>
-__device__ __forceinline__ float dpp_mov(float old, float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, old), __builtin_bit_cast(int, v),
-                                                               CTRL, 0xf, BANK, false));
-}
-struct OpAdd { static __device__ __forceinline__ float f(float a, float b) { return a + b; } };
-struct OpMax { static __device__ __forceinline__ float f(float a, float b) { return fmaxf(a, b); } };
-
-// op(v[lane], v[lane ^ MASK]) in every lane
-template <int MASK, class Op>
-__device__ __forceinline__ float pair_op(float v) {
-  if constexpr (MASK == 1) return Op::f(v, dpp_mov<0xB1, 0xf>(v, v));           // quad_perm [1,0,3,2]
-  else if constexpr (MASK == 2) return Op::f(v, dpp_mov<0x4E, 0xf>(v, v));      // quad_perm [2,3,0,1]
-  else if constexpr (MASK == 4) {
-    float t = dpp_mov<0x104, 0x5>(v, v);      // row_shl:4 into banks 0,2 (lanes with bit 2 clear read lane+4)
-    t = dpp_mov<0x114, 0xA>(t, v);            // row_shr:4 into banks 1,3 (lanes with bit 2 set read lane-4)
-    return Op::f(v, t);
-  } else if constexpr (MASK == 8) return Op::f(v, dpp_mov<0x128, 0xf>(v, v));   // row_ror:8
-  else if constexpr (MASK == 16) {
-    // v_permlane16_swap a, b: odd rows of a <-> even rows of b.  With a = b = v: a = {r0,r0,r2,r2},
-    // b = {r1,r1,r3,r3}, so op(a, b) is the pair result in every lane.  Inline asm because hipcc
-    // (ROCm 7.2) returns the first result twice from the builtin when both operands are one value;
-    // s_nop 1 = the two wait states between a VALU write of an operand and the swap.
-    float a = v, b = v;
-    asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-    return Op::f(a, b);
-  } else {
-    float a = v, b = v;   // lanes 32-63 of a <-> lanes 0-31 of b: a = {lo,lo}, b = {hi,hi}
-    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-    return Op::f(a, b);
-  }
-}
-
-template <class Op>
-__device__ __forceinline__ float wave_all(float v) {
-  v = pair_op<1, Op>(v); v = pair_op<2, Op>(v); v = pair_op<4, Op>(v);
-  v = pair_op<8, Op>(v); v = pair_op<16, Op>(v); v = pair_op<32, Op>(v);
-  return v;
-}
-__device__ __forceinline__ float wave_sum(float v) { return wave_all<OpAdd>(v); }
-__device__ __forceinline__ float wave_max(float v) { return wave_all<OpMax>(v); }
-
-// Transpose-reduce: p[k] = this lane's term of sum k (k < NP = 32 or 64) -> every sum ends in ONE lane (NP = 64) or in
-// a pair of neighbouring lanes (NP = 32), tr_index(lane) tells which.  Each level halves the registers: a lane keeps one
-// half and hands the other to its partner.  Written so that the levels with many pairs cost TWO instructions per pair
-// and no select (round 2's butterfly spent five: two DPP moves, two adds, one select):
-//   lane ^ 32 : v_permlane32_swap X, Y leaves {X.lo, Y.lo} / {X.hi, Y.hi}; X + Y = X's sum in lanes 0-31, Y's in 32-63
-//   lane ^ 16 : v_permlane16_swap likewise for the rows of 16 lanes
-//   15 - i    : row_mirror DPP add with bank-masked writes: banks 0-1 keep X, banks 2-3 receive Y's sum (into X)
-//   7 - i     : row_half_mirror, banks 0 / 2 keep X, banks 1 / 3 receive Y's
-//   3 - i     : inside the quad by select + quad_perm (one or two pairs are left by then)
-//   i ^ 1     : NP = 64: one more transposing level; NP = 32: a plain sum (both lanes of a pair hold it)
-// (s_nop 1: the two wait states a DPP / permlane operand needs after the VALU write of its register.)
-template <int NP>
-__device__ __forceinline__ float transpose_reduce(float (&p)[NP], int lane) {
-  constexpr int H1 = NP / 2, H2 = NP / 4, H3 = NP / 8, H4 = NP / 16, H5 = NP / 32;
-  asm volatile("s_nop 1" ::: "memory");
-#pragma unroll
-  for (int k = 0; k < H1; ++k) asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(p[k]), "+v"(p[k + H1]));
-#pragma unroll
-  for (int k = 0; k < H1; ++k) p[k] += p[k + H1];
-  asm volatile("s_nop 1" ::: "memory");
-#pragma unroll
-  for (int k = 0; k < H2; ++k) asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(p[k]), "+v"(p[k + H2]));
-#pragma unroll
-  for (int k = 0; k < H2; ++k) p[k] += p[k + H2];
-  asm volatile("s_nop 1" ::: "memory");
-#pragma unroll
-  for (int k = 0; k < H3; ++k)
-    asm volatile("s_nop 1\n\tv_add_f32_dpp %0, %0, %0 row_mirror row_mask:0xf bank_mask:0x3" : "+v"(p[k]));
-#pragma unroll
-  for (int k = 0; k < H3; ++k)
-    asm volatile("s_nop 1\n\tv_add_f32_dpp %0, %1, %1 row_mirror row_mask:0xf bank_mask:0xc" : "+v"(p[k]) : "v"(p[k + H3]));
-  asm volatile("s_nop 1" ::: "memory");
-#pragma unroll
-  for (int k = 0; k < H4; ++k)
-    asm volatile("s_nop 1\n\tv_add_f32_dpp %0, %0, %0 row_half_mirror row_mask:0xf bank_mask:0x5" : "+v"(p[k]));
-  asm volatile("s_nop 1" ::: "memory");
-#pragma unroll
-  for (int k = 0; k < H4; ++k)
-    asm volatile("s_nop 1\n\tv_add_f32_dpp %0, %1, %1 row_half_mirror row_mask:0xf bank_mask:0xa" : "+v"(p[k]) : "v"(p[k + H4]));
-  const bool b1 = (lane & 2) != 0, b0 = (lane & 1) != 0;
-#pragma unroll
-  for (int k = 0; k < H5; ++k) {                 // lane 3 - i of the quad: quad_perm [3,2,1,0]
-    const float own = b1 ? p[k + H5] : p[k], other = b1 ? p[k] : p[k + H5];
-    p[k] = own + dpp_mov<0x1B, 0xf>(other, other);
-  }
-  if constexpr (NP == 64) {                      // lane i ^ 1 takes the second of the last two sums
-    const float own = b0 ? p[1] : p[0], other = b0 ? p[0] : p[1];
-    return own + dpp_mov<0xB1, 0xf>(other, other);
-  } else {
-    return p[0] + dpp_mov<0xB1, 0xf>(p[0], p[0]);
-  }
-}
-// lane bits b5..b0 -> the sum it holds
-template <int NP>
-__device__ __forceinline__ int tr_index(int lane) {
-  const int b5 = (lane >> 5) & 1, b4 = (lane >> 4) & 1, b3 = (lane >> 3) & 1, b2 = (lane >> 2) & 1, b1 = (lane >> 1) & 1;
-  if constexpr (NP == 64) return 32 * b5 + 16 * b4 + 8 * b3 + 4 * b2 + 2 * b1 + (lane & 1);
-  else return 16 * b5 + 8 * b4 + 4 * b3 + 2 * b2 + b1;
-}
 
 constexpr float kFineInvSqrtC = 0.125f;      // 1 / sqrt(Cf), Cf = 64 (exact)
 
@@ -173,12 +70,12 @@ __device__ __forceinline__ float heat_sums2(float e0, float e1, int pos) {
                  0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   asm volatile("s_nop 1" ::: "memory");
 #pragma unroll
-  for (int k = 0; k < 8; ++k) asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(q[k]), "+v"(q[k + 8]));
+  for (int k = 0; k < 8; ++k) permlane32_swap(q[k], q[k + 8]);
 #pragma unroll
   for (int k = 0; k < 8; ++k) q[k] += q[k + 8];
   asm volatile("s_nop 1" ::: "memory");
 #pragma unroll
-  for (int k = 0; k < 4; ++k) asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(q[k]), "+v"(q[k + 4]));
+  for (int k = 0; k < 4; ++k) permlane16_swap(q[k], q[k + 4]);
 #pragma unroll
   for (int k = 0; k < 4; ++k) q[k] += q[k + 4];
   asm volatile("s_nop 1" ::: "memory");

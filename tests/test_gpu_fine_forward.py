@@ -1,4 +1,4 @@
-"""The fine stage's forward (fine_core / soft_argmax2 of csrc/fine.hip, the cross-lane helpers of fm_fine_device.h) on
+"""The fine stage's forward (fine_core / soft_argmax2 of csrc/fine.hip, the helpers of fm_fine_device.h / fm_wave_device.h) on
 every route that computes it - k_fine<5|7> on window tensors and the eight k_fine_maps instantiations behind
 fm_fine_match_maps*, the NCHW routes through k_nchw_to_nhwc64 and the copy a coarse call prepared - against the float64
 yardstick of tests/fine_grad_ref.py (pinned by tests/test_fine_ref.py).

@@ -1,7 +1,6 @@
 // Host side of the C ABI (include/fmatch.h): argument checks, workspace layout, launch order.
 #include <math.h>
 #include <stdlib.h>
-#include <string.h>
 
 #include "fm_debug.h"
 #include "fm_internal.h"
@@ -48,8 +47,7 @@ constexpr int kMaxPassTarget = 256;
 constexpr int kMaxPassSlots = 512;
 
 CoarseWs coarse_layout(int N, int L, int S, int C, int slots, bool alone) {
-  CoarseWs w;
-  memset(&w, 0, sizeof(w));
+  CoarseWs w{};
   C = padded_channels(C);
   w.N = N; w.L = L; w.S = S; w.C = C; w.slots = slots;
   w.Lp = round_up(L, kPanelRows);
@@ -81,54 +79,54 @@ CoarseWs coarse_layout(int N, int L, int S, int C, int slots, bool alone) {
   const size_t rows = (size_t)N * w.Lp, cols = (size_t)N * w.Sp;
   const size_t nblk = (rows * slots + 255) / 256;
   size_t o = 0;
-  auto take = [&](size_t bytes) { size_t at = o; o = align256(o + bytes); return at; };
+  // (r = the next `count` elements of r's type, from a 256-byte boundary on)
+  auto take = [&](auto& r, size_t count) { r.at = o; o = align256(o + r.bytes(count)); };
   auto since = [&](size_t at) { return Span{at, o - at}; };      // what was taken from `at` on
   // ---- the common path ----
-  w.cand_count = take(rows * 4);
-  w.ccand_count = take(cols * 4);
-  w.cand_count_b = take(rows * 4);
-  w.ccand_count_b = take(cols * 4);
-  w.dense_cnt = take((size_t)N * 4);
-  w.counters[0] = since(w.cand_count);
-  w.cell0 = take(rows * 4);
-  w.cell1 = take(cols * 4);
-  w.ties0 = take((kTieCap + 1) * 4);
-  w.ties1 = take((kTieCap + 1) * 4);
-  w.reassign[0] = since(w.cell0);
-  w.rowmax_u = take(rows * 4);
-  w.colmax_u = take(cols * 4);
-  w.blocktot = take(nblk * 4);
-  w.reassign[1] = since(w.blocktot);
-  w.scalars = take(sizeof(Scalars));
-  w.reassign[2] = Span{w.scalars, sizeof(Scalars::flags)};     // (dense_units stays: the dense kernels read it)
-  w.counters[1] = Span{w.scalars, sizeof(Scalars)};
-  w.prep_zero = since(w.cand_count);
-  w.q0 = take(rows * C); w.q1 = take(cols * C);
-  w.sigimg = take((size_t)N * 2 * 4);
-  w.imgstat = take((size_t)N * 8 * 4);
-  w.l1_0 = take(rows * 4); w.l1_1 = take(cols * 4);
-  w.bstat0 = take(rows / 32 * 16); w.bstat1 = take(cols / 32 * 16);
-  w.emarg = take((size_t)N * 4);
-  w.rowS = take(0); w.colS = take(0);
-  w.nmr = take(rows * 4); w.nmc = take(cols * 4);
-  w.umax = take(rows / 32 * (cols / N / 32) * 4);
-  w.cand_j = take(rows * slots * 4); w.cand_x = take(rows * slots * 4);
-  w.ccand_i = take(cols * slots * 4); w.ccand_x = take(cols * slots * 4);
-  w.thr_r = take(rows * 4); w.thr_c = take(cols * 4);
-  w.wmaxb = take(rows / 32 * 4); w.cmaxu = take(cols / 32 * 4);
-  w.tmin_r = take(rows / 32 * 4); w.tmin_c = take(cols / 32 * 4);
-  w.umax2 = take(rows / 32 * (cols / N / 32) * 4);
-  w.upos = take(rows / 32 * (cols / N / 32) * 4);
+  take(w.cand.count, rows);
+  take(w.ccand.count, cols);
+  take(w.cand_b.count, rows);
+  take(w.ccand_b.count, cols);
+  take(w.dense_cnt, N);
+  w.counters[0] = since(w.cand.count.at);
+  take(w.cell0, rows);
+  take(w.cell1, cols);
+  take(w.ties0, kTieCap + 1);
+  take(w.ties1, kTieCap + 1);
+  w.reassign[0] = since(w.cell0.at);
+  take(w.rowmax_u, rows);
+  take(w.colmax_u, cols);
+  take(w.blocktot, nblk);
+  w.reassign[1] = since(w.blocktot.at);
+  take(w.scalars, 1);
+  w.reassign[2] = Span{w.scalars.at, sizeof(Scalars::flags)};     // (dense_units stays: the dense kernels read it)
+  w.counters[1] = Span{w.scalars.at, sizeof(Scalars)};
+  w.prep_zero = since(w.cand.count.at);
+  take(w.q0, rows * C); take(w.q1, cols * C);
+  take(w.sigimg, (size_t)N * 2);
+  take(w.imgstat, (size_t)N * 8);
+  take(w.l1_0, rows); take(w.l1_1, cols);
+  take(w.bstat0, rows / 32); take(w.bstat1, cols / 32);
+  take(w.emarg, N);
+  take(w.nmr, rows); take(w.nmc, cols);
+  take(w.umax, rows / 32 * (cols / N / 32));
+  take(w.cand.idx, rows * slots); take(w.cand.x, rows * slots);
+  take(w.ccand.idx, cols * slots); take(w.ccand.x, cols * slots);
+  take(w.thr_r, rows); take(w.thr_c, cols);
+  take(w.wmaxb, rows / 32); take(w.cmaxu, cols / 32);
+  take(w.tmin_r, rows / 32); take(w.tmin_c, cols / 32);
+  take(w.umax2, rows / 32 * (cols / N / 32));
+  take(w.upos, rows / 32 * (cols / N / 32));
   w.common_total = o;
   // ---- FM_MODE_DENSE / FM_MODE_EXACT_SCREENING / conf_matrix ----
-  w.hi0 = take(rows * C * 2); w.lo0 = take(rows * C * 2);
-  w.hi1 = take(cols * C * 2); w.lo1 = take(cols * C * 2);
-  w.f16inv = take((size_t)N * 4);
-  w.rowB = take(rows * w.splits * 4); w.colB = take(cols * w.panels * kColParts * 4);
-  w.rsum = take(rows * 4); w.csum = take(cols * 4);
-  w.nmr2 = take(rows * 4); w.nmc2 = take(cols * 4);
-  w.cand_j_b = take(rows * slots * 4); w.cand_x_b = take(rows * slots * 4);
-  w.ccand_i_b = take(cols * slots * 4); w.ccand_x_b = take(cols * slots * 4);
+  take(w.hi0, rows * C); take(w.lo0, rows * C);
+  take(w.hi1, cols * C); take(w.lo1, cols * C);
+  take(w.f16inv, N);
+  take(w.rowB, rows * w.splits); take(w.colB, cols * w.panels);
+  take(w.rsum, rows); take(w.csum, cols);
+  take(w.nmr2, rows); take(w.nmc2, cols);
+  take(w.cand_b.idx, rows * slots); take(w.cand_b.x, rows * slots);
+  take(w.ccand_b.idx, cols * slots); take(w.ccand_b.x, cols * slots);
   w.total = o;
   return w;
 }
@@ -163,6 +161,9 @@ extern "C" int fm_default_cand_slots(float thr) {
   while (s < need && s < 64) s <<= 1;
   return s;
 }
+
+// 1 / (C temperature): what scales a dot product into a similarity
+static float inv_ct_of(int C, float temperature) { return 1.0f / ((float)C * temperature); }
 
 // a power of two in [4, 64]: a row's slots are adjacent lanes of one wave and k_keep_emit keeps 256/slots <= 64 rows
 static bool valid_slots(int s) { return s >= 4 && s <= 64 && (s & (s - 1)) == 0; }
@@ -248,35 +249,24 @@ extern "C" int fm_coarse_workspace_bytes(int N, int L, int S, int C, int cand_sl
 // Diagnostic: the workspace layout (ints then byte offsets), so that tests can inspect the
 // intermediate statistics of a run.  out[0..9] = N,L,S,C,Lp,Sp,panels,tiles,splits,slots;
 // out[10..] = cand_count, ccand_count, scalars, blocktot, hi0, lo0, hi1, lo1, q0, q1, sigimg, l1_0,
-// rowS, colS (both zero-length), rowB, colB, nmr, nmc, rsum, csum, cand_j, cand_x, ccand_i, umax, dense_cnt, rowmax_u,
+// nmr, nmr (22, 23: the slots of two zero-length regions that lay in front of nmr, so its offset is what they always
+// held), rowB, colB, nmr, nmc, rsum, csum, cand_j, cand_x, ccand_i, umax, dense_cnt, rowmax_u,
 // colmax_u, splits_s, units_s, total; out[40] = common_total (when n_out > 40)  (40 or 41 values).
 extern "C" int fm_debug_coarse_layout(int N, int L, int S, int C, int cand_slots, int64_t* out, int n_out) {
   if (!out) return FM_E_NULL;
   if (n_out < 40) return FM_E_SHAPE;
   CoarseWs w;
   if (const int bad = checked_layout(true, N, L, S, C, cand_slots, &w)) return bad;
+  const auto at = [](const auto& r) { return (int64_t)r.at; };
   const int64_t v[41] = {w.N, w.L, w.S, w.C, w.Lp, w.Sp, w.panels, w.tiles, w.splits, w.slots,
-                         (int64_t)w.cand_count, (int64_t)w.ccand_count, (int64_t)w.scalars, (int64_t)w.blocktot,
-                         (int64_t)w.hi0, (int64_t)w.lo0, (int64_t)w.hi1, (int64_t)w.lo1, (int64_t)w.q0,
-                         (int64_t)w.q1, (int64_t)w.sigimg, (int64_t)w.l1_0, (int64_t)w.rowS, (int64_t)w.colS,
-                         (int64_t)w.rowB, (int64_t)w.colB, (int64_t)w.nmr, (int64_t)w.nmc, (int64_t)w.rsum,
-                         (int64_t)w.csum, (int64_t)w.cand_j, (int64_t)w.cand_x, (int64_t)w.ccand_i,
-                         (int64_t)w.umax, (int64_t)w.dense_cnt, (int64_t)w.rowmax_u, (int64_t)w.colmax_u,
+                         at(w.cand.count), at(w.ccand.count), at(w.scalars), at(w.blocktot), at(w.hi0), at(w.lo0),
+                         at(w.hi1), at(w.lo1), at(w.q0), at(w.q1), at(w.sigimg), at(w.l1_0), at(w.nmr), at(w.nmr),
+                         at(w.rowB), at(w.colB), at(w.nmr), at(w.nmc), at(w.rsum), at(w.csum), at(w.cand.idx),
+                         at(w.cand.x), at(w.ccand.idx), at(w.umax), at(w.dense_cnt), at(w.rowmax_u), at(w.colmax_u),
                          w.splits_s, w.units_s, (int64_t)w.total, (int64_t)w.common_total};
   for (int i = 0; i < 40; ++i) out[i] = v[i];
   if (n_out > 40) out[40] = v[40];
   return FM_OK;
-}
-
-extern "C" int fm_coarse_match(const float* feat0, const float* feat1, int N, int L, int S, int C, int h0c, int w0c,
-                               int h1c, int w1c, float temperature, float thr, int border_rm, float scale_px,
-                               const float* scale0, const float* scale1, void* workspace, size_t workspace_bytes,
-                               int cand_slots, int mode, int64_t* b_ids, int64_t* i_ids, int64_t* j_ids,
-                               float* mkpts0_c, float* mkpts1_c, float* mconf, int cap, int32_t* d_count,
-                               float* conf_matrix, void* stream) {
-  return fm_coarse_match_dtype(feat0, feat1, FM_F32, N, L, S, C, h0c, w0c, h1c, w1c, temperature, thr, border_rm, scale_px,
-                               scale0, scale1, workspace, workspace_bytes, cand_slots, mode, b_ids, i_ids,
-                               j_ids, mkpts0_c, mkpts1_c, mconf, cap, d_count, conf_matrix, stream);
 }
 
 template <int K>
@@ -292,59 +282,64 @@ static hipError_t clear_spans(char* base, const Span (&spans)[K], hipStream_t st
 // same arguments on the common path - mode without FM_MODE_DENSE, the only plan whose screening reports flat similarity -
 // reported just that; its prep, max pass and screening results are in the workspace, so what its assignment left is
 // cleared and the plan of mode | FM_MODE_DENSE continues from the float16 planes.
-static int coarse_match_impl(const void* feat0, const void* feat1, int in_dtype, int N, int L, int S, int C,
-                             int h0c, int w0c, int h1c, int w1c, float temperature, float thr, int border_rm,
-                             float scale_px, const float* scale0, const float* scale1, void* workspace,
-                             size_t workspace_bytes, int cand_slots, int mode, int64_t* b_ids,
-                             int64_t* i_ids, int64_t* j_ids, float* mkpts0_c, float* mkpts1_c, float* mconf,
-                             int cap, int32_t* d_count, float* conf_matrix, const MapCopyJob* job, void* stream,
-                             bool resume) {
-  if (!feat0 || !feat1 || !workspace || !d_count) return FM_E_NULL;
-  if (in_dtype != FM_F32 && in_dtype != FM_F16 && in_dtype != FM_BF16) return FM_E_UNSUPPORTED;
-  if (cap > 0 && (!b_ids || !i_ids || !j_ids || !mkpts0_c || !mkpts1_c || !mconf)) return FM_E_NULL;
-  if (cap < 0 || L != h0c * w0c || S != h1c * w1c) return FM_E_SHAPE;
-  if (const int bad = check_coarse_shape(N, L, S, C, cand_slots)) return bad;
-  if (!(thr > 0.f) || !(thr < 1.f) || !(temperature > 0.f)) return FM_E_UNSUPPORTED;
-  if (mode & ~kKnownModes) return FM_E_UNSUPPORTED;
-  const CoarsePlan p = plan_coarse(mode, conf_matrix != nullptr, cand_slots);
-  const CoarseWs w = coarse_layout(N, L, S, C, cand_slots, p.alone);
-  if (workspace_bytes < p.workspace_bytes(w) || ((uintptr_t)workspace & 255)) return FM_E_WORKSPACE;
-  char* base = (char*)workspace;
-  hipStream_t st = (hipStream_t)stream;
-  const float inv_ct = 1.0f / ((float)C * temperature);
-  const float thr_list = fminf(thr, p.list_cap);     // candidate threshold of the dense kernels' LISTS
+static int coarse_match_impl(const CoarseCall& c, const MapCopyJob* job, bool resume) {
+  if (!c.feat0 || !c.feat1 || !c.workspace || !c.d_count) return FM_E_NULL;
+  if (c.in_dtype != FM_F32 && c.in_dtype != FM_F16 && c.in_dtype != FM_BF16) return FM_E_UNSUPPORTED;
+  if (c.cap > 0 && (!c.b_ids || !c.i_ids || !c.j_ids || !c.mkpts0_c || !c.mkpts1_c || !c.mconf)) return FM_E_NULL;
+  if (c.cap < 0 || c.L != c.h0c * c.w0c || c.S != c.h1c * c.w1c) return FM_E_SHAPE;
+  if (const int bad = check_coarse_shape(c.N, c.L, c.S, c.C, c.cand_slots)) return bad;
+  if (!(c.thr > 0.f) || !(c.thr < 1.f) || !(c.temperature > 0.f)) return FM_E_UNSUPPORTED;
+  if (c.mode & ~kKnownModes) return FM_E_UNSUPPORTED;
+  const CoarsePlan p = plan_coarse(c.mode, c.conf_matrix != nullptr, c.cand_slots);
+  const CoarseWs w = coarse_layout(c.N, c.L, c.S, c.C, c.cand_slots, p.alone);
+  if (c.workspace_bytes < p.workspace_bytes(w) || ((uintptr_t)c.workspace & 255)) return FM_E_WORKSPACE;
+  char* base = (char*)c.workspace;
+  hipStream_t st = (hipStream_t)c.stream;
+  const float inv_ct = inv_ct_of(c.C, c.temperature);
+  const float thr_list = fminf(c.thr, p.list_cap);     // candidate threshold of the dense kernels' LISTS
 #define FM_TRY(call) do { const hipError_t e_ = (call); if (e_ != hipSuccess) return (int)e_; } while (0)
   if (!resume) {
     // The common path is four launches: prep -> max pass -> sparse sum kernel -> assignment.
     // prep: clear the per-call counters, quantise both images (one int8 step per image), L1 norms
-    FM_TRY(launch_prep(feat0, feat1, in_dtype, C, w, base, p.exact_step, p.flat, st));
+    FM_TRY(launch_prep(c.feat0, c.feat1, c.in_dtype, c.C, w, base, p.exact_step, p.flat, st));
     // max pass: row / column / unit maxima of the integer screening product (atomicMax: no partials, no reduction kernel)
     FM_TRY(launch_max_i8(w, base, unit_cert_on(w, !p.dense), st));
     // sparse sum kernel: stabilisers, live units, exact terms of the few significant entries, candidates (listed per row
     // and per column); flags the samples with too many significant entries per unit (flat similarity).  FM_MODE_FLAT:
     // the sweep would only find that out again - a small kernel forms the stabilisers and flags every sample
-    if (p.flat) FM_TRY(launch_stab(w, base, inv_ct, thr, p.allow_dead, st));
-    else FM_TRY(launch_screen(feat0, feat1, in_dtype, C, w, base, inv_ct, thr, p.dense, p.allow_dead, st));
+    if (p.flat) FM_TRY(launch_stab(w, base, inv_ct, c.thr, p.allow_dead, st));
+    else FM_TRY(launch_screen(c.feat0, c.feat1, c.in_dtype, c.C, w, base, inv_ct, c.thr, p.dense, p.allow_dead, st));
   } else {
     FM_TRY(clear_spans(base, w.reassign, st));
   }
-  if (p.prep_f16) FM_TRY(launch_prep_f16(feat0, feat1, in_dtype, C, w, base, p.f16_force, st));
+  if (p.prep_f16) FM_TRY(launch_prep_f16(c.feat0, c.feat1, c.in_dtype, c.C, w, base, p.f16_force, st));
   // (the dense sum kernel redoes the flagged samples - one arithmetic per sample keeps exact conf ties exact - and exits
   // at once when there are none)
   if (p.dense) FM_TRY(launch_dense(w, base, inv_ct, thr_list, st));
   if (p.reduce) FM_TRY(launch_reduce(w, base, inv_ct, st));
   // (exits immediately unless the sum kernels' screening overflowed a row's slots)
   if (p.rescreen) FM_TRY(launch_dense(w, base, inv_ct, thr_list, st, nullptr, 1));
-  if (p.exact_lists) FM_TRY(launch_exact_lists(w, base, inv_ct, feat0, feat1, in_dtype, C, st));
+  if (p.exact_lists) FM_TRY(launch_exact_lists(w, base, inv_ct, c.feat0, c.feat1, c.in_dtype, c.C, st));
   if (p.conf) {
     // dense data['conf_matrix'] (one more sweep), whose hi/lo-split products carry 22 bits: the entries that matter are
     // rewritten from their exact float32 dot products (the rows' lists of significant entries)
-    FM_TRY(launch_dense(w, base, inv_ct, thr, st, conf_matrix));
-    FM_TRY(launch_conf_patch(w, base, inv_ct, conf_matrix, st));
+    FM_TRY(launch_dense(w, base, inv_ct, c.thr, st, c.conf_matrix));
+    FM_TRY(launch_conf_patch(w, base, inv_ct, c.conf_matrix, st));
   }
 #undef FM_TRY
-  return (int)launch_select(w, base, h0c, w0c, h1c, w1c, inv_ct, thr, border_rm, scale_px, scale0, scale1, b_ids, i_ids,
-                            j_ids, mkpts0_c, mkpts1_c, mconf, cap, d_count, p.select(), st, job);
+  return (int)launch_select(w, base, c, inv_ct, p.select(), job);
+}
+
+extern "C" int fm_coarse_match(const float* feat0, const float* feat1, int N, int L, int S, int C, int h0c, int w0c,
+                               int h1c, int w1c, float temperature, float thr, int border_rm, float scale_px,
+                               const float* scale0, const float* scale1, void* workspace, size_t workspace_bytes,
+                               int cand_slots, int mode, int64_t* b_ids, int64_t* i_ids, int64_t* j_ids,
+                               float* mkpts0_c, float* mkpts1_c, float* mconf, int cap, int32_t* d_count,
+                               float* conf_matrix, void* stream) {
+  const CoarseCall c{feat0, feat1, FM_F32, N, L, S, C, h0c, w0c, h1c, w1c, temperature, thr, border_rm, scale_px, scale0, scale1,
+                     workspace, workspace_bytes, cand_slots, mode, b_ids, i_ids, j_ids, mkpts0_c, mkpts1_c, mconf, cap,
+                     d_count, conf_matrix, stream};
+  return coarse_match_impl(c, nullptr, false);
 }
 
 extern "C" int fm_coarse_match_dtype(const void* feat0, const void* feat1, int in_dtype, int N, int L, int S, int C,
@@ -353,9 +348,10 @@ extern "C" int fm_coarse_match_dtype(const void* feat0, const void* feat1, int i
                                      size_t workspace_bytes, int cand_slots, int mode, int64_t* b_ids,
                                      int64_t* i_ids, int64_t* j_ids, float* mkpts0_c, float* mkpts1_c, float* mconf,
                                      int cap, int32_t* d_count, float* conf_matrix, void* stream) {
-  return coarse_match_impl(feat0, feat1, in_dtype, N, L, S, C, h0c, w0c, h1c, w1c, temperature, thr, border_rm, scale_px,
-                           scale0, scale1, workspace, workspace_bytes, cand_slots, mode, b_ids, i_ids, j_ids, mkpts0_c,
-                           mkpts1_c, mconf, cap, d_count, conf_matrix, nullptr, stream, false);
+  const CoarseCall c{feat0, feat1, in_dtype, N, L, S, C, h0c, w0c, h1c, w1c, temperature, thr, border_rm, scale_px, scale0,
+                     scale1, workspace, workspace_bytes, cand_slots, mode, b_ids, i_ids, j_ids, mkpts0_c, mkpts1_c, mconf, cap,
+                     d_count, conf_matrix, stream};
+  return coarse_match_impl(c, nullptr, false);
 }
 
 // fm_coarse_match_dtype + the channels-last copy of image 1's fine map as a side job of the assignment launch
@@ -371,9 +367,10 @@ extern "C" int fm_coarse_match_maps(const void* feat0, const void* feat1, int in
   if (Cf != 64) return FM_E_UNSUPPORTED;
   if (((uintptr_t)scratch1 & 15) || ((uintptr_t)feat_f1 & 15)) return FM_E_WORKSPACE;
   const MapCopyJob job{feat_f1, (float*)scratch1, Nf, Hf1, Wf1};
-  return coarse_match_impl(feat0, feat1, in_dtype, N, L, S, C, h0c, w0c, h1c, w1c, temperature, thr, border_rm, scale_px,
-                           scale0, scale1, workspace, workspace_bytes, cand_slots, mode, b_ids, i_ids, j_ids, mkpts0_c,
-                           mkpts1_c, mconf, cap, d_count, conf_matrix, &job, stream, false);
+  const CoarseCall c{feat0, feat1, in_dtype, N, L, S, C, h0c, w0c, h1c, w1c, temperature, thr, border_rm, scale_px, scale0,
+                     scale1, workspace, workspace_bytes, cand_slots, mode, b_ids, i_ids, j_ids, mkpts0_c, mkpts1_c, mconf, cap,
+                     d_count, conf_matrix, stream};
+  return coarse_match_impl(c, &job, false);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -420,13 +417,16 @@ extern "C" int fm_coarse_match_auto(const void* feat0, const void* feat1, int in
   int st = FM_OK;
   int32_t m = 0, info = 0;
   int attempts = 0;
+  // one call for every attempt: only its slots and its mode change
+  CoarseCall c{feat0, feat1, in_dtype, N, L, S, C, h0c, w0c, h1c, w1c, temperature, thr, border_rm, scale_px, scale0, scale1,
+               workspace, workspace_bytes, slots, mode, b_ids, i_ids, j_ids, mkpts0_c, mkpts1_c, mconf, cap, d_count,
+               conf_matrix, stream};
   for (int attempt = 0; attempt < 10; ++attempt) {
     ++attempts;
     const int call_mode = fixed | cur | ((cur & FM_MODE_FLAT) ? FM_MODE_DENSE : 0);
     // every attempt must fit the caller's workspace (sized by fm_coarse_workspace_bytes_auto for max_cand_slots)
-    st = fm_coarse_match_dtype(feat0, feat1, in_dtype, N, L, S, C, h0c, w0c, h1c, w1c, temperature, thr, border_rm, scale_px,
-                               scale0, scale1, workspace, workspace_bytes, slots, call_mode, b_ids, i_ids, j_ids, mkpts0_c,
-                               mkpts1_c, mconf, cap, d_count, conf_matrix, stream);
+    c.cand_slots = slots; c.mode = call_mode;
+    st = coarse_match_impl(c, nullptr, false);
     if (st != FM_OK) return st;
     st = fm_read_count_info(d_count, cap, &m, &info, stream);
     if (st == FM_E_DENSE && !(cur & FM_MODE_DENSE) && !conf_matrix && !(mode & FM_MODE_STATS)) {
@@ -435,9 +435,8 @@ extern "C" int fm_coarse_match_auto(const void* feat0, const void* feat1, int in
       // (the resume clears the WHOLE status word: only when "flat similarity" is all it holds - anything else the device
       // reported with it would be dropped, so such a call is repeated from the start instead)
       if ((info & ~FM_DEV_ALL_DENSE) != FM_DEV_DENSE) continue;
-      st = coarse_match_impl(feat0, feat1, in_dtype, N, L, S, C, h0c, w0c, h1c, w1c, temperature, thr, border_rm, scale_px,
-                             scale0, scale1, workspace, workspace_bytes, slots, fixed | cur, b_ids, i_ids, j_ids, mkpts0_c,
-                             mkpts1_c, mconf, cap, d_count, conf_matrix, nullptr, stream, true);
+      c.mode = fixed | cur;
+      st = coarse_match_impl(c, nullptr, true);
       if (st != FM_OK) return st;
       st = fm_read_count_info(d_count, cap, &m, &info, stream);
     }
@@ -486,8 +485,8 @@ extern "C" int fm_coarse_cell_maps(void* workspace, int N, int L, int S, int C, 
   if (const int bad = checked_layout(workspace && cell0 && cell1 && pitch0 && pitch1 && ties0 && ties1, N, L, S, C,
                                      cand_slots, &w))
     return bad;
-  *cell0 = (int32_t*)((char*)workspace + w.cell0); *pitch0 = w.Lp; *ties0 = (int32_t*)((char*)workspace + w.ties0);
-  *cell1 = (int32_t*)((char*)workspace + w.cell1); *pitch1 = w.Sp; *ties1 = (int32_t*)((char*)workspace + w.ties1);
+  *cell0 = w.cell0.in(workspace); *pitch0 = w.Lp; *ties0 = w.ties0.in(workspace);
+  *cell1 = w.cell1.in(workspace); *pitch1 = w.Sp; *ties1 = w.ties1.in(workspace);
   return FM_OK;
 }
 
@@ -502,8 +501,8 @@ extern "C" int fm_coarse_softmax_stats(void* workspace, int N, int L, int S, int
   if (const int bad = checked_layout(workspace && nm_r && sum_r && pitch_r && nm_c && sum_c && pitch_c, N, L, S, C,
                                      cand_slots, &w))
     return bad;
-  *nm_r = (const float*)((char*)workspace + w.nmr); *sum_r = (const float*)((char*)workspace + w.rsum); *pitch_r = w.Lp;
-  *nm_c = (const float*)((char*)workspace + w.nmc); *sum_c = (const float*)((char*)workspace + w.csum); *pitch_c = w.Sp;
+  *nm_r = w.nmr.in(workspace); *sum_r = w.rsum.in(workspace); *pitch_r = w.Lp;
+  *nm_c = w.nmc.in(workspace); *sum_c = w.csum.in(workspace); *pitch_c = w.Sp;
   return FM_OK;
 }
 
@@ -518,8 +517,8 @@ extern "C" int fm_debug_launch_corr(void* workspace, int N, int L, int S, int C,
   if (mode < 0 || mode > 2) return FM_E_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   if (mode == 0) return (int)launch_max_i8(w, (char*)workspace, unit_cert_on(w), st);
-  if (mode == 1) return (int)launch_dense(w, (char*)workspace, 1.0f / ((float)C * temperature), thr, st);
-  return (int)launch_dense(w, (char*)workspace, 1.0f / ((float)C * temperature), thr, st, nullptr, 1);      // mode 2: the re-screening
+  if (mode == 1) return (int)launch_dense(w, (char*)workspace, inv_ct_of(C, temperature), thr, st);
+  return (int)launch_dense(w, (char*)workspace, inv_ct_of(C, temperature), thr, st, nullptr, 1);      // mode 2: the re-screening
 }
 
 // Diagnostic: launch the sparse sum kernel alone on a workspace a previous fm_coarse_match filled.
@@ -527,7 +526,7 @@ extern "C" int fm_debug_launch_screen(void* workspace, const float* feat0, const
                                           int C, int cand_slots, float temperature, float thr, void* stream) {
   CoarseWs w;
   if (const int bad = checked_layout(workspace && feat0 && feat1, N, L, S, C, cand_slots, &w)) return bad;
-  return (int)launch_screen(feat0, feat1, FM_F32, C, w, (char*)workspace, 1.0f / ((float)C * temperature), thr, 1, 1,
+  return (int)launch_screen(feat0, feat1, FM_F32, C, w, (char*)workspace, inv_ct_of(C, temperature), thr, 1, 1,
                                 (hipStream_t)stream);
 }
 
@@ -557,7 +556,7 @@ extern "C" int fm_debug_launch_flat(void* workspace, const float* feat0, const f
   if (const int bad = checked_layout(workspace && feat0 && feat1, N, L, S, C, cand_slots, &w)) return bad;
   if (which < 0 || which > 1) return FM_E_UNSUPPORTED;
   if (which == 0) return (int)launch_prep(feat0, feat1, FM_F32, C, w, (char*)workspace, 0, 1, (hipStream_t)stream);
-  return (int)launch_stab(w, (char*)workspace, 1.0f / ((float)C * temperature), thr, 1, (hipStream_t)stream);
+  return (int)launch_stab(w, (char*)workspace, inv_ct_of(C, temperature), thr, 1, (hipStream_t)stream);
 }
 
 // Diagnostic: zero the candidate counters and the scalars, so that the sum kernels can be launched again on a
@@ -582,8 +581,8 @@ extern "C" int fm_debug_unit_cert_layout(int N, int L, int S, int C, int cand_sl
   if (n_out < 9) return FM_E_SHAPE;
   CoarseWs w;
   if (const int bad = checked_layout(true, N, L, S, C, cand_slots, &w)) return bad;
-  const int64_t v[9] = {(int64_t)w.umax, (int64_t)w.umax2, (int64_t)w.upos, (int64_t)w.thr_r, (int64_t)w.thr_c,
-                        (int64_t)w.tmin_r, (int64_t)w.tmin_c, (int64_t)(w.scalars + offsetof(Scalars, cert_units)), w.top2};
+  const int64_t v[9] = {(int64_t)w.umax.at, (int64_t)w.umax2.at, (int64_t)w.upos.at, (int64_t)w.thr_r.at, (int64_t)w.thr_c.at,
+                        (int64_t)w.tmin_r.at, (int64_t)w.tmin_c.at, (int64_t)(w.scalars.at + offsetof(Scalars, cert_units)), w.top2};
   for (int i = 0; i < 9; ++i) out[i] = v[i];
   return FM_OK;
 }

@@ -500,17 +500,17 @@ hipError_t launch_dense(const CoarseWs& w, char* base, float inv_ct, float thr, 
   DenseArgs a;
   a.conf = conf;
   const bool offsets = conf != nullptr || rescreen;      // both read the log-softmax offsets of k_reduce_sums
-  a.hi0 = (const _Float16*)(base + w.hi0); a.lo0 = (const _Float16*)(base + w.lo0);
-  a.hi1 = (const _Float16*)(base + w.hi1); a.lo1 = (const _Float16*)(base + w.lo1);
-  a.nmr = (const float*)(base + (offsets ? w.nmr2 : w.nmr)); a.nmc = (const float*)(base + (offsets ? w.nmc2 : w.nmc));
-  a.rowpart = (float*)(base + w.rowB); a.colpart = (float*)(base + w.colB);
-  a.dense_cnt = (const int*)(base + w.dense_cnt);
-  a.dense_units = &((const Scalars*)(base + w.scalars))->dense_units;
-  a.f16inv = (const float*)(base + w.f16inv);
-  a.cand_count = (int*)(base + w.cand_count_b); a.cand_j = (int*)(base + w.cand_j_b); a.cand_x = (float*)(base + w.cand_x_b);
-  a.ccand_count = (int*)(base + w.ccand_count_b); a.ccand_i = (int*)(base + w.ccand_i_b); a.ccand_x = (float*)(base + w.ccand_x_b);
-  a.flags = (unsigned*)(base + w.scalars);
-  a.diag = (float*)(base + w.cand_x);
+  a.hi0 = w.hi0.in(base); a.lo0 = w.lo0.in(base);
+  a.hi1 = w.hi1.in(base); a.lo1 = w.lo1.in(base);
+  a.nmr = (offsets ? w.nmr2 : w.nmr).in(base); a.nmc = (offsets ? w.nmc2 : w.nmc).in(base);
+  a.rowpart = w.rowB.in(base); a.colpart = w.colB.in(base);
+  a.dense_cnt = w.dense_cnt.in(base);
+  a.dense_units = &w.scalars.in(base)->dense_units;
+  a.f16inv = w.f16inv.in(base);
+  a.cand_count = w.cand_b.count.in(base); a.cand_j = w.cand_b.idx.in(base); a.cand_x = w.cand_b.x.in(base);
+  a.ccand_count = w.ccand_b.count.in(base); a.ccand_i = w.ccand_b.idx.in(base); a.ccand_x = w.ccand_b.x.in(base);
+  a.flags = &w.scalars.in(base)->flags;
+  a.diag = w.cand.x.in(base);
   a.L = w.L; a.S = w.S; a.Lp = w.Lp; a.Sp = w.Sp; a.panels = w.panels; a.units = w.Sp / 32;
   // the row partials are [N][w.splits][Lp] (k_select / k_reduce_sums fold w.splits of them): the same number of splits
   // as the tile-based kernel it replaces, in units of 32 columns
@@ -527,37 +527,30 @@ hipError_t launch_dense(const CoarseWs& w, char* base, float inv_ct, float thr, 
   a.k = inv_ct * kLog2e;
   a.lt = log2f(thr) - (rescreen ? 2e-4f : 0.f);      // the re-screening compares rounded log-softmax values: small guard
   const int blocks = w.N * a.splits * w.panels;
-  hipError_t e = hipSuccess;
-#define FM_DENSE_CASE(CC)                                                                        \
-  case CC: {                                                                                     \
-    static unsigned long long lds_set = 0, lds_set_c = 0, lds_set_r = 0;                         \
-    if (conf) {      /* the samples the screening kernel served, then (exits at once without any) the dense kernel's */ \
-      static unsigned long long lds_set_l = 0;                                                   \
-      e = ensure_dynamic_lds(&k_dense<CC, kDenseConfLite>, kDenseRing * 2 * (CC / 16) * 1024, &lds_set_l); \
-      if (e != hipSuccess) return e;                                                             \
-      hipLaunchKernelGGL((k_dense<CC, kDenseConfLite>), dim3(blocks), dim3(512), kDenseRing * 2 * (CC / 16) * 1024, st, a);   \
-      e = ensure_dynamic_lds(&k_dense<CC, kDenseConf>, kDenseRing * 2 * (CC / 16) * 1024, &lds_set_c); \
-      if (e != hipSuccess) return e;                                                             \
-      hipLaunchKernelGGL((k_dense<CC, kDenseConf>), dim3(blocks), dim3(512), kDenseRing * 2 * (CC / 16) * 1024, st, a);   \
-    } else if (rescreen) {                                                                       \
-      e = ensure_dynamic_lds(&k_dense<CC, kDenseRescreen>, kDenseRing * 2 * (CC / 16) * 1024, &lds_set_r); \
-      if (e != hipSuccess) return e;                                                             \
-      hipLaunchKernelGGL((k_dense<CC, kDenseRescreen>), dim3(blocks), dim3(512), kDenseRing * 2 * (CC / 16) * 1024, st, a);   \
-    } else {                                                                                     \
-      e = ensure_dynamic_lds(&k_dense<CC, kDenseSums>, kDenseRing * 2 * (CC / 16) * 1024, &lds_set);  \
-      if (e != hipSuccess) return e;                                                             \
-      hipLaunchKernelGGL((k_dense<CC, kDenseSums>), dim3(blocks), dim3(512), kDenseRing * 2 * (CC / 16) * 1024, st, a);  \
-    }                                                                                            \
-    break;                                                                                       \
-  }
-  switch (w.C) {
-    FM_DENSE_CASE(64)
-    FM_DENSE_CASE(128)
-    FM_DENSE_CASE(256)
-    default: return hipErrorInvalidValue;
-  }
-#undef FM_DENSE_CASE
-  return hipGetLastError();
+  return with_padded_channels(w.C, [&](auto cc) {
+    constexpr int CC = cc.value;
+    hipError_t e = hipSuccess;
+    constexpr int lds = kDenseRing * 2 * (CC / 16) * 1024;
+    static unsigned long long lds_set = 0, lds_set_c = 0, lds_set_r = 0;
+    if (conf) {      // the samples the screening kernel served, then (exits at once without any) the dense kernel's
+      static unsigned long long lds_set_l = 0;
+      e = ensure_dynamic_lds(&k_dense<CC, kDenseConfLite>, lds, &lds_set_l);
+      if (e != hipSuccess) return e;
+      hipLaunchKernelGGL((k_dense<CC, kDenseConfLite>), dim3(blocks), dim3(512), lds, st, a);
+      e = ensure_dynamic_lds(&k_dense<CC, kDenseConf>, lds, &lds_set_c);
+      if (e != hipSuccess) return e;
+      hipLaunchKernelGGL((k_dense<CC, kDenseConf>), dim3(blocks), dim3(512), lds, st, a);
+    } else if (rescreen) {
+      e = ensure_dynamic_lds(&k_dense<CC, kDenseRescreen>, lds, &lds_set_r);
+      if (e != hipSuccess) return e;
+      hipLaunchKernelGGL((k_dense<CC, kDenseRescreen>), dim3(blocks), dim3(512), lds, st, a);
+    } else {
+      e = ensure_dynamic_lds(&k_dense<CC, kDenseSums>, lds, &lds_set);
+      if (e != hipSuccess) return e;
+      hipLaunchKernelGGL((k_dense<CC, kDenseSums>), dim3(blocks), dim3(512), lds, st, a);
+    }
+    return hipGetLastError();
+  });
 }
 
 }  // namespace fm

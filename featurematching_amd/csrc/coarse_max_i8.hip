@@ -529,13 +529,13 @@ __global__ __launch_bounds__(256, 2) void k_max_i8(MaxArgs a) {
 
 hipError_t launch_max_i8(const CoarseWs& w, char* base, bool top2, hipStream_t st) {
   MaxArgs a;
-  a.q0 = (const signed char*)(base + w.q0); a.q1 = (const signed char*)(base + w.q1);
-  a.rowmax_u = (unsigned*)(base + w.rowmax_u); a.colmax_u = (unsigned*)(base + w.colmax_u);
-  a.umax = (float*)(base + w.umax);
-  a.umax2 = (int*)(base + w.umax2); a.upos = (int*)(base + w.upos);
-  a.bstat0 = (const float4*)(base + w.bstat0); a.bstat1 = (const float4*)(base + w.bstat1);
-  a.imgstat = (float*)(base + w.imgstat);
-  a.diag = (float*)(base + w.rowB);      // (diagnostic builds run on a full-size workspace)
+  a.q0 = w.q0.in(base); a.q1 = w.q1.in(base);
+  a.rowmax_u = w.rowmax_u.in(base); a.colmax_u = w.colmax_u.in(base);
+  a.umax = w.umax.in(base);
+  a.umax2 = w.umax2.in(base); a.upos = w.upos.in(base);
+  a.bstat0 = w.bstat0.in(base); a.bstat1 = w.bstat1.in(base);
+  a.imgstat = w.imgstat.in(base);
+  a.diag = w.rowB.in(base);      // (diagnostic builds run on a full-size workspace)
   a.L = w.L; a.S = w.S; a.Lp = w.Lp; a.Sp = w.Sp; a.panels = w.panels; a.tiles = w.tiles;
   a.tiles_per_split = (w.tiles + w.splits0 - 1) / w.splits0;
   a.splits = (w.tiles + a.tiles_per_split - 1) / a.tiles_per_split;      // (no empty split)
@@ -548,29 +548,21 @@ hipError_t launch_max_i8(const CoarseWs& w, char* base, bool top2, hipStream_t s
     if (a.splits == 1) a.pgroup = w.panels;
   }
   const int blocks = w.N * a.splits * w.panels;
-  hipError_t e = hipSuccess;
-#define FM_MAX_CASE(CC)                                                                        \
-  case CC: {                                                                                   \
-    static unsigned long long lds_set[2] = {0, 0};                                             \
-    if (top2) {                                                                                \
-      e = ensure_dynamic_lds(&k_max_i8<CC, true>, 4 * kTileCols * CC, &lds_set[1]);            \
-      if (e != hipSuccess) return e;                                                           \
-      hipLaunchKernelGGL((k_max_i8<CC, true>), dim3(blocks), dim3(256), 4 * kTileCols * CC, st, a);  \
-    } else {                                                                                   \
-      e = ensure_dynamic_lds(&k_max_i8<CC, false>, 4 * kTileCols * CC, &lds_set[0]);           \
-      if (e != hipSuccess) return e;                                                           \
-      hipLaunchKernelGGL((k_max_i8<CC, false>), dim3(blocks), dim3(256), 4 * kTileCols * CC, st, a); \
-    }                                                                                          \
-    break;                                                                                     \
-  }
-  switch (w.C) {
-    FM_MAX_CASE(64)
-    FM_MAX_CASE(128)
-    FM_MAX_CASE(256)
-    default: return hipErrorInvalidValue;
-  }
-#undef FM_MAX_CASE
-  return hipGetLastError();
+  return with_padded_channels(w.C, [&](auto cc) {
+    constexpr int CC = cc.value;
+    hipError_t e = hipSuccess;
+    static unsigned long long lds_set[2] = {0, 0};
+    if (top2) {
+      e = ensure_dynamic_lds(&k_max_i8<CC, true>, 4 * kTileCols * CC, &lds_set[1]);
+      if (e != hipSuccess) return e;
+      hipLaunchKernelGGL((k_max_i8<CC, true>), dim3(blocks), dim3(256), 4 * kTileCols * CC, st, a);
+    } else {
+      e = ensure_dynamic_lds(&k_max_i8<CC, false>, 4 * kTileCols * CC, &lds_set[0]);
+      if (e != hipSuccess) return e;
+      hipLaunchKernelGGL((k_max_i8<CC, false>), dim3(blocks), dim3(256), 4 * kTileCols * CC, st, a);
+    }
+    return hipGetLastError();
+  });
 }
 
 }  // namespace fm

@@ -379,19 +379,19 @@ __global__ __launch_bounds__(256) void k_prep_f16(PrepArgs a) {
 static void fill_prep_args(PrepArgs& a, const void* feat0, const void* feat1, int in_dtype, int c_in, const CoarseWs& w,
                            char* base) {
   a.src0 = feat0; a.src1 = feat1; a.in_dtype = in_dtype;
-  a.hi0 = (_Float16*)(base + w.hi0); a.lo0 = (_Float16*)(base + w.lo0);
-  a.hi1 = (_Float16*)(base + w.hi1); a.lo1 = (_Float16*)(base + w.lo1);
-  a.q0 = (signed char*)(base + w.q0); a.q1 = (signed char*)(base + w.q1);
-  a.sigimg = (float*)(base + w.sigimg);
+  a.hi0 = w.hi0.in(base); a.lo0 = w.lo0.in(base);
+  a.hi1 = w.hi1.in(base); a.lo1 = w.lo1.in(base);
+  a.q0 = w.q0.in(base); a.q1 = w.q1.in(base);
+  a.sigimg = w.sigimg.in(base);
   a.exact_step = 0;
-  a.l1_0 = (float*)(base + w.l1_0); a.l1_1 = (float*)(base + w.l1_1);
-  a.bstat0 = (float4*)(base + w.bstat0); a.bstat1 = (float4*)(base + w.bstat1);
-  a.zero = (uint4*)(base + w.prep_zero.at); a.zero_vec = (int)(w.prep_zero.bytes / 16);
+  a.l1_0 = w.l1_0.in(base); a.l1_1 = w.l1_1.in(base);
+  a.bstat0 = w.bstat0.in(base); a.bstat1 = w.bstat1.in(base);
+  a.zero = span_ptr<uint4>(base, w.prep_zero); a.zero_vec = (int)(w.prep_zero.bytes / 16);
   a.L = w.L; a.S = w.S; a.Lp = w.Lp; a.Sp = w.Sp; a.c_in = c_in;
   a.blocks0 = (int)((long)w.N * w.Lp / 32);
-  a.dense_cnt = (const int*)(base + w.dense_cnt); a.force = 0; a.f16inv = (float*)(base + w.f16inv);
-  a.bstat0r = (const float4*)(base + w.bstat0); a.bstat1r = (const float4*)(base + w.bstat1); a.N = w.N;
-  a.diag = (float*)(base + w.colB);       // (diagnostic builds run on a full-size workspace)
+  a.dense_cnt = w.dense_cnt.in(base); a.force = 0; a.f16inv = w.f16inv.in(base);
+  a.bstat0r = w.bstat0.in(base); a.bstat1r = w.bstat1.in(base); a.N = w.N;
+  a.diag = w.colB.in(base);       // (diagnostic builds run on a full-size workspace)
 }
 
 hipError_t launch_prep_f16(const void* feat0, const void* feat1, int in_dtype, int c_in, const CoarseWs& w, char* base,
@@ -400,13 +400,10 @@ hipError_t launch_prep_f16(const void* feat0, const void* feat1, int in_dtype, i
   fill_prep_args(a, feat0, feat1, in_dtype, c_in, w, base);
   a.force = force;
   const int blocks = a.blocks0 + (int)((long)w.N * w.Sp / 32);
-  switch (w.C) {
-    case 64: hipLaunchKernelGGL(k_prep_f16<64>, dim3(blocks), dim3(256), 0, st, a); break;
-    case 128: hipLaunchKernelGGL(k_prep_f16<128>, dim3(blocks), dim3(256), 0, st, a); break;
-    case 256: hipLaunchKernelGGL(k_prep_f16<256>, dim3(blocks), dim3(256), 0, st, a); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_padded_channels(w.C, [&](auto cc) {
+    hipLaunchKernelGGL(k_prep_f16<cc.value>, dim3(blocks), dim3(256), 0, st, a);
+    return hipGetLastError();
+  });
 }
 
 hipError_t launch_prep(const void* feat0, const void* feat1, int in_dtype, int c_in, const CoarseWs& w, char* base,
@@ -418,19 +415,11 @@ hipError_t launch_prep(const void* feat0, const void* feat1, int in_dtype, int c
     a.exact_step = 1;
     hipLaunchKernelGGL(k_prep_amax, dim3(blocks), dim3(256), 0, st, a);
   }
-#define FM_PREP_CASE(CC)                                                                                  \
-  case CC:                                                                                                \
-    if (planes) hipLaunchKernelGGL((k_prep_split<CC, true>), dim3(blocks), dim3(256), 0, st, a);          \
-    else hipLaunchKernelGGL((k_prep_split<CC, false>), dim3(blocks), dim3(256), 0, st, a);                \
-    break;
-  switch (w.C) {
-    FM_PREP_CASE(64)
-    FM_PREP_CASE(128)
-    FM_PREP_CASE(256)
-    default: return hipErrorInvalidValue;
-  }
-#undef FM_PREP_CASE
-  return hipGetLastError();
+  return with_padded_channels(w.C, [&](auto cc) {
+    if (planes) hipLaunchKernelGGL((k_prep_split<cc.value, true>), dim3(blocks), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((k_prep_split<cc.value, false>), dim3(blocks), dim3(256), 0, st, a);
+    return hipGetLastError();
+  });
 }
 
 // Softmax denominators of EVERY row and column (only the exact screening pass and the dense conf_matrix need
@@ -504,13 +493,11 @@ __global__ __launch_bounds__(256) void k_reduce_sums(const float* __restrict__ r
 hipError_t launch_reduce(const CoarseWs& w, char* base, float inv_ct, hipStream_t st) {
   const int chunks = (max(w.Lp, w.Sp) + 15) / 16;
   const dim3 grid(chunks, w.N, 2);
-  hipLaunchKernelGGL(k_reduce_sums, grid, dim3(256), 0, st, (const float*)(base + w.rowB), (const float*)(base + w.colB),
-                     (float*)(base + w.rsum), (float*)(base + w.csum), w.Lp, w.Sp, w.splits, w.panels, w.slots,
-                     inv_ct * kLog2e, (const float*)(base + w.nmr), (const float*)(base + w.nmc), (float*)(base + w.nmr2),
-                     (float*)(base + w.nmc2), (const int*)(base + w.cand_count), (const int*)(base + w.cand_j),
-                     (const float*)(base + w.cand_x), (const int*)(base + w.ccand_count), (const int*)(base + w.ccand_i),
-                     (const float*)(base + w.ccand_x), (int*)(base + w.cand_count_b), (int*)(base + w.ccand_count_b),
-                     (const int*)(base + w.dense_cnt), (const Scalars*)(base + w.scalars));
+  hipLaunchKernelGGL(k_reduce_sums, grid, dim3(256), 0, st, w.rowB.in(base), w.colB.in(base), w.rsum.in(base), w.csum.in(base),
+                     w.Lp, w.Sp, w.splits, w.panels, w.slots, inv_ct * kLog2e, w.nmr.in(base), w.nmc.in(base), w.nmr2.in(base),
+                     w.nmc2.in(base), w.cand.count.in(base), w.cand.idx.in(base), w.cand.x.in(base), w.ccand.count.in(base),
+                     w.ccand.idx.in(base), w.ccand.x.in(base), w.cand_b.count.in(base), w.ccand_b.count.in(base),
+                     w.dense_cnt.in(base), w.scalars.in(base));
   return hipGetLastError();
 }
 

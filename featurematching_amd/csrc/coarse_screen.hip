@@ -457,13 +457,13 @@ __global__ __launch_bounds__(256, 3) void k_screen_rows(ScreenArgs a, RowsExtra 
 }
 
 static void fill_screen_stats(ScreenArgs& a, const CoarseWs& w, char* base, float inv_ct, float thr, int allow_dead) {
-  a.rowmax_u = (const unsigned*)(base + w.rowmax_u); a.colmax_u = (const unsigned*)(base + w.colmax_u);
-  a.sigimg = (const float*)(base + w.sigimg); a.imgstat = (const float*)(base + w.imgstat);
-  a.l1_0 = (const float*)(base + w.l1_0); a.l1_1 = (const float*)(base + w.l1_1);
-  a.bstat0 = (const float4*)(base + w.bstat0); a.bstat1 = (const float4*)(base + w.bstat1);
-  a.umax = (const float*)(base + w.umax);
-  a.nmr = (float*)(base + w.nmr); a.nmc = (float*)(base + w.nmc); a.emarg = (float*)(base + w.emarg);
-  a.dense_cnt = (int*)(base + w.dense_cnt); a.scal = (Scalars*)(base + w.scalars);
+  a.rowmax_u = w.rowmax_u.in(base); a.colmax_u = w.colmax_u.in(base);
+  a.sigimg = w.sigimg.in(base); a.imgstat = w.imgstat.in(base);
+  a.l1_0 = w.l1_0.in(base); a.l1_1 = w.l1_1.in(base);
+  a.bstat0 = w.bstat0.in(base); a.bstat1 = w.bstat1.in(base);
+  a.umax = w.umax.in(base);
+  a.nmr = w.nmr.in(base); a.nmc = w.nmc.in(base); a.emarg = w.emarg.in(base);
+  a.dense_cnt = w.dense_cnt.in(base); a.scal = w.scalars.in(base);
   a.L = w.L; a.S = w.S; a.Lp = w.Lp; a.Sp = w.Sp;
   a.slots = w.slots; a.allow_dead = allow_dead;
   a.k = inv_ct * kLog2e; a.lt = log2f(thr); a.inv_ct = inv_ct; a.cpad = (float)w.C;
@@ -474,7 +474,7 @@ hipError_t launch_stab(const CoarseWs& w, char* base, float inv_ct, float thr, i
   memset(&a, 0, sizeof(a));
   fill_screen_stats(a, w, base, inv_ct, thr, allow_dead);
   const int lenp = w.Lp > w.Sp ? w.Lp : w.Sp;
-  hipLaunchKernelGGL(k_stab, dim3((lenp + 255) / 256, w.N, 2), dim3(256), 0, st, a, (float*)(base + w.f16inv));
+  hipLaunchKernelGGL(k_stab, dim3((lenp + 255) / 256, w.N, 2), dim3(256), 0, st, a, w.f16inv.in(base));
   return hipGetLastError();
 }
 
@@ -484,16 +484,16 @@ hipError_t launch_screen(const void* feat0, const void* feat1, int in_dtype, int
   memset(&a, 0, sizeof(a));
   fill_screen_stats(a, w, base, inv_ct, thr, allow_dead);
   a.in_dtype = in_dtype;
-  a.q0 = (const signed char*)(base + w.q0); a.q1 = (const signed char*)(base + w.q1);
+  a.q0 = w.q0.in(base); a.q1 = w.q1.in(base);
   a.src0 = feat0; a.src1 = feat1; a.c_in = c_in;
-  a.rcount = (int*)(base + w.cand_count); a.rlist_j = (int*)(base + w.cand_j); a.rlist_x = (float*)(base + w.cand_x);
-  a.ccount = (int*)(base + w.ccand_count); a.clist_i = (int*)(base + w.ccand_i); a.clist_x = (float*)(base + w.ccand_x);
+  a.rcount = w.cand.count.in(base); a.rlist_j = w.cand.idx.in(base); a.rlist_x = w.cand.x.in(base);
+  a.ccount = w.ccand.count.in(base); a.clist_i = w.ccand.idx.in(base); a.clist_x = w.ccand.x.in(base);
   a.dense_enabled = dense_enabled;
   RowsExtra x;
-  x.thr_r = (int*)(base + w.thr_r); x.thr_c = (int*)(base + w.thr_c);
-  x.wmaxb = (float*)(base + w.wmaxb); x.cmaxu = (float*)(base + w.cmaxu);
-  x.tmin_r = (int*)(base + w.tmin_r); x.tmin_c = (int*)(base + w.tmin_c);
-  x.umax2 = (const int*)(base + w.umax2); x.upos = (const int*)(base + w.upos);
+  x.thr_r = w.thr_r.in(base); x.thr_c = w.thr_c.in(base);
+  x.wmaxb = w.wmaxb.in(base); x.cmaxu = w.cmaxu.in(base);
+  x.tmin_r = w.tmin_r.in(base); x.tmin_c = w.tmin_c.in(base);
+  x.umax2 = w.umax2.in(base); x.upos = w.upos.in(base);
   x.look = g_unit_cert != 1;
   x.count_cert = g_unit_cert == 2;
   x.chunk_units = w.units_s;
@@ -505,13 +505,10 @@ hipError_t launch_screen(const void* feat0, const void* feat1, int in_dtype, int
   const int lenp = w.Lp > w.Sp ? w.Lp : w.Sp;
   hipLaunchKernelGGL(k_thresh, dim3((lenp + 255) / 256, w.N, 2), dim3(256), 0, st, a, x);
   const int blocks_r = (x.items + 3) / 4;
-  switch (w.C) {
-    case 64: hipLaunchKernelGGL(k_screen_rows<64>, dim3(blocks_r), dim3(256), 0, st, a, x); break;
-    case 128: hipLaunchKernelGGL(k_screen_rows<128>, dim3(blocks_r), dim3(256), 0, st, a, x); break;
-    case 256: hipLaunchKernelGGL(k_screen_rows<256>, dim3(blocks_r), dim3(256), 0, st, a, x); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_padded_channels(w.C, [&](auto cc) {
+    hipLaunchKernelGGL(k_screen_rows<cc.value>, dim3(blocks_r), dim3(256), 0, st, a, x);
+    return hipGetLastError();
+  });
 }
 
 }  // namespace fm

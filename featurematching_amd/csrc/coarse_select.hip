@@ -392,37 +392,34 @@ __global__ __launch_bounds__(256) void k_select(SelArgs a) {
   SEL_DIAG_OUT
 }
 
-hipError_t launch_select(const CoarseWs& w, char* base, int h0c, int w0c,
-                         int h1c, int w1c, float inv_ct, float thr, int border, float scale_px,
-                         const float* scale0, const float* scale1, int64_t* b_ids, int64_t* i_ids,
-                         int64_t* j_ids, float* k0, float* k1, float* mconf, int cap, int32_t* d_count,
-                         SelectFlags flags, hipStream_t st, const MapCopyJob* job) {
+hipError_t launch_select(const CoarseWs& w, char* base, const CoarseCall& c, float inv_ct, SelectFlags flags,
+                         const MapCopyJob* job) {
   SelArgs a;
   a.exact = flags.exact; a.dense_enabled = flags.dense; a.cell_maps = flags.cell_maps; a.sums_ready = flags.sums_ready;
-  a.nmr = (const float*)(base + w.nmr); a.nmc = (const float*)(base + w.nmc);
-  a.rowB = (const float*)(base + w.rowB); a.colB = (const float*)(base + w.colB);
-  a.cand_count = (const int*)(base + w.cand_count); a.cand_j = (const int*)(base + w.cand_j);
-  a.cand_x = (const float*)(base + w.cand_x);
-  a.ccand_count = (const int*)(base + w.ccand_count); a.ccand_i = (const int*)(base + w.ccand_i);
-  a.ccand_x = (const float*)(base + w.ccand_x);
-  a.cand_count_b = (const int*)(base + w.cand_count_b); a.cand_j_b = (const int*)(base + w.cand_j_b);
-  a.cand_x_b = (const float*)(base + w.cand_x_b);
-  a.ccand_count_b = (const int*)(base + w.ccand_count_b); a.ccand_i_b = (const int*)(base + w.ccand_i_b);
-  a.ccand_x_b = (const float*)(base + w.ccand_x_b);
-  a.dense_cnt = (const int*)(base + w.dense_cnt);
-  a.rsum = (const float*)(base + w.rsum); a.csum = (const float*)(base + w.csum);
-  a.blocktot = (int*)(base + w.blocktot);
-  a.scal = (Scalars*)(base + w.scalars);
+  a.nmr = w.nmr.in(base); a.nmc = w.nmc.in(base);
+  a.rowB = w.rowB.in(base); a.colB = w.colB.in(base);
+  a.cand_count = w.cand.count.in(base); a.cand_j = w.cand.idx.in(base);
+  a.cand_x = w.cand.x.in(base);
+  a.ccand_count = w.ccand.count.in(base); a.ccand_i = w.ccand.idx.in(base);
+  a.ccand_x = w.ccand.x.in(base);
+  a.cand_count_b = w.cand_b.count.in(base); a.cand_j_b = w.cand_b.idx.in(base);
+  a.cand_x_b = w.cand_b.x.in(base);
+  a.ccand_count_b = w.ccand_b.count.in(base); a.ccand_i_b = w.ccand_b.idx.in(base);
+  a.ccand_x_b = w.ccand_b.x.in(base);
+  a.dense_cnt = w.dense_cnt.in(base);
+  a.rsum = w.rsum.in(base); a.csum = w.csum.in(base);
+  a.blocktot = w.blocktot.in(base);
+  a.scal = w.scalars.in(base);
   a.N = w.N; a.L = w.L; a.S = w.S; a.C = w.C; a.Lp = w.Lp; a.Sp = w.Sp; a.splits = w.splits; a.splits_s = w.splits_s; a.panels = w.panels;
-  a.slots = w.slots; a.h0c = h0c; a.w0c = w0c; a.h1c = h1c; a.w1c = w1c; a.border = border;
-  a.k = inv_ct * kLog2e; a.thr = thr; a.scale_px = scale_px; a.scale0 = scale0; a.scale1 = scale1;
-  a.b_ids = b_ids; a.i_ids = i_ids; a.j_ids = j_ids; a.k0 = k0; a.k1 = k1; a.mconf = mconf;
-  a.cap = cap; a.d_count = d_count;
-  a.cell0 = (int*)(base + w.cell0); a.cell1 = (int*)(base + w.cell1);
-  a.ties0 = (int*)(base + w.ties0); a.ties1 = (int*)(base + w.ties1);
+  a.slots = w.slots; a.h0c = c.h0c; a.w0c = c.w0c; a.h1c = c.h1c; a.w1c = c.w1c; a.border = c.border_rm;
+  a.k = inv_ct * kLog2e; a.thr = c.thr; a.scale_px = c.scale_px; a.scale0 = c.scale0; a.scale1 = c.scale1;
+  a.b_ids = c.b_ids; a.i_ids = c.i_ids; a.j_ids = c.j_ids; a.k0 = c.mkpts0_c; a.k1 = c.mkpts1_c; a.mconf = c.mconf;
+  a.cap = c.cap; a.d_count = c.d_count;
+  a.cell0 = w.cell0.in(base); a.cell1 = w.cell1.in(base);
+  a.ties0 = w.ties0.in(base); a.ties1 = w.ties1.in(base);
   const int blocks = (int)(((long)w.N * w.Lp * w.slots + 255) / 256);
   a.nblk = blocks;
-  a.diag = (float*)(base + w.rowB);       // (diagnostic builds run on a full-size workspace)
+  a.diag = w.rowB.in(base);       // (diagnostic builds run on a full-size workspace)
   a.job = MapCopyJob{nullptr, nullptr, 0, 0, 0};
   int extra = 0;
   if (job && job->src) {
@@ -431,7 +428,7 @@ hipError_t launch_select(const CoarseWs& w, char* base, int h0c, int w0c,
     const long units = (long)((job->Wf + 63) / 64) * job->Hf * job->N;
     extra = (int)(units < 1024 ? units : 1024);
   }
-  hipLaunchKernelGGL(k_select, dim3(blocks + extra), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(k_select, dim3(blocks + extra), dim3(256), 0, (hipStream_t)c.stream, a);
   return hipGetLastError();
 }
 

@@ -303,29 +303,27 @@ __global__ __launch_bounds__(256) void k_fix_sums(const int* __restrict__ rcount
 
 hipError_t launch_exact_lists(const CoarseWs& w, char* base, float inv_ct, const void* feat0, const void* feat1, int in_dtype,
                               int c_in, hipStream_t st) {
+  // the dense kernel's lists; every term's change goes to the same slot of the sparse kernel's x arrays (idle for the
+  // samples the dense kernel redid), where k_fix_sums reads it
+  const CandList &rows = w.cand_b, &cols = w.ccand_b;
+  float *rdelta = w.cand.x.in(base), *cdelta = w.ccand.x.in(base);
   const long groups = (long)w.N * max(w.Lp, w.Sp);
   hipLaunchKernelGGL(k_exact_lists, dim3((unsigned)((groups + 15) / 16), 1, 2), dim3(256), 0, st, feat0, feat1, in_dtype, c_in,
-                     (const int*)(base + w.cand_count_b), (const int*)(base + w.cand_j_b), (float*)(base + w.cand_x_b),
-                     (float*)(base + w.cand_x), (const int*)(base + w.ccand_count_b), (const int*)(base + w.ccand_i_b),
-                     (float*)(base + w.ccand_x_b), (float*)(base + w.ccand_x), (const float*)(base + w.nmr),
-                     (const float*)(base + w.nmc), (const int*)(base + w.dense_cnt), w.N, w.L, w.S, w.Lp, w.Sp, w.slots,
-                     inv_ct * kLog2e);
-  hipLaunchKernelGGL(k_fix_sums, dim3((max(w.Lp, w.Sp) + 255) / 256, w.N, 2), dim3(256), 0, st,
-                     (const int*)(base + w.cand_count_b), (const int*)(base + w.cand_j_b), (const float*)(base + w.cand_x),
-                     (const int*)(base + w.ccand_count_b), (const int*)(base + w.ccand_i_b), (const float*)(base + w.ccand_x),
-                     (const float*)(base + w.nmr), (const float*)(base + w.nmc), (float*)(base + w.rsum), (float*)(base + w.csum),
-                     (float*)(base + w.nmr2), (float*)(base + w.nmc2), (const int*)(base + w.dense_cnt), w.Lp, w.Sp, w.slots);
+                     rows.count.in(base), rows.idx.in(base), rows.x.in(base), rdelta, cols.count.in(base), cols.idx.in(base),
+                     cols.x.in(base), cdelta, w.nmr.in(base), w.nmc.in(base), w.dense_cnt.in(base), w.N, w.L, w.S, w.Lp, w.Sp,
+                     w.slots, inv_ct * kLog2e);
+  hipLaunchKernelGGL(k_fix_sums, dim3((max(w.Lp, w.Sp) + 255) / 256, w.N, 2), dim3(256), 0, st, rows.count.in(base),
+                     rows.idx.in(base), rdelta, cols.count.in(base), cols.idx.in(base), cdelta, w.nmr.in(base), w.nmc.in(base),
+                     w.rsum.in(base), w.csum.in(base), w.nmr2.in(base), w.nmc2.in(base), w.dense_cnt.in(base), w.Lp, w.Sp, w.slots);
   return hipGetLastError();
 }
 
 hipError_t launch_conf_patch(const CoarseWs& w, char* base, float inv_ct, float* conf, hipStream_t st) {
   const long total = (long)w.N * w.Lp * w.slots;
-  hipLaunchKernelGGL(k_conf_patch, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const int*)(base + w.cand_count),
-                     (const int*)(base + w.cand_j), (const float*)(base + w.cand_x), (const int*)(base + w.cand_count_b),
-                     (const int*)(base + w.cand_j_b), (const float*)(base + w.cand_x_b), (const float*)(base + w.nmr),
-                     (const float*)(base + w.rsum), (const float*)(base + w.nmc), (const float*)(base + w.csum),
-                     (const int*)(base + w.dense_cnt), w.N, w.L, w.S, w.Lp, w.Sp, w.slots,
-                     inv_ct * kLog2e, conf);
+  hipLaunchKernelGGL(k_conf_patch, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, w.cand.count.in(base),
+                     w.cand.idx.in(base), w.cand.x.in(base), w.cand_b.count.in(base), w.cand_b.idx.in(base), w.cand_b.x.in(base),
+                     w.nmr.in(base), w.rsum.in(base), w.nmc.in(base), w.csum.in(base), w.dense_cnt.in(base), w.N, w.L, w.S, w.Lp,
+                     w.Sp, w.slots, inv_ct * kLog2e, conf);
   return hipGetLastError();
 }
 

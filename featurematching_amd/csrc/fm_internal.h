@@ -11,7 +11,6 @@
 namespace fm {
 
 constexpr int kPanelRows = 256;   // coarse rows (image-0 cells) one workgroup owns
-constexpr int kColParts = 1;         // column partials per 256-row panel (the 8 waves' partials are folded in LDS)
 constexpr int kTieCap = 1023;        // listed tie losers per image; beyond it the gathers scan the match list
 constexpr int kTileCols = 64;     // coarse columns (image-1 cells) per streamed tile
 constexpr float kLog2e = 1.4426950408889634f;
@@ -32,6 +31,17 @@ inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 struct Span { size_t at, bytes; };           // bytes [at, at + bytes) of a workspace
 template <typename T>
 inline T* span_ptr(void* base, const Span& s) { return reinterpret_cast<T*>(static_cast<char*>(base) + s.at); }
+// Where a workspace's array of T starts.  in(base) is its pointer: the element type is stated once, where the region is
+// declared, and a launcher that hands it to a kernel argument of another type does not compile.
+template <typename T>
+struct Region {
+  size_t at;
+  T* in(void* base) const { return reinterpret_cast<T*>(static_cast<char*>(base) + at); }
+  static size_t bytes(size_t count) { return count * sizeof(T); }
+};
+// one listing of the candidates, per row or per column: how many each holds, then `slots` entries each - the index on
+// the other side and the exact dot product
+struct CandList { Region<int> count, idx; Region<float> x; };
 
 // A runtime choice as a compile-time constant, so that a launch's argument list is written once: with_window calls
 // f(int_c<W>) for the window sizes the fine kernels are instantiated for and returns false (f not called) for any other
@@ -50,6 +60,13 @@ inline bool crop_shape_ok(int N, int Hf, int Wf, int stride, int m_max) {
   return N > 0 && Hf > 0 && Wf > 0 && stride > 0 && m_max >= 0;
 }
 
+struct Scalars {          // lives at ws.scalars (zeroed per call)
+  unsigned flags;         // FM_DEV_* bits
+  int dense_units;        // 32x32 units the sparse sum kernel left to the dense one (0: that kernel exits at once)
+  int cert_units;         // live units k_screen_rows resolved from the max pass's certificate (counted only while
+                          // fm_debug_unit_cert forces the certificate on)
+};
+
 // Device workspace of the coarse stage; all offsets in bytes from the base.  The regions the common path uses come
 // first (`common_total` bytes); the float16 planes, the dense sum kernel's partials and candidate set and the
 // softmax denominators of every row / column follow and are needed only with FM_MODE_DENSE / FM_MODE_EXACT_SCREENING /
@@ -66,49 +83,45 @@ struct CoarseWs {
                                               // maps and tie lists, its look-back totals, the status word
   Span counters[2];                           // zeroed by fm_debug_reset_counters: the candidate counters, the scalars
   // zeroed on every call (contiguous, starts at the base)
-  size_t cand_count, ccand_count, cand_count_b, ccand_count_b, dense_cnt, scalars;
-                                              // cand_count / ccand_count: candidates per row / per column found by the
-                                              // sparse sum kernel (the same entries, listed from both sides); *_b: by
-                                              // the dense one; dense_cnt [N]: units of a sample the sparse kernel left
-                                              // to the dense one (> 0: the dense kernel redoes the sample)
-  size_t cell0, cell1;                        // (zeroed) match index + 1 of every image-0 / image-1 cell
-  size_t ties0, ties1;                        // (zeroed) [0] = count, [1..kTieCap] = matches that lost their cell to an
+  CandList cand, ccand;                       // every significant entry the sparse sum kernel found, listed per row
+                                              // (column, exact dot product) and per column (row, ...): the same entries
+  CandList cand_b, ccand_b;                   // ... the dense kernel's candidate set (samples it redid); its lists lie in
+                                              // the dense region below, the four counts here (zeroed on every call)
+  Region<int> dense_cnt;                      // [N]: units of a sample the sparse kernel left to the dense one (> 0: the
+                                              // dense kernel redoes the sample)
+  Region<Scalars> scalars;
+  Region<int> cell0, cell1;                   // (zeroed) match index + 1 of every image-0 / image-1 cell
+  Region<int> ties0, ties1;                   // (zeroed) [0] = count, [1..kTieCap] = matches that lost their cell to an
                                               // exactly tied match (the cell-ordered gathers pick them up)
-  size_t rowmax_u, colmax_u;                  // (zeroed) q_encode'd row / column maxima of the integer screening
+  Region<unsigned> rowmax_u, colmax_u;        // (zeroed) q_encode'd row / column maxima of the integer screening
                                               // product (max pass: atomicMax, exact and order independent)
-  size_t blocktot;                            // (zeroed) k_select: matches per workgroup | published flag
+  Region<int> blocktot;                       // (zeroed) k_select: matches per workgroup | published flag
   // per-row / per-column statistics
-  size_t q0, q1;                              // int8 screening planes
-  size_t sigimg;                              // [N][2] the int8 step of image 0 / image 1 of every sample
-  size_t imgstat;                             // [N][8] per sample {largest L1 norm, largest clipped mass, largest |x|} of
+  Region<signed char> q0, q1;                 // int8 screening planes
+  Region<float> sigimg;                       // [N][2] the int8 step of image 0 / image 1 of every sample
+  Region<float> imgstat;                      // [N][8] per sample {largest L1 norm, largest clipped mass, largest |x|} of
                                               // image 0, then of image 1 (max pass: the block statistics folded once);
                                               // [6]: 1 when that max pass wrote umax2 / upos, else 0
-  size_t l1_0, l1_1;                          // L1 norm per descriptor
-  size_t bstat0, bstat1;                      // float4 per 32-row block: {largest L1 norm (+inf: a bad value), largest
+  Region<float> l1_0, l1_1;                   // L1 norm per descriptor
+  Region<float4> bstat0, bstat1;              // per 32-row block: {largest L1 norm (+inf: a bad value), largest
                                               // clipped L1 mass sum_k max(|x_k| - 127 sigma, 0), largest |x|, 0}
-  size_t emarg;                               // [N] log2-domain bound of k * |screening product - exact product|
-  size_t rowS, colS;                          // zero-length (the sparse sum kernel's partial sum-exp, until the screening
-                                              // kernel handed over lists of significant entries); kept because
-                                              // fm_debug_coarse_layout exports its slots by index
-  size_t nmr, nmc;                            // -stabiliser*log2e per row / column
-  size_t umax;                                // unit maxima [N][Lp/32][Sp/32] of the integer screening product (as float)
-  size_t cand_j, cand_x;                      // k_screen: every significant entry of a row (column, exact dot product)
-  size_t ccand_i, ccand_x;                    // ... of a column (row, exact dot product)
-  size_t thr_r, thr_c;                        // k_thresh (batched screening): integer significance threshold per row / column
-  size_t wmaxb, cmaxu;                        // ... largest -stabiliser*log2e of every 32-row block / 32-column unit
-  size_t tmin_r, tmin_c;                      // ... smallest integer threshold of every 32-row block / 32-column unit
-  size_t umax2, upos;                         // k_max_i8<C, true>, [N][Lp/32][Sp/32] ints: the unit's second-largest valid entry
+  Region<float> emarg;                        // [N] log2-domain bound of k * |screening product - exact product|
+  Region<float> nmr, nmc;                     // -stabiliser*log2e per row / column
+  Region<float> umax;                         // unit maxima [N][Lp/32][Sp/32] of the integer screening product (as float)
+  Region<int> thr_r, thr_c;                   // k_thresh (batched screening): integer significance threshold per row / column
+  Region<float> wmaxb, cmaxu;                 // ... largest -stabiliser*log2e of every 32-row block / 32-column unit
+  Region<int> tmin_r, tmin_c;                 // ... smallest integer threshold of every 32-row block / 32-column unit
+  Region<int> umax2, upos;                    // k_max_i8<C, true>, [N][Lp/32][Sp/32]: the unit's second-largest valid entry
                                               // (with multiplicity; kQMasked: none) and where one entry equal to its maximum
                                               // sits: (lane of the accumulator << 4) | register, lane = 32 (row bit 2) + column
   size_t common_total;
   // ---- dense / exact-screening / conf_matrix only ----
-  size_t hi0, lo0, hi1, lo1;                  // float16 planes
-  size_t f16inv;                              // [N] 1 / (power-of-two scales of the two images' float16 planes)
-  size_t rowB, colB;                          // partial sum-exp of the dense sum kernel: rows [N][splits][Lp],
+  Region<_Float16> hi0, lo0, hi1, lo1;        // float16 planes
+  Region<float> f16inv;                       // [N] 1 / (power-of-two scales of the two images' float16 planes)
+  Region<float> rowB, colB;                   // partial sum-exp of the dense sum kernel: rows [N][splits][Lp],
                                               // columns [N][panels][Sp] (one partial per workgroup)
-  size_t rsum, csum;                          // softmax denominators per row / column
-  size_t nmr2, nmc2;                          // nmr - log2(rsum), nmc - log2(csum): log-softmax offsets
-  size_t cand_j_b, cand_x_b, ccand_i_b, ccand_x_b;   // ... the dense kernel's candidate set (samples it redid)
+  Region<float> rsum, csum;                   // softmax denominators per row / column
+  Region<float> nmr2, nmc2;                   // nmr - log2(rsum), nmc - log2(csum): log-softmax offsets
   size_t total;
 };
 
@@ -116,13 +129,6 @@ struct CoarseWs {
 int choose_splits(int N, int panels, int tiles, int target = 256);
 // (alone: FM_MODE_ALONE - launch geometry only, the offsets and sizes do not depend on it)
 CoarseWs coarse_layout(int N, int L, int S, int C, int slots, bool alone = false);
-
-struct Scalars {          // lives at ws.scalars (zeroed per call)
-  unsigned flags;         // FM_DEV_* bits
-  int dense_units;        // 32x32 units the sparse sum kernel left to the dense one (0: that kernel exits at once)
-  int cert_units;         // live units k_screen_rows resolved from the max pass's certificate (counted only while
-                          // fm_debug_unit_cert forces the certificate on)
-};
 
 // fm_debug_unit_cert: 0 = the launch plan decides, 1 = never, 2 = always.  The plan takes the top-2 epilogue where the
 // shape allows it (CoarseWs::top2) and the call runs the common path: with FM_MODE_DENSE / FM_MODE_FLAT / every row's
@@ -133,6 +139,17 @@ extern int g_unit_cert;
 inline bool unit_cert_on(const CoarseWs& w, bool common_path = true) {
   return g_unit_cert == 2 || (g_unit_cert == 0 && w.top2 != 0 && common_path);
 }
+
+// One coarse call as the C ABI takes it (fmatch.h: fm_coarse_match_dtype's arguments, in their order)
+struct CoarseCall {
+  const void *feat0, *feat1; int in_dtype;
+  int N, L, S, C, h0c, w0c, h1c, w1c;
+  float temperature, thr; int border_rm; float scale_px; const float *scale0, *scale1;
+  void* workspace; size_t workspace_bytes;
+  int cand_slots, mode;
+  int64_t *b_ids, *i_ids, *j_ids; float *mkpts0_c, *mkpts1_c, *mconf; int cap; int32_t* d_count; float* conf_matrix;
+  void* stream;
+};
 
 // ---- launchers (each enqueues on `st`, returns hipGetLastError()) ----
 hipError_t launch_prep(const void* feat0, const void* feat1, int in_dtype, int c_in, const CoarseWs& w, char* base,
@@ -154,10 +171,7 @@ struct MapCopyJob {
 };
 // what the assignment launch is told about the launches before it (SelArgs: exact, dense_enabled, cell_maps, sums_ready)
 struct SelectFlags { bool exact, dense, cell_maps, sums_ready; };
-hipError_t launch_select(const CoarseWs& w, char* base, int h0c, int w0c, int h1c, int w1c, float inv_ct, float thr, int border,
-                         float scale_px, const float* scale0, const float* scale1,
-                         int64_t* b_ids, int64_t* i_ids, int64_t* j_ids, float* k0, float* k1,
-                         float* mconf, int cap, int32_t* d_count, SelectFlags flags, hipStream_t st,
+hipError_t launch_select(const CoarseWs& w, char* base, const CoarseCall& c, float inv_ct, SelectFlags flags,
                          const MapCopyJob* job = nullptr);
 hipError_t launch_conf_patch(const CoarseWs& w, char* base, float inv_ct, float* conf, hipStream_t st);
 hipError_t launch_exact_lists(const CoarseWs& w, char* base, float inv_ct, const void* feat0, const void* feat1, int in_dtype,

@@ -14,6 +14,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libfmatch_hip.so")
 
 FM_OK = 0
 FM_F32, FM_F16, FM_BF16 = 0, 1, 2     # enum fm_dtype
+FM_E_UNSUPPORTED = -3
 FM_E_CAPACITY = -5
 FM_E_CANDIDATES = -6
 FM_E_RANGE = -7

@@ -31,6 +31,11 @@ from . import ops
 logger = logging.getLogger("featurematching_amd")
 
 
+def _wants_grad(*tensors, training: bool = False) -> bool:
+    """autograd will ask for a gradient through these tensors (or the module trains) - the kernels with a HIP backward"""
+    return torch.is_grad_enabled() and (training or any(t.requires_grad for t in tensors))
+
+
 class CoarseMatching(nn.Module):
     """`conf_matrix=True` also materialises the dense data['conf_matrix'] [N,L,S] the reference
     always writes (coarse_matching_new.py:70; only its training loss reads it) - one more sweep and
@@ -74,7 +79,7 @@ class CoarseMatching(nn.Module):
             data['_fm_coarse_loss'] = (out['_coarse_buffers'], feat_c0, feat_c1)
         if self.conf_matrix:
             conf = out['conf_matrix']
-            if torch.is_grad_enabled() and (feat_c0.requires_grad or feat_c1.requires_grad):
+            if _wants_grad(feat_c0, feat_c1):
                 conf = ops.attach_conf_matrix_grad(feat_c0, feat_c1, conf, self.temperature, out['_coarse_buffers'])
             data.update({'conf_matrix': conf})
         mconf = out['mconf']
@@ -261,7 +266,7 @@ class FinePreprocess(nn.Module):
         require grad under grad mode take the torch layers) on maps with 64 fine channels and W in {5,7}: both maps
         NCHW-contiguous, or both channels-last with one element type out of float32 / float16 / bfloat16 (read in
         place: no layout copy, no up-cast pass)."""
-        wants_grad = torch.is_grad_enabled() and any(t.requires_grad for t in (feat_f0, feat_f1, feat_c0, feat_c1))
+        wants_grad = _wants_grad(feat_f0, feat_f1, feat_c0, feat_c1)
         nchw = feat_f0.is_contiguous() and feat_f1.is_contiguous()
         return self.fused_merge and not self.training and not wants_grad and self.d_model_f == 64 and W in (5, 7) \
             and feat_f0.shape[1] == 64 and (nchw or self._both_channels_last(feat_f0, feat_f1))
@@ -293,7 +298,7 @@ class FinePreprocess(nn.Module):
         self._ctx_ready = None
         if not (self.cat_c_feat and self.fused_merge and not self.training and feat_c0.is_cuda):
             return
-        if torch.is_grad_enabled() and (feat_c0.requires_grad or feat_c1.requires_grad):
+        if _wants_grad(feat_c0, feat_c1):
             return
         with torch.no_grad():
             _, e_w, e_b = self._merge_constants()
@@ -340,7 +345,7 @@ class FinePreprocess(nn.Module):
                     win0 = ops.gather_merge_windows(feat_f0, packed, ctx0, b_ids, i_ids, W, stride, hw0_c[0], hw0_c[1])
                     win1 = ops.gather_merge_windows(feat_f1, packed, ctx1, b_ids, j_ids, W, stride, hw1_c[0], hw1_c[1])
             return win0, win1
-        if torch.is_grad_enabled() and (self.training or feat_f0.requires_grad or feat_f1.requires_grad):
+        if _wants_grad(feat_f0, feat_f1, training=self.training):
             # the crop with its HIP backward (fm_gather_windows_backward): the fine loss reaches the fine maps
             win0 = ops.gather_windows_grad(feat_f0, b_ids, i_ids, W, stride, hw0_c[1], hw0_c[0], cells=cells0)
             win1 = ops.gather_windows_grad(feat_f1, b_ids, j_ids, W, stride, hw1_c[1], hw1_c[0], cells=cells1)
@@ -391,7 +396,7 @@ class FineMatching(nn.Module):
             data.update({'expec_f': torch.empty(0, 3, device=feat_f0.device),
                          'mkpts0_f': data['mkpts0_c'], 'mkpts1_f': data['mkpts1_c']})
             return
-        if torch.is_grad_enabled() and (self.training or feat_f0.requires_grad or feat_f1.requires_grad):
+        if _wants_grad(feat_f0, feat_f1, training=self.training):
             mix = [torch.cat([lin.weight.view(-1), lin.bias]) for lin in (self.mix_feat_0, self.mix_feat_1)]
             k0, k1 = ops.fine_match_grad(feat_f0, feat_f1, mix[0], mix[1], data['mkpts0_c'], data['mkpts1_c'], scale)
         else:

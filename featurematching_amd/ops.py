@@ -7,6 +7,7 @@ torch stream of the inputs' device.
 from __future__ import annotations
 
 import ctypes as C
+import functools
 from dataclasses import dataclass
 from typing import Optional
 
@@ -15,8 +16,11 @@ import torch
 from . import _lib
 
 
+_P = C.c_void_p
+
+
 def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else C.c_void_p(t.data_ptr())
+    return None if t is None else _P(t.data_ptr())
 
 
 def _stream(device) -> C.c_void_p:
@@ -26,27 +30,49 @@ def _stream(device) -> C.c_void_p:
 _DTYPES = {torch.float32: _lib.FM_F32, torch.float16: _lib.FM_F16, torch.bfloat16: _lib.FM_BF16}
 
 
+def _on_gpu(t: torch.Tensor, name: str) -> torch.Tensor:
+    if not t.is_cuda:
+        raise RuntimeError(f"{name} must live on the GPU: the HIP path has no CPU fallback")
+    return t
+
+
 def _desc(t: torch.Tensor, name: str) -> torch.Tensor:
     """Coarse descriptors go to the kernels in the type they come in (float32, float16 or bfloat16: no up-cast
     pass); anything else is converted to float32."""
-    if not t.is_cuda:
-        raise RuntimeError(f"{name} must live on the GPU: the HIP path has no CPU fallback")
-    if t.dtype not in _DTYPES:
+    if _on_gpu(t, name).dtype not in _DTYPES:
         t = t.float()
     return t.contiguous()
 
 
 def _f32c(t: torch.Tensor, name: str) -> torch.Tensor:
-    if not t.is_cuda:
-        raise RuntimeError(f"{name} must live on the GPU: the HIP path has no CPU fallback")
-    if t.dtype != torch.float32:
+    if _on_gpu(t, name).dtype != torch.float32:
         t = t.float()
     return t.contiguous()
 
 
+def _aligned(ws: torch.Tensor) -> C.c_void_p:
+    """the first 256-byte aligned address inside a byte buffer"""
+    return C.c_void_p(ws.data_ptr() + (-ws.data_ptr()) % 256)
+
+
+def _aligned_workspace(nbytes: int, device):
+    """(buffer, 256-byte aligned address) of at least nbytes of device memory"""
+    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
+    return ws, _aligned(ws)
+
+
+@functools.lru_cache(maxsize=256)
+def _workspace_bytes(query: str, *args) -> int:
+    """fm_coarse_workspace_bytes_mode / _auto: a pure function of its arguments, asked once per distinct call"""
+    nb = C.c_size_t(0)
+    _lib.check(getattr(_lib.load(), query)(*args, C.byref(nb)), query)
+    return int(nb.value)
+
+
 @dataclass
 class CoarseBuffers:
-    """Capacity-sized device outputs of the coarse stage plus the device-side count."""
+    """Capacity-sized device outputs of the coarse stage plus the device-side count, and what the call that filled
+    them ran with (coarse_match_async / coarse_match write every field below `conf_matrix`)."""
     b_ids: torch.Tensor
     i_ids: torch.Tensor
     j_ids: torch.Tensor
@@ -57,6 +83,16 @@ class CoarseBuffers:
     cap: int
     workspace: torch.Tensor   # kept alive until the stream has consumed it
     conf_matrix: Optional[torch.Tensor] = None   # dense [N,L,S] when requested
+    _shape: tuple = ()                 # (N, L, S, C, candidate slots) the workspace is laid out for
+    _has_cell_maps: bool = False       # the call did not run with FM_MODE_NO_CELL_MAPS
+    _has_stats: bool = False           # the call ran with stats=True or conf_matrix=True
+    _temperature: float = 0.1
+    info: int = 0                      # raw FM_DEV_* bits (read_count, coarse_match)
+    hint: int = 0                      # coarse_match: mode bits + slots of the attempt that served the call
+    attempts: int = 0                  # coarse_match: attempts fm_coarse_match_auto made
+    side_scratch: Optional[torch.Tensor] = None   # coarse_match_async(side_map=...): image 1's channels-last copy
+    _side_map: Optional[torch.Tensor] = None
+    _keep: tuple = ()                  # inputs must outlive the enqueued kernels
 
     def read_count(self) -> int:
         """The single host sync of the path: returns M (raises on a device-side status)."""
@@ -70,42 +106,82 @@ class CoarseBuffers:
             raise err
         return int(m.value)
 
+    def _workspace_query(self, query: str, *kinds):
+        """the six values (addresses, and pitches where `kinds` says c_int) a layout query of the workspace returns"""
+        outs = [kind() for kind in kinds]
+        _lib.check(getattr(_lib.load(), query)(_aligned(self.workspace), *self._shape, *map(C.byref, outs)), query)
+        return [o.value for o in outs]
+
     def cell_maps(self):
         """((map0, pitch0, ties0), (map1, pitch1, ties1)): device addresses of the cell -> match-index+1
         maps and tie lists of image 0 and image 1 inside the workspace (valid while this object is alive);
         feed them to gather_windows(cells=...) for the cell-ordered crops."""
-        lib = _lib.load()
-        if not getattr(self, '_has_cell_maps', True):
+        if not self._has_cell_maps:
             raise RuntimeError("this coarse call ran with cell_maps=False (FM_MODE_NO_CELL_MAPS)")
-        n, l, s, c, slots = self._shape
-        p0, p1, t0, t1 = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
-        q0, q1 = C.c_int(), C.c_int()
-        base = self.workspace.data_ptr() + ((-self.workspace.data_ptr()) % 256)
-        _lib.check(lib.fm_coarse_cell_maps(C.c_void_p(base), n, l, s, c, slots, C.byref(p0), C.byref(q0), C.byref(t0),
-                                           C.byref(p1), C.byref(q1), C.byref(t1)), "fm_coarse_cell_maps")
-        return (p0.value, q0.value, t0.value), (p1.value, q1.value, t1.value)
+        v = self._workspace_query("fm_coarse_cell_maps", _P, C.c_int, _P, _P, C.c_int, _P)
+        return tuple(v[:3]), tuple(v[3:])
 
     def softmax_stats(self):
         """(nm_r, sum_r, pitch_r, nm_c, sum_c, pitch_c): device addresses of the stabilisers and denominators of every
         row / column inside the workspace (fm_coarse_softmax_stats; valid while this object is alive).  Needs
         stats=True or conf_matrix=True."""
-        if not getattr(self, '_has_stats', False):
+        if not self._has_stats:
             raise RuntimeError("this coarse call ran without stats=True / conf_matrix=True: no softmax statistics")
-        lib = _lib.load()
-        n, l, s, c, slots = self._shape
-        nr, sr, nc, sc = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
-        qr, qc = C.c_int(), C.c_int()
-        base = self.workspace.data_ptr() + ((-self.workspace.data_ptr()) % 256)
-        _lib.check(lib.fm_coarse_softmax_stats(C.c_void_p(base), n, l, s, c, slots, C.byref(nr), C.byref(sr), C.byref(qr),
-                                               C.byref(nc), C.byref(sc), C.byref(qc)), "fm_coarse_softmax_stats")
-        return C.c_void_p(nr.value), C.c_void_p(sr.value), qr.value, C.c_void_p(nc.value), C.c_void_p(sc.value), qc.value
+        nr, sr, qr, nc, sc, qc = self._workspace_query("fm_coarse_softmax_stats", _P, _P, C.c_int, _P, _P, C.c_int)
+        return _P(nr), _P(sr), qr, _P(nc), _P(sc), qc
 
     def sliced(self, m: int) -> dict:
         return dict(b_ids=self.b_ids[:m], i_ids=self.i_ids[:m], j_ids=self.j_ids[:m],
                     mkpts0_c=self.mkpts0_c[:m], mkpts1_c=self.mkpts1_c[:m], mconf=self.mconf[:m])
 
 
-_WS_BYTES = {}       # (N, L, S, C, slots, mode, conf) -> fm_coarse_workspace_bytes_mode
+def _mode_word(exact_screening=None, dense=None, exact_step=None, flat=None, stats=None, alone=None,
+               cell_maps=True) -> int:
+    """the `mode` argument of the coarse calls: None and False both leave a bit off; cell_maps=False sets its bit"""
+    flags = ((exact_screening, _lib.FM_MODE_EXACT_SCREENING), (dense, _lib.FM_MODE_DENSE),
+             (exact_step, _lib.FM_MODE_EXACT_STEP), (flat, _lib.FM_MODE_FLAT), (stats, _lib.FM_MODE_STATS),
+             (alone, _lib.FM_MODE_ALONE), (not cell_maps, _lib.FM_MODE_NO_CELL_MAPS))
+    return sum(bit for on, bit in flags if on)
+
+
+def _coarse_inputs(feat_c0, feat_c1, scale0, scale1):
+    """(f0, f1, scale0, scale1, (N, L, S, C)) as the coarse calls read them: descriptors of one element type,
+    contiguous, float32 scales on the descriptors' device"""
+    f0 = _desc(feat_c0, "feat_c0")
+    f1 = _desc(feat_c1, "feat_c1")
+    if f1.dtype != f0.dtype:
+        f1 = f1.to(f0.dtype)
+    n, l, c = f0.shape
+    if f1.shape[0] != n or f1.shape[2] != c:
+        raise ValueError(f"feat_c0 {tuple(f0.shape)} and feat_c1 {tuple(f1.shape)} disagree")
+    sc0 = None if scale0 is None else _f32c(scale0.to(f0.device), "scale0")
+    sc1 = None if scale1 is None else _f32c(scale1.to(f0.device), "scale1")
+    return f0, f1, sc0, sc1, (n, l, f1.shape[1], c)
+
+
+def _coarse_call(inputs, hw0_c, hw1_c, scale_px, thr, border_rm, temperature, ws_bytes, slots, mode, cap, conf):
+    """(CoarseBuffers for `cap` matches on a fresh workspace of ws_bytes, the leading arguments fm_coarse_match_dtype,
+    fm_coarse_match_maps and fm_coarse_match_auto share)"""
+    f0, f1, sc0, sc1, (n, l, s, c) = inputs
+    dev = f0.device
+    # (one block for the workspace and the outputs, carved into typed views, was tried: the slicing costs a module
+    # caller more than the nine allocations it replaces - 5.1 k against 6.4 k pairs/s)
+    ws, ws_ptr = _aligned_workspace(ws_bytes, dev)
+    i64 = dict(dtype=torch.int64, device=dev)
+    f32 = dict(dtype=torch.float32, device=dev)
+    out = CoarseBuffers(torch.empty(cap, **i64), torch.empty(cap, **i64), torch.empty(cap, **i64),
+                        torch.empty(cap, 2, **f32), torch.empty(cap, 2, **f32), torch.empty(cap, **f32),
+                        torch.empty(2, dtype=torch.int32, device=dev), cap, ws, conf,
+                        _shape=(n, l, s, c, slots), _has_cell_maps=not mode & _lib.FM_MODE_NO_CELL_MAPS,
+                        _has_stats=bool(mode & _lib.FM_MODE_STATS or conf is not None),
+                        _temperature=float(temperature),
+                        _keep=(f0, f1, sc0, sc1))
+    args = (_ptr(f0), _ptr(f1), _DTYPES[f0.dtype], n, l, s, c, int(hw0_c[0]), int(hw0_c[1]), int(hw1_c[0]),
+            int(hw1_c[1]), float(temperature), float(thr), int(border_rm), float(scale_px),
+            _ptr(sc0), _ptr(sc1), ws_ptr, ws_bytes, slots, mode,
+            _ptr(out.b_ids), _ptr(out.i_ids), _ptr(out.j_ids), _ptr(out.mkpts0_c),
+            _ptr(out.mkpts1_c), _ptr(out.mconf), cap, _ptr(out.count), _ptr(conf))
+    return out, args
 
 
 def coarse_match_async(feat_c0: torch.Tensor, feat_c1: torch.Tensor, hw0_c, hw1_c, scale_px: float,
@@ -137,51 +213,19 @@ def coarse_match_async(feat_c0: torch.Tensor, feat_c1: torch.Tensor, hw0_c, hw1_
     `alone` (FM_MODE_ALONE): this call has the GPU to itself - launches that cannot fill the chip take the grid that is
     fastest for the kernel alone instead of the small footprint that leaves room for other streams' kernels."""
     lib = _lib.load()
-    f0 = _desc(feat_c0, "feat_c0")
-    f1 = _desc(feat_c1, "feat_c1")
-    if f1.dtype != f0.dtype:
-        f1 = f1.to(f0.dtype)
-    n, l, c = f0.shape
-    s = f1.shape[1]
-    if f1.shape[0] != n or f1.shape[2] != c:
-        raise ValueError(f"feat_c0 {tuple(f0.shape)} and feat_c1 {tuple(f1.shape)} disagree")
-    dev = f0.device
+    inputs = _coarse_inputs(feat_c0, feat_c1, scale0, scale1)
+    n, l, s, c = inputs[4]
+    dev = inputs[0].device
     if cap is None:
         cap = n * min(l, s)
     if cand_slots is None:
         cand_slots = lib.fm_default_cand_slots(float(thr))
-    mode = (_lib.FM_MODE_EXACT_SCREENING if exact_screening else 0) | (_lib.FM_MODE_DENSE if dense else 0) | \
-           (0 if cell_maps else _lib.FM_MODE_NO_CELL_MAPS) | (_lib.FM_MODE_EXACT_STEP if exact_step else 0) | \
-           (_lib.FM_MODE_STATS if stats else 0) | (_lib.FM_MODE_FLAT if flat else 0) | (_lib.FM_MODE_ALONE if alone else 0)
-    wkey = (n, l, s, c, cand_slots, mode, bool(conf_matrix))
-    ws_bytes = _WS_BYTES.get(wkey)
-    if ws_bytes is None:                       # (a pure function of the shapes: asked once per shape)
-        nb = C.c_size_t(0)
-        _lib.check(lib.fm_coarse_workspace_bytes_mode(n, l, s, c, cand_slots, mode, int(bool(conf_matrix)), C.byref(nb)),
-                   "fm_coarse_workspace_bytes_mode")
-        if len(_WS_BYTES) > 256:
-            _WS_BYTES.clear()
-        ws_bytes = _WS_BYTES[wkey] = int(nb.value)
-    nbytes = C.c_size_t(ws_bytes)
-    # (one block for the workspace and the outputs, carved into typed views, was tried: the slicing costs a module
-    # caller more than the nine allocations it replaces - 5.1 k against 6.4 k pairs/s)
-    ws = torch.empty(nbytes.value + 256, dtype=torch.uint8, device=dev)
-    off = (-ws.data_ptr()) % 256
-    ws_ptr = C.c_void_p(ws.data_ptr() + off)
-    i64 = dict(dtype=torch.int64, device=dev)
-    f32 = dict(dtype=torch.float32, device=dev)
-    out = CoarseBuffers(torch.empty(cap, **i64), torch.empty(cap, **i64), torch.empty(cap, **i64),
-                        torch.empty(cap, 2, **f32), torch.empty(cap, 2, **f32), torch.empty(cap, **f32),
-                        torch.empty(2, dtype=torch.int32, device=dev), cap, ws)
-    if conf_matrix:      # data['conf_matrix'] (coarse_matching_new.py:70): one more sweep + N*L*S*4 bytes
-        out.conf_matrix = torch.empty(n, l, s, dtype=torch.float32, device=dev)
-    sc0 = None if scale0 is None else _f32c(scale0.to(dev), "scale0")
-    sc1 = None if scale1 is None else _f32c(scale1.to(dev), "scale1")
-    args = (_ptr(f0), _ptr(f1), _DTYPES[f0.dtype], n, l, s, c, int(hw0_c[0]), int(hw0_c[1]), int(hw1_c[0]),
-            int(hw1_c[1]), float(temperature), float(thr), int(border_rm), float(scale_px),
-            _ptr(sc0), _ptr(sc1), ws_ptr, nbytes.value, cand_slots, mode,
-            _ptr(out.b_ids), _ptr(out.i_ids), _ptr(out.j_ids), _ptr(out.mkpts0_c),
-            _ptr(out.mkpts1_c), _ptr(out.mconf), cap, _ptr(out.count), _ptr(out.conf_matrix))
+    mode = _mode_word(exact_screening, dense, exact_step, flat, stats, alone, cell_maps)
+    ws_bytes = _workspace_bytes("fm_coarse_workspace_bytes_mode", n, l, s, c, cand_slots, mode, int(bool(conf_matrix)))
+    # data['conf_matrix'] (coarse_matching_new.py:70): one more sweep + N*L*S*4 bytes
+    conf = torch.empty(n, l, s, dtype=torch.float32, device=dev) if conf_matrix else None
+    out, args = _coarse_call(inputs, hw0_c, hw1_c, scale_px, thr, border_rm, temperature, ws_bytes, cand_slots, mode,
+                             cap, conf)
     if side_map is not None:
         if not (side_map.is_cuda and side_map.dtype == torch.float32 and side_map.dim() == 4 and side_map.shape[1] == 64
                 and side_map.is_contiguous()):
@@ -191,16 +235,10 @@ def coarse_match_async(feat_c0: torch.Tensor, feat_c1: torch.Tensor, hw0_c, hw1_
             side_scratch = torch.empty(need, dtype=torch.uint8, device=dev)
         st = lib.fm_coarse_match_maps(*args, _ptr(side_map), int(side_map.shape[0]), 64, int(side_map.shape[2]),
                                       int(side_map.shape[3]), _ptr(side_scratch), _stream(dev))
-        out.side_scratch = side_scratch
-        out._side_map = side_map
+        out.side_scratch, out._side_map = side_scratch, side_map
     else:
         st = lib.fm_coarse_match_dtype(*args, _stream(dev))
     _lib.check(st, "fm_coarse_match_dtype")
-    out._keep = (f0, f1, sc0, sc1)   # inputs must outlive the enqueued kernels
-    out._shape = (n, l, s, c, cand_slots)
-    out._has_cell_maps = bool(cell_maps)
-    out._has_stats = bool(stats or conf_matrix)
-    out._temperature = float(temperature)
     return out
 
 
@@ -278,7 +316,6 @@ MODE_MEMORY = HintMemory()
 # how often a correct-but-slow route served a call in this process (bench.py prints them in `extra.slow_paths`, so a
 # silent detour shows in the record): the torch formula of the conf_matrix backward (three [N,L,S] temporaries)
 SLOW_PATHS = {"conf_matrix_grad_torch_formula": 0}
-_AUTO_WS_BYTES = {}
 
 
 def coarse_match(feat_c0, feat_c1, hw0_c, hw1_c, scale_px, thr=0.2, border_rm=2, temperature=0.1,
@@ -296,51 +333,22 @@ def coarse_match(feat_c0, feat_c1, hw0_c, hw1_c, scale_px, thr=0.2, border_rm=2,
     demo/demo.py:95-116 - so its launches take the grids that are fastest for a kernel alone on the device; a process
     that runs several such calls side by side (threads, streams) passes alone=False."""
     lib = _lib.load()
-    f0 = _desc(feat_c0, "feat_c0")
-    f1 = _desc(feat_c1, "feat_c1")
-    if f1.dtype != f0.dtype:
-        f1 = f1.to(f0.dtype)
-    n, l, c = f0.shape
-    s = f1.shape[1]
-    if f1.shape[0] != n or f1.shape[2] != c:
-        raise ValueError(f"feat_c0 {tuple(f0.shape)} and feat_c1 {tuple(f1.shape)} disagree")
-    dev = f0.device
-    key = hint_key(feat_c0.shape, feat_c1.shape, thr, temperature, f0.dtype, conf_matrix, stats)
+    inputs = _coarse_inputs(feat_c0, feat_c1, scale0, scale1)
+    n, l, s, c = inputs[4]
+    dev = inputs[0].device
+    key = hint_key(feat_c0.shape, feat_c1.shape, thr, temperature, inputs[0].dtype, conf_matrix, stats)
     managed = exact_screening is None and dense is None and exact_step is None and flat is None
-    mode = (_lib.FM_MODE_EXACT_SCREENING if exact_screening else 0) | (_lib.FM_MODE_DENSE if dense else 0) | \
-           (_lib.FM_MODE_EXACT_STEP if exact_step else 0) | (_lib.FM_MODE_FLAT if flat else 0) | \
-           (0 if cell_maps else _lib.FM_MODE_NO_CELL_MAPS) | (_lib.FM_MODE_STATS if stats else 0) | \
-           (_lib.FM_MODE_ALONE if alone else 0)
+    mode = _mode_word(exact_screening, dense, exact_step, flat, stats, alone, cell_maps)
     hint0, probing = MODE_MEMORY.start(key) if managed else (0, False)
-    sc0 = None if scale0 is None else _f32c(scale0.to(dev), "scale0")
-    sc1 = None if scale1 is None else _f32c(scale1.to(dev), "scale1")
-    i64 = dict(dtype=torch.int64, device=dev)
-    f32 = dict(dtype=torch.float32, device=dev)
     cap = n * min(l, s)
     max_slots = 16                      # (64 only when 16 slots and the exact re-screening still overflow: thr < 1/16)
-    conf = torch.empty(n, l, s, **f32) if conf_matrix else None
+    conf = torch.empty(n, l, s, dtype=torch.float32, device=dev) if conf_matrix else None
     for _ in range(4):
-        wkey = (n, l, s, c, max_slots)
-        ws_bytes = _AUTO_WS_BYTES.get(wkey)
-        if ws_bytes is None:
-            nb = C.c_size_t(0)
-            _lib.check(lib.fm_coarse_workspace_bytes_auto(n, l, s, c, max_slots, C.byref(nb)), "fm_coarse_workspace_bytes_auto")
-            if len(_AUTO_WS_BYTES) > 256:
-                _AUTO_WS_BYTES.clear()
-            ws_bytes = _AUTO_WS_BYTES[wkey] = int(nb.value)
-        ws = torch.empty(ws_bytes + 256, dtype=torch.uint8, device=dev)
-        off = (-ws.data_ptr()) % 256
-        out = CoarseBuffers(torch.empty(cap, **i64), torch.empty(cap, **i64), torch.empty(cap, **i64),
-                            torch.empty(cap, 2, **f32), torch.empty(cap, 2, **f32), torch.empty(cap, **f32),
-                            torch.empty(2, dtype=torch.int32, device=dev), cap, ws)
-        out.conf_matrix = conf
+        ws_bytes = _workspace_bytes("fm_coarse_workspace_bytes_auto", n, l, s, c, max_slots)
+        out, args = _coarse_call(inputs, hw0_c, hw1_c, scale_px, thr, border_rm, temperature, ws_bytes, max_slots, mode,
+                                 cap, conf)
         hint, m, info = C.c_int32(hint0), C.c_int32(0), C.c_int32(0)
-        st = lib.fm_coarse_match_auto(_ptr(f0), _ptr(f1), _DTYPES[f0.dtype], n, l, s, c, int(hw0_c[0]), int(hw0_c[1]),
-                                      int(hw1_c[0]), int(hw1_c[1]), float(temperature), float(thr), int(border_rm),
-                                      float(scale_px), _ptr(sc0), _ptr(sc1), C.c_void_p(ws.data_ptr() + off), ws_bytes,
-                                      max_slots, mode, _ptr(out.b_ids), _ptr(out.i_ids), _ptr(out.j_ids),
-                                      _ptr(out.mkpts0_c), _ptr(out.mkpts1_c), _ptr(out.mconf), cap, _ptr(out.count),
-                                      _ptr(conf), C.byref(hint), C.byref(m), C.byref(info), _stream(dev))
+        st = lib.fm_coarse_match_auto(*args, C.byref(hint), C.byref(m), C.byref(info), _stream(dev))
         if st == _lib.FM_E_CAPACITY:
             cap, hint0 = int(m.value), int(hint.value) & 0xffff
             continue
@@ -351,13 +359,8 @@ def coarse_match(feat_c0, feat_c1, hw0_c, hw1_c, scale_px, thr=0.2, border_rm=2,
         if managed:
             MODE_MEMORY.finish(key, int(hint.value))
         h = int(hint.value)
-        slots_used = (h >> 16) & 0xff          # the slot count the serving attempt ran with (always written)
+        out._shape = (n, l, s, c, (h >> 16) & 0xff)  # the slot count the serving attempt ran with (always written)
         out.info, out.hint, out.attempts = int(info.value), h & 0xffff, (h >> 24) & 0xff
-        out._keep = (f0, f1, sc0, sc1)
-        out._shape = (n, l, s, c, slots_used)
-        out._has_cell_maps = bool(cell_maps)
-        out._has_stats = bool(stats or conf_matrix)
-        out._temperature = float(temperature)
         res = out.sliced(int(m.value))
         if conf_matrix:
             res['conf_matrix'] = conf
@@ -366,25 +369,28 @@ def coarse_match(feat_c0, feat_c1, hw0_c, hw1_c, scale_px, thr=0.2, border_rm=2,
     raise RuntimeError("coarse_match: overflow persisted after retries")
 
 
-def _aligned_workspace(nbytes: int, device):
-    """(buffer, 256-byte aligned address) of at least nbytes of device memory"""
-    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
-    return ws, C.c_void_p(ws.data_ptr() + (-ws.data_ptr()) % 256)
-
-
 def _i64c(t: torch.Tensor) -> torch.Tensor:
     """an id list as the library reads it: int64, contiguous"""
     return t.to(torch.int64).contiguous()
+
+
+def _desc_pair(f0, f1):
+    """(x0, x1, N, L, S, C): both descriptor sets as contiguous float32 and their sizes"""
+    x0, x1 = _f32c(f0, "feat_c0"), _f32c(f1, "feat_c1")
+    n, l, c = x0.shape
+    return x0, x1, n, l, x1.shape[1], c
+
+
+def _desc_side(f0, f1, buffers):
+    """what the dual-softmax and coarse-loss calls open with: _desc_pair and the softmax statistics of `buffers`"""
+    return (*_desc_pair(f0, f1), buffers.softmax_stats())
 
 
 def _dsm_backward(f0, f1, temperature, buffers, b_ids, i_ids, j_ids, gc):
     """(dL/df0, dL/df1) of sum_e g_e conf_e from gc = g * conf at the entries (fm_dual_softmax_backward): two launches of
     one tiled kernel that recomputes the similarities tile by tile - no [N, L, S] array."""
     lib = _lib.load()
-    x0, x1 = _f32c(f0, "feat_c0"), _f32c(f1, "feat_c1")
-    n, l, c = x0.shape
-    s = x1.shape[1]
-    stats = buffers.softmax_stats()
+    x0, x1, n, l, s, c, stats = _desc_side(f0, f1, buffers)
     need = int(lib.fm_dual_softmax_backward_workspace_bytes(n, l, s, c))
     ws, wsp = _aligned_workspace(need, x0.device)
     d0, d1 = torch.empty_like(x0), torch.empty_like(x1)
@@ -402,10 +408,7 @@ class _DualSoftmaxAt(torch.autograd.Function):
     @staticmethod
     def forward(ctx, feat_c0, feat_c1, b_ids, i_ids, j_ids, temperature, buffers):
         lib = _lib.load()
-        x0, x1 = _f32c(feat_c0, "feat_c0"), _f32c(feat_c1, "feat_c1")
-        n, l, c = x0.shape
-        s = x1.shape[1]
-        stats = buffers.softmax_stats()
+        x0, x1, n, l, s, c, stats = _desc_side(feat_c0, feat_c1, buffers)
         k = int(b_ids.shape[0])
         bb, ii, jj = _i64c(b_ids), _i64c(i_ids), _i64c(j_ids)
         conf = torch.empty(k, dtype=torch.float32, device=x0.device)
@@ -435,11 +438,8 @@ def _dsm_backward_dense(f0, f1, temperature, buffers, grad):
     """(dL/df0, dL/df1) for a DENSE dL/dconf (fm_dual_softmax_backward_dense): three tiled sweeps that recompute conf from
     exact float32 dot products and the forward call's softmax statistics - no [N, L, S] temporary."""
     lib = _lib.load()
-    x0, x1 = _f32c(f0, "feat_c0"), _f32c(f1, "feat_c1")
-    n, l, c = x0.shape
-    s = x1.shape[1]
+    x0, x1, n, l, s, c, stats = _desc_side(f0, f1, buffers)
     g = _f32c(grad, "grad")
-    stats = buffers.softmax_stats()
     need = int(lib.fm_dual_softmax_backward_workspace_bytes(n, l, s, c))
     ws, wsp = _aligned_workspace(need, x0.device)
     d0, d1 = torch.empty_like(x0), torch.empty_like(x1)
@@ -536,9 +536,7 @@ class _CoarseLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, feat_c0, feat_c1, bb, ii, jj, buffers, kind, alpha, gamma, pos_weight, neg_weight):
         lib = _lib.load()
-        x0, x1 = _f32c(feat_c0, "feat_c0"), _f32c(feat_c1, "feat_c1")
-        n, l, c = x0.shape
-        s = x1.shape[1]
+        x0, x1, n, l, s, c = _desc_pair(feat_c0, feat_c1)
         k = int(bb.shape[0])
         need = int(lib.fm_coarse_loss_workspace_bytes(n, l, s, c, k))
         ws, wsp = _aligned_workspace(need, x0.device)
@@ -679,12 +677,24 @@ def fine_loss(expec0: torch.Tensor, expec1: torch.Tensor, gt0: torch.Tensor, gt1
     if tuple(gt0.shape) != (m, 2) or tuple(gt1.shape) != (m, 2):
         raise ValueError(f"gt0 / gt1 must be [{m}, 2], got {tuple(gt0.shape)} and {tuple(gt1.shape)}")
     if m == 0:
-        if not expec0.is_cuda:
-            raise RuntimeError("expec0 must live on the GPU: the HIP path has no CPU fallback")
+        _on_gpu(expec0, "expec0")
         return (expec0.sum() + expec1.sum()).float() * 0         # 0, attached to the graph of both inputs; no HIP launch
     loss, out = _FineLoss.apply(expec0, expec1, gt0, gt1, count)
     loss.terms = out[1:]
     return loss
+
+
+def _map_layout(t: torch.Tensor):
+    """(tensor, layout) of a logical [N,Cf,Hf,Wf] fine map as the crop and fine kernels read it: 0 = NCHW-contiguous
+    (any other strides are copied to it), 1 = channels-last storage.  float32, float16 and bfloat16 maps are taken as
+    they are (no up-cast pass)."""
+    if t.dtype not in _DTYPES:
+        t = t.float()
+    if t.is_contiguous():
+        return t, 0
+    if t.is_contiguous(memory_format=torch.channels_last):
+        return t, 1
+    return t.contiguous(), 0
 
 
 def gather_windows(feat_f: torch.Tensor, b_ids: torch.Tensor, ids: torch.Tensor, w: int, stride: int,
@@ -696,17 +706,8 @@ def gather_windows(feat_f: torch.Tensor, b_ids: torch.Tensor, ids: torch.Tensor,
     selects the cell-ordered kernel when the shape allows it (NCHW, Cf 64, W 5/7): the windows are
     visited in raster order of THIS image's cells, which keeps each XCD's reads inside a band of the map."""
     lib = _lib.load()
-    if not feat_f.is_cuda:
-        raise RuntimeError("feat_f must live on the GPU: the HIP path has no CPU fallback")
-    n, cf, hf, wf = feat_f.shape
-    if feat_f.dtype not in _DTYPES:             # float16 / bfloat16 maps go to the kernels as they are (no up-cast pass)
-        feat_f = feat_f.float()
-    if feat_f.is_contiguous():
-        layout = 0
-    elif feat_f.is_contiguous(memory_format=torch.channels_last):
-        layout = 1
-    else:
-        feat_f, layout = feat_f.contiguous(), 0
+    n, cf, hf, wf = _on_gpu(feat_f, "feat_f").shape
+    feat_f, layout = _map_layout(feat_f)
     m_max = int(b_ids.shape[0])
     if out is None:
         out = torch.empty(m_max, w * w, cf, dtype=torch.float32, device=feat_f.device)
@@ -721,7 +722,7 @@ def gather_windows(feat_f: torch.Tensor, b_ids: torch.Tensor, ids: torch.Tensor,
         st = lib.fm_gather_windows_cells(_ptr(feat_f), n, cf, hf, wf, w, stride, pad, int(h_c), int(w_c),
                                          C.c_void_p(cells[0]), int(cells[1]), C.c_void_p(cells[2]), _ptr(b_ids), _ptr(ids),
                                          _ptr(count), m_max, _ptr(out), _stream(feat_f.device))
-        if st != -3:                       # FM_E_UNSUPPORTED: fall through to the per-window kernel
+        if st != _lib.FM_E_UNSUPPORTED:    # fall through to the per-window kernel
             _lib.check(st, "fm_gather_windows_cells")
             return out
     st = lib.fm_gather_windows(_ptr(feat_f), n, cf, hf, wf, layout, w, stride, pad, w_c, _ptr(b_ids), _ptr(ids),
@@ -758,9 +759,7 @@ def gather_merge_windows(feat_f: torch.Tensor, packed_w: torch.Tensor, ctx_bias:
     A channels-last map (float32, float16 or bfloat16) is read in place, in list order (`cells` is ignored); the
     result is bit-identical to the call on the same float32 values stored NCHW."""
     lib = _lib.load()
-    if not feat_f.is_cuda:
-        raise RuntimeError("feat_f must live on the GPU: the HIP path has no CPU fallback")
-    n, cf, hf, wf = feat_f.shape
+    n, cf, hf, wf = _on_gpu(feat_f, "feat_f").shape
     nhwc = merge_reads_in_place(feat_f)
     if not nhwc:
         feat_f = _f32c(feat_f, "feat_f")
@@ -892,13 +891,6 @@ def fine_match_grad(win0: torch.Tensor, win1: torch.Tensor, mix0: torch.Tensor, 
     return _FineMatch.apply(win0, win1, mix0, mix1, mkpts0_c, mkpts1_c, scale_f)
 
 
-def _crop_layout(feat_f: torch.Tensor) -> int:
-    """the layout gather_windows reads a map in: 0 = NCHW (also for any other strides: it copies), 1 = channels-last"""
-    if feat_f.is_contiguous():
-        return 0
-    return 1 if feat_f.is_contiguous(memory_format=torch.channels_last) else 0
-
-
 def gather_windows_backward(d_win: torch.Tensor, b_ids: torch.Tensor, ids: torch.Tensor, shape, w: int, stride: int,
                             w_c: int, h_c: int, pad: int = 2, layout: int = 0,
                             count: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -928,9 +920,10 @@ def gather_windows_backward(d_win: torch.Tensor, b_ids: torch.Tensor, ids: torch
 class _GatherWindows(torch.autograd.Function):
     @staticmethod
     def forward(ctx, feat_f, b_ids, ids, w, stride, w_c, h_c, pad, cells):
-        out = gather_windows(feat_f, b_ids, ids, w, stride, w_c, pad=pad, cells=cells, h_c=h_c)
+        feat, layout = _map_layout(_on_gpu(feat_f, "feat_f"))
+        out = gather_windows(feat, b_ids, ids, w, stride, w_c, pad=pad, cells=cells, h_c=h_c)
         ctx.save_for_backward(b_ids, ids)
-        ctx.args = (tuple(feat_f.shape), w, stride, w_c, h_c, pad, _crop_layout(feat_f), feat_f.dtype)
+        ctx.args = (tuple(feat_f.shape), w, stride, w_c, h_c, pad, layout, feat_f.dtype)
         return out
 
     @staticmethod
@@ -949,18 +942,6 @@ def gather_windows_grad(feat_f: torch.Tensor, b_ids: torch.Tensor, ids: torch.Te
     return _GatherWindows.apply(feat_f, b_ids, ids, w, stride, w_c, h_c, pad, cells)
 
 
-def _map_layout(t: torch.Tensor):
-    """(tensor, layout) of a logical [N,Cf,Hf,Wf] fine map: 0 = NCHW-contiguous, 1 = channels-last storage.  float32,
-    float16 and bfloat16 maps are taken as they are (fm_fine_match_maps_dtype: no up-cast pass)."""
-    if t.dtype not in _DTYPES:
-        t = t.float()
-    if t.is_contiguous():
-        return t, 0
-    if t.is_contiguous(memory_format=torch.channels_last):
-        return t, 1
-    return t.contiguous(), 0
-
-
 def fine_match_maps(feat_f0: torch.Tensor, feat_f1: torch.Tensor, b_ids, i_ids, j_ids, w: int, stride: int, w0c: int,
                     w1c: int, mix0: torch.Tensor, mix1: torch.Tensor, mkpts0_c: torch.Tensor, mkpts1_c: torch.Tensor,
                     scale_f: float, pad: int = 2, count: Optional[torch.Tensor] = None,
@@ -973,9 +954,7 @@ def fine_match_maps(feat_f0: torch.Tensor, feat_f1: torch.Tensor, b_ids, i_ids, 
     float32 maps, image 1's copy exists already - no transpose launch here).
     Returns (mkpts0_f, mkpts1_f), float32."""
     lib = _lib.load()
-    if not feat_f0.is_cuda:
-        raise RuntimeError("feat_f0 must live on the GPU: the HIP path has no CPU fallback")
-    f0, lay0 = _map_layout(feat_f0)
+    f0, lay0 = _map_layout(_on_gpu(feat_f0, "feat_f0"))
     f1, lay1 = _map_layout(feat_f1)
     if f1.dtype != f0.dtype:
         f1 = f1.to(f0.dtype)
@@ -1011,19 +990,26 @@ _TF_NAMES = ("q_proj.weight", "k_proj.weight", "v_proj.weight", "merge.weight", 
              "norm1.weight", "norm1.bias", "norm2.weight", "norm2.bias")
 
 
-def pack_coarse_transformer(state_dict: dict, n_layers: int, device) -> torch.Tensor:
-    """state dict of a coarse LocalFeatureTransformer (d_model 256, 8 heads, `n_layers` encoder layers) -> the
-    A-operand fragments fm_coarse_transformer reads (fm_coarse_tf_pack_weights)."""
-    lib = _lib.load()
-    keep, arrs = [], []
-    want = [(256, 256)] * 4 + [(512, 512), (256, 512)] + [(256,)] * 4
+def _tf_pointer_tables(state_dict: dict, n_layers: int, device, kind: str, d: int):
+    """(tensors to keep alive, per layer the (void* x 10) table of its _TF_NAMES tensors as float32 on `device`) of a
+    LocalFeatureTransformer with d_model `d`"""
+    keep, tables = [], []
+    want = [(d, d)] * 4 + [(2 * d, 2 * d), (d, 2 * d)] + [(d,)] * 4
     for l in range(n_layers):
         ts = [state_dict[f"layers.{l}.{name}"].detach().to(device=device, dtype=torch.float32).contiguous()
               for name in _TF_NAMES]
         if [tuple(t.shape) for t in ts] != want:
-            raise ValueError(f"fm_coarse_transformer serves d_model 256 only, got {[tuple(t.shape) for t in ts]}")
+            raise ValueError(f"fm_{kind}_transformer serves d_model {d} only, got {[tuple(t.shape) for t in ts]}")
         keep.extend(ts)
-        arrs.append((C.c_void_p * 10)(*[t.data_ptr() for t in ts]))
+        tables.append((C.c_void_p * 10)(*[t.data_ptr() for t in ts]))
+    return keep, tables
+
+
+def pack_coarse_transformer(state_dict: dict, n_layers: int, device) -> torch.Tensor:
+    """state dict of a coarse LocalFeatureTransformer (d_model 256, 8 heads, `n_layers` encoder layers) -> the
+    A-operand fragments fm_coarse_transformer reads (fm_coarse_tf_pack_weights)."""
+    lib = _lib.load()
+    keep, arrs = _tf_pointer_tables(state_dict, n_layers, device, "coarse", 256)
     table = (C.POINTER(C.c_void_p) * n_layers)(*[C.cast(a, C.POINTER(C.c_void_p)) for a in arrs])
     nbytes = int(lib.fm_coarse_tf_packed_bytes(n_layers))
     if nbytes == 0:
@@ -1072,17 +1058,7 @@ def pack_fine_transformer(state_dict: dict, device) -> torch.Tensor:
     """state dict of a fine LocalFeatureTransformer (layers.0 = 'self', layers.1 = 'cross'; d_model 64, 8 heads) ->
     the packed operand fragments fm_fine_transformer reads (fm_fine_tf_pack_weights)."""
     lib = _lib.load()
-    keep, arrs = [], []
-    for l in range(2):
-        ptrs = []
-        for name in _TF_NAMES:
-            t = state_dict[f"layers.{l}.{name}"].detach().to(device=device, dtype=torch.float32).contiguous()
-            keep.append(t)
-            ptrs.append(t.data_ptr())
-        arrs.append((C.c_void_p * 10)(*ptrs))
-    shapes = [tuple(t.shape) for t in keep[:10]]
-    if shapes != [(64, 64)] * 4 + [(128, 128), (64, 128)] + [(64,)] * 4:
-        raise ValueError(f"fm_fine_transformer serves d_model 64 only, got {shapes}")
+    keep, arrs = _tf_pointer_tables(state_dict, 2, device, "fine", 64)
     packed = torch.empty(int(lib.fm_fine_tf_packed_bytes()), dtype=torch.uint8, device=device)
     _lib.check(lib.fm_fine_tf_pack_weights(arrs[0], arrs[1], _ptr(packed), _stream(packed.device)), "fm_fine_tf_pack_weights")
     torch.cuda.current_stream(packed.device).synchronize()       # the sources in `keep` may be freed after this

@@ -17,6 +17,29 @@ def declared_symbols(path=("include", "fmatch.h")):
     return sorted(set(re.findall(r"\b(fm_[a-z_0-9]+)\s*\(", text)))
 
 
+def declared_constants(path=("include", "fmatch.h")):
+    """{name: value} of the `#define FM_*` integers and of the enumerators of fm_status / fm_dtype / fm_loss_kind"""
+    text = open(os.path.join(ROOT, *path)).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    vals = {k: int(v) for k, v in re.findall(r"^\s*#\s*define\s+(FM_[A-Z_0-9]+)\s+(-?\d+)\s*$", text, flags=re.M)}
+    for enum in ("fm_status", "fm_dtype", "fm_loss_kind"):
+        body = re.search(r"\benum\s+%s\s*\{(.*?)\}" % enum, text, flags=re.S).group(1)
+        vals.update({k: int(v) for k, v in re.findall(r"\b(FM_[A-Z_0-9]+)\s*=\s*(-?\d+)", body)})
+    return vals
+
+
+def test_constants_match_the_header():
+    """every FM_* number copied by hand into _lib.py is the header's"""
+    header = declared_constants()
+    assert header["FM_OK"] == 0 and header["FM_E_STEP"] == -10 and header["FM_MODE_ALONE"] == 64      # (the parser reads)
+    assert header["FM_BF16"] == 2 and header["FM_LOSS_FOCAL"] == 1 and header["FM_LAYOUT_NCHW_PREPARED"] == 2
+    ours = {k: v for k, v in vars(_lib).items() if k.startswith("FM_")}
+    assert len(ours) >= 20
+    for name, value in ours.items():
+        assert name in header, f"_lib.{name} is not declared in fmatch.h"
+        assert value == header[name], f"_lib.{name} = {value}, fmatch.h says {header[name]}"
+
+
 def test_header_symbols_are_exported():
     lib = _lib.load()
     syms = declared_symbols()

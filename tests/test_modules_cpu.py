@@ -159,3 +159,24 @@ def test_hint_memory_is_bounded_decays_and_forgets():
     assert d['dense'] and not d['flat'] and not d['wide']
     m.clear()
     assert not m.snapshot()
+
+
+def test_mode_word():
+    """ops._mode_word, the one place the coarse calls' `mode` argument is put together: each flag its FM_MODE_* bit,
+    None and False no bit, cell_maps=False the bit that skips the cell maps."""
+    from featurematching_amd import _lib
+    from featurematching_amd.ops import _mode_word
+    bits = {'exact_screening': _lib.FM_MODE_EXACT_SCREENING, 'dense': _lib.FM_MODE_DENSE,
+            'exact_step': _lib.FM_MODE_EXACT_STEP, 'flat': _lib.FM_MODE_FLAT, 'stats': _lib.FM_MODE_STATS,
+            'alone': _lib.FM_MODE_ALONE}
+    assert sorted(bits.values()) == [1, 2, 8, 16, 32, 64] and _lib.FM_MODE_NO_CELL_MAPS == 4
+    assert _mode_word() == 0
+    for name, bit in bits.items():
+        assert _mode_word(**{name: True}) == bit
+        assert _mode_word(**{name: False}) == 0 and _mode_word(**{name: None}) == 0
+    assert _mode_word(cell_maps=False) == _lib.FM_MODE_NO_CELL_MAPS and _mode_word(cell_maps=True) == 0
+    assert _mode_word(**{name: True for name in bits}, cell_maps=False) == 127
+    assert _mode_word(**{name: None for name in bits}) == 0 and _mode_word(**{name: False for name in bits}) == 0
+    # positional order as coarse_match_async and coarse_match pass it
+    assert _mode_word(True, False, None, False, True, False, True) == 1 | 16
+    assert _mode_word(False, True, True, True, False, True, False) == 2 | 8 | 32 | 64 | 4

@@ -60,6 +60,8 @@ SIGNATURES = {
     "fm_debug_reset_counters": (_i, [_p, _i, _i, _i, _i, _i, _p]),
     "fm_debug_unit_cert": (_i, [_i]),
     "fm_debug_unit_cert_layout": (_i, [_i, _i, _i, _i, _i, C.POINTER(C.c_int64), _i]),
+    "fm_debug_defer_exact": (_i, [_i]),
+    "fm_debug_defer_exact_layout": (_i, [_i, _i, _i, _i, _i, C.POINTER(C.c_int64), _i]),
     "fm_read_count": (_i, [_p, _i, C.POINTER(C.c_int32), _p]),
     "fm_read_count_info": (_i, [_p, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _p]),
     "fm_debug_launch_flat": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _f, _f, _i, _p]),

@@ -8,6 +8,7 @@
 namespace fm {
 
 int g_unit_cert = 0;
+int g_defer_exact = 0;
 
 int choose_splits(int N, int panels, int tiles, int target) {
   // One workgroup per (sample, panel, split); aim at one full round of the 256 CUs when the
@@ -201,7 +202,7 @@ struct CoarsePlan {
   bool exact_lists;    // k_exact_lists: the dense kernel's lists and their denominators made exact together
   bool conf;           // the dense conf_matrix sweep and its patch
   bool cell_maps;      // the assignment writes the cell -> match maps
-  SelectFlags select() const { return {rescreen, dense, cell_maps, reduce}; }
+  SelectFlags select(bool deferred) const { return {rescreen, dense, cell_maps, reduce, deferred}; }
   size_t workspace_bytes(const CoarseWs& w) const { return dense ? w.total : w.common_total; }
 };
 
@@ -308,7 +309,9 @@ static int coarse_match_impl(const CoarseCall& c, const MapCopyJob* job, bool re
     // and per column); flags the samples with too many significant entries per unit (flat similarity).  FM_MODE_FLAT:
     // the sweep would only find that out again - a small kernel forms the stabilisers and flags every sample
     if (p.flat) FM_TRY(launch_stab(w, base, inv_ct, c.thr, p.allow_dead, st));
-    else FM_TRY(launch_screen(c.feat0, c.feat1, c.in_dtype, c.C, w, base, inv_ct, c.thr, p.dense, p.allow_dead, st));
+    // (sure entries without their exact dot product only where the assignment is the lists' sole reader: fm_internal.h)
+    else FM_TRY(launch_screen(c.feat0, c.feat1, c.in_dtype, c.C, w, base, inv_ct, c.thr, p.dense, p.allow_dead,
+                              defer_exact_on(w, !p.dense), st));
   } else {
     FM_TRY(clear_spans(base, w.reassign, st));
   }
@@ -327,7 +330,9 @@ static int coarse_match_impl(const CoarseCall& c, const MapCopyJob* job, bool re
     FM_TRY(launch_conf_patch(w, base, inv_ct, c.conf_matrix, st));
   }
 #undef FM_TRY
-  return (int)launch_select(w, base, c, inv_ct, p.select(), job);
+  // (the lists hold tagged entries when this call's screening deferred, or - resume - when the common-path call did
+  // whose results this one continues)
+  return (int)launch_select(w, base, c, inv_ct, p.select(defer_exact_on(w, resume || !p.dense)), job);
 }
 
 extern "C" int fm_coarse_match(const float* feat0, const float* feat1, int N, int L, int S, int C, int h0c, int w0c,
@@ -527,7 +532,7 @@ extern "C" int fm_debug_launch_screen(void* workspace, const float* feat0, const
   CoarseWs w;
   if (const int bad = checked_layout(workspace && feat0 && feat1, N, L, S, C, cand_slots, &w)) return bad;
   return (int)launch_screen(feat0, feat1, FM_F32, C, w, (char*)workspace, inv_ct_of(C, temperature), thr, 1, 1,
-                                (hipStream_t)stream);
+                            defer_exact_on(w), (hipStream_t)stream);
 }
 
 // Diagnostic: launch k_prep_split alone (it clears the per-call counters: run a complete fm_coarse_match afterwards
@@ -584,6 +589,27 @@ extern "C" int fm_debug_unit_cert_layout(int N, int L, int S, int C, int cand_sl
   const int64_t v[9] = {(int64_t)w.umax.at, (int64_t)w.umax2.at, (int64_t)w.upos.at, (int64_t)w.thr_r.at, (int64_t)w.thr_c.at,
                         (int64_t)w.tmin_r.at, (int64_t)w.tmin_c.at, (int64_t)(w.scalars.at + offsetof(Scalars, cert_units)), w.top2};
   for (int i = 0; i < 9; ++i) out[i] = v[i];
+  return FM_OK;
+}
+
+// Test-only switch of the deferred exact dot products (process-global; returns the previous value, mode outside 0..2
+// only reads).
+extern "C" int fm_debug_defer_exact(int mode) {
+  const int prev = g_defer_exact;
+  if (mode >= 0 && mode <= 2) g_defer_exact = mode;
+  return prev;
+}
+
+// Diagnostic: byte offset of the per-call counter of deferred entries, the tag bit of a list index, and whether the
+// common path of this shape defers under the present switch (3 values).
+extern "C" int fm_debug_defer_exact_layout(int N, int L, int S, int C, int cand_slots, int64_t* out, int n_out) {
+  if (!out) return FM_E_NULL;
+  if (n_out < 3) return FM_E_SHAPE;
+  CoarseWs w;
+  if (const int bad = checked_layout(true, N, L, S, C, cand_slots, &w)) return bad;
+  out[0] = (int64_t)(w.scalars.at + offsetof(Scalars, defer_entries));
+  out[1] = 0x40000000;
+  out[2] = defer_exact_on(w) ? 1 : 0;
   return FM_OK;
 }
 

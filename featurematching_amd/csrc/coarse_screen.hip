@@ -25,7 +25,7 @@
 //
 // Kernels (round 5): k_thresh (one thread per row / column: stabilisers, integer thresholds, per-block maxima of them)
 // and k_screen_rows (ONE independent wave per (32-row block, <= 64 column units): live units only, B fragments straight
-// from global memory into registers, no barrier, 4 KiB of LDS per workgroup) - see the block comment in front of them
+// from global memory into registers, no barrier, 12 KiB of LDS per workgroup) - see the block comment in front of them
 // for the one-round-trip, 128-KiB-of-LDS workgroup kernel of round 4 they replace and why.  k_stab serves FM_MODE_FLAT.
 #include <stdlib.h>
 #include <string.h>
@@ -33,6 +33,7 @@
 #include <type_traits>
 
 #include "fm_device.h"
+#include "fm_exact_device.h"
 #include "fm_wave_device.h"
 
 namespace fm {
@@ -41,7 +42,7 @@ constexpr int kMaxExact = 24;         // significant entries of a unit resolved 
 
 struct ScreenArgs {
   const signed char* q0; const signed char* q1;       // int8 screening planes (k_prep_split)
-  const void* src0; const void* src1; int c_in, in_dtype;   // the caller's descriptors [N,L,c_in] / [N,S,c_in]
+  DescRows desc;                                       // the caller's descriptors [N,L,c_in] / [N,S,c_in]
   const unsigned* rowmax_u; const unsigned* colmax_u;  // max pass: q_encode'd maxima of the integer screening product
   const float* sigimg;                                 // [N][2] quantisation step of image 0 / image 1
   const float* imgstat;                                // [N][8] {largest L1 norm, clipped mass, |x|} of image 0, of image 1 (max pass)
@@ -63,6 +64,36 @@ struct ScreenArgs {
 __device__ __forceinline__ int sig_threshold(float nm, float emu, float inv_kss) {
   const float t = floorf((-kSkipLog2 - emu - nm) * inv_kss) - 1.f;
   return (int)fminf(fmaxf(t, -1.0e9f), 1.0e9f);       // (NaN -> -1e9: everything significant)
+}
+
+// Sure entries (deferred exact dot products).  The exact phase lists a parked entry (i, j) with its float32 dot product x
+// in row i's list iff fma(x, k, nmr_i) > -kSkipLog2 and in column j's iff fma(x, k, nmc_j) > -kSkipLog2.  An entry whose
+// INTEGER product q already proves both is listed without the two 1-KiB gathers (k_select forms x if it ever needs it):
+//     q > max(thr_r[i], thr_c[j]) + D        (and both thresholds are real ones, > -1e9: see sig_threshold's NaN case)
+// with one slack D per sample.  Proof for the row (the column is the same with nmc, thr_c):
+//   * thr_r = floor(t) - 1, t = fl((-kSkipLog2 - emu - nmr) / kss), emu the margin of the row's block (k_thresh).  q and
+//     thr_r + D are integers, so q >= floor(t) + D > t - 1 + D:   kss q > (-kSkipLog2 - emu - nmr) + kss (D - 1) - r1,
+//     r1 = the roundings of t (four operations on a quantity <= kSkipLog2 + emu + |nmr|).
+//   * the int8 product is within the pair margin of the real dot product x* (fm_device.h; its factor 1.0001 covers the
+//     roundings of kss and of the scaled product):   k x* >= kss q - emarg,   and emu <= emarg (the same monotone float
+//     expression on a block's largest L1 norm instead of the image's).
+//   * float32 x against x*: 16 fmas and 4 additions per lane, |x - x*| <= 20 u sum|a_k b_k| <= 20 u l1A_max infB
+//     (u = 2^-24; float16 / bfloat16 rows convert exactly); the filter's own fma rounds once more: u |k x + nmr|.
+//   Together:  fma(x, k, nmr) > -kSkipLog2 + kss (D - 1) - 2 emarg - r,   r <= 30 u P + 10 u (kSkipLog2 + 2 emarg + 1),
+//   P = k l1A_max infB  (|nmr| <= P + emarg + 1: the stabiliser is a screening product less a margin).  With emarg < 60
+//   (k_thresh reports FM_DEV_RANGE / FM_DEV_STEP otherwise, and then nothing is sure) r < 2^-19 P + 1e-4, and
+//       D = ceil((2 emarg + 2^-17 P + 0.01) / kss * 1.0001) + 2
+//   makes kss (D - 1) >= 2 emarg + 4 r with a whole integer step to spare for the roundings of D itself.
+// The stand-in x~ = fl(sigma_0 sigma_1 q) passes the same two tests with more room (k x~ = kss q up to roundings), and
+// k x~ + nm <= emarg + 1 < 61 (q <= the row's / column's maximum, the stabiliser is that maximum less a margin); the exact
+// term's exponent is below 2 emarg + 1 < 121.  Both exponentials are finite, non-zero normals, and e / e = 1.0f for
+// either (k_select's one-entry lists: the only expression that reads a stand-in).
+// tests/test_defer_model.py replays this rule in float32 against the exact filters.
+__device__ __forceinline__ int sure_slack(float emarg, float kss, float k, float l1A_max, float infB) {
+#pragma clang fp contract(off)
+  const float P = k * l1A_max * infB;
+  const float dq = ceilf((2.0f * emarg + 7.62939453125e-6f * P + 0.01f) * (1.0f / kss) * 1.0001f);
+  return (emarg < 60.f && dq < 1.0e9f) ? (int)dq + 2 : 0x3fffffff;        // (NaN -> never sure)
 }
 
 // FM_MODE_FLAT: what the screening kernel does besides screening, for a call whose samples all go to the dense sum
@@ -138,6 +169,8 @@ struct RowsExtra {
   const int* umax2; const int* upos;     // max pass with the top-2 epilogue (valid when imgstat[b][6] != 0; fm_internal.h)
   int look;                              // 0: fm_debug_unit_cert(1), never look
   int count_cert;                        // fm_debug_unit_cert(2): count the certified live units
+  int defer;                             // list sure entries without their exact dot product (k_select is the lists' only reader)
+  int count_defer;                       // fm_debug_defer_exact(2): count them
   int nchunks, chunk_units, items;       // chunk_units <= 64 units per item (one ballot covers a chunk)
 };
 
@@ -202,7 +235,9 @@ __global__ __launch_bounds__(256, 3) void k_screen_rows(ScreenArgs a, RowsExtra 
   const int lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = lane & 31, h = lane >> 5;
-  __shared__ int s_list[4][LIST];
+  __shared__ int s_list[4][LIST];          // parked entries that take the exact phase: (unit << 10) | (row << 5) | column
+  __shared__ int s_sure[4][LIST];          // ... that are sure: the same key
+  __shared__ int s_sq[4][LIST];            // ... and their integer product
 
   // item = (sample, chunk, group of 4 row blocks) -> the 4 waves of a workgroup take 4 consecutive row blocks of one
   // chunk: their live units overlap (L1 / L2 hits on the B fragments); through the bijective XCD remap one XCD's share
@@ -225,6 +260,8 @@ __global__ __launch_bounds__(256, 3) void k_screen_rows(ScreenArgs a, RowsExtra 
   const float sig0 = a.sigimg[b * 2], sig1 = a.sigimg[b * 2 + 1];
   const float* ist = a.imgstat + (long)b * 8;
   const float clipA = ist[1], clipB = ist[4];
+  const float l1A_max = ist[0], infB = ist[5];
+  const float emarg_b = a.emarg[b];                 // (k_thresh wrote it)
   const float bl1A = a.bstat0[(long)b * nrb + rb].x;
   const float wmax = x.wmaxb[(long)b * nrb + rb];
   const int ul_c = min(lane, U - 1);
@@ -237,7 +274,7 @@ __global__ __launch_bounds__(256, 3) void k_screen_rows(ScreenArgs a, RowsExtra 
   const int um2 = x.umax2[((long)b * nrb + rb) * nunits + u0 + ul_c];
   const int upos = x.upos[((long)b * nrb + rb) * nunits + u0 + ul_c];
   const int tmin = min(x.tmin_r[(long)b * nrb + rb], x.tmin_c[(long)b * nunits + u0 + ul_c]);
-  int trr[16];
+  v16i trr;                                 // (a vector, not an array: the hit walk picks one by a uniform index, and an array would go to scratch for that)
   {
     const int* tp = x.thr_r + (long)b * a.Lp + wrow0 + 4 * h;
 #pragma unroll
@@ -255,6 +292,7 @@ __global__ __launch_bounds__(256, 3) void k_screen_rows(ScreenArgs a, RowsExtra 
   const float ss = sig0 * sig1;
   const float kss = a.k * ss;
   const bool screen_ok = kss > 1e-30f && kss < 1e30f;
+  const int D = (x.defer && screen_ok) ? sure_slack(emarg_b, kss, a.k, l1A_max, infB) : 0x3fffffff;
 
   // ---- live units of this row block (the same bound as k_screen) ----
   unsigned long long live;
@@ -275,15 +313,17 @@ __global__ __launch_bounds__(256, 3) void k_screen_rows(ScreenArgs a, RowsExtra 
   // does not start when the sample is flagged already (a plain, possibly stale load: only an optimisation).
   const bool flat = !screen_ok || a.dense_cnt[b] != 0;
   int nd_units = flat ? 1 : 0;
-  int nlist = 0;
+  int nlist = 0, nsure = 0;
 #ifdef FM_ABL_ROWS          // ablation builds (tools/): 1 = no sweep, 2 = no exact phase
   if (FM_ABL_ROWS & 1) live = 0;
 #endif
-  int cert_thr = 0x3fffffff, cert_key = 0;
+  int cert_thr = 0x3fffffff, cert_tmx = 0x3fffffff, cert_key = 0;
   if (!flat && ((cert >> lane) & 1)) {
     const int g = upos & 15, lw = (upos >> 4) & 63;
     const int rl = (g & 3) + 8 * (g >> 2) + 4 * (lw >> 5), cl = lw & 31;
-    cert_thr = min(x.thr_r[(long)b * a.Lp + wrow0 + rl], x.thr_c[(long)b * a.Sp + (u0 + lane) * 32 + cl]);
+    const int tr = x.thr_r[(long)b * a.Lp + wrow0 + rl], tc = x.thr_c[(long)b * a.Sp + (u0 + lane) * 32 + cl];
+    cert_thr = min(tr, tc);
+    cert_tmx = max(tr, tc);
     cert_key = (lane << 10) | (rl << 5) | cl;
   }
   if (x.count_cert && cert && lane == 0) atomicAdd(&a.scal->cert_units, __builtin_popcountll(cert));
@@ -319,7 +359,7 @@ __global__ __launch_bounds__(256, 3) void k_screen_rows(ScreenArgs a, RowsExtra 
       int cnt = 0;
 #pragma unroll
       for (int g = 0; g < 16; ++g) cnt += __builtin_popcountll(__ballot((bm >> g) & 1u));
-      if (cnt > kMaxExact || nlist + cnt > LIST) { ++nd_units; return; }
+      if (cnt > kMaxExact || nlist + nsure + cnt > LIST) { ++nd_units; return; }
       while (hitl) {
         const int l = __builtin_ctzll(hitl);
         hitl &= hitl - 1;
@@ -328,8 +368,23 @@ __global__ __launch_bounds__(256, 3) void k_screen_rows(ScreenArgs a, RowsExtra 
           const int g = __builtin_ctz(bits);
           bits &= bits - 1;
           const int rl = (g & 3) + 8 * (g >> 2) + 4 * (l >> 5);
-          if (lane == 0) s_list[wv][nlist] = (ul << 10) | (rl << 5) | (l & 31);
-          ++nlist;
+          const int key = (ul << 10) | (rl << 5) | (l & 31);
+          int sure_e = 0, q_e = 0;             // (uniform)
+          if (D != 0x3fffffff) {               // (uniform: a call that does not defer pays nothing per hit - flat units hold dozens)
+            // this entry's product and row threshold out of the 16 registers (g is uniform: a chain of selects, no indexing)
+            int qv = acc[0], tv = trr[0];
+#pragma unroll
+            for (int g2 = 1; g2 < 16; ++g2) { qv = (g == g2) ? acc[g2] : qv; tv = (g == g2) ? trr[g2] : tv; }
+            const bool sure_l = min(tv, tcl) > -1000000000 && qv > max(tv, tcl) + D;
+            q_e = __builtin_amdgcn_readlane(qv, l);
+            sure_e = __builtin_amdgcn_readlane((int)sure_l, l);
+          }
+          if (lane == 0) {
+            if (sure_e) { s_sure[wv][nsure] = key; s_sq[wv][nsure] = q_e; }
+            else s_list[wv][nlist] = key;
+          }
+          nsure += sure_e;                     // (plain sums: two counters picked by a branch end up in scratch)
+          nlist += 1 - sure_e;
         }
       }
     };
@@ -356,23 +411,50 @@ __global__ __launch_bounds__(256, 3) void k_screen_rows(ScreenArgs a, RowsExtra 
     // meet is LIST, and the wave's total decides that in either order)
     const unsigned long long hits = __ballot((int)um > cert_thr);
     const int nh = __builtin_popcountll(hits);
-    if (nlist + nh > LIST) ++nd_units;
+    if (nlist + nsure + nh > LIST) ++nd_units;
     else {
-      if ((hits >> lane) & 1) s_list[wv][nlist + __builtin_popcountll(hits & ((1ull << lane) - 1ull))] = cert_key;
-      nlist += nh;
+      const unsigned long long sure = hits & __ballot(cert_thr > -1000000000 && (int)um > cert_tmx + D);
+      const unsigned long long rest = hits & ~sure, below = (1ull << lane) - 1ull;
+      if ((rest >> lane) & 1) s_list[wv][nlist + __builtin_popcountll(rest & below)] = cert_key;
+      if ((sure >> lane) & 1) {
+        s_sure[wv][nsure + __builtin_popcountll(sure & below)] = cert_key;
+        s_sq[wv][nsure + __builtin_popcountll(sure & below)] = (int)um;
+      }
+      nlist += __builtin_popcountll(rest);
+      nsure += __builtin_popcountll(sure);
     }
   }
-  if (nd_units) nlist = 0;             // the sample goes to the dense kernel: its lists are not read
+  if (nd_units) nlist = nsure = 0;     // the sample goes to the dense kernel: its lists are not read
+
+  // ---- the sure entries: a place in the row's and in the column's list (the same two returning atomics as the exact
+  // phase), the tagged index and the stand-in sigma_0 sigma_1 q - one lane per entry, no descriptor, no stabiliser ----
+  int overflow = 0;
+#ifdef FM_ABL_ROWS
+  if (FM_ABL_ROWS & 2) nsure = 0;
+#endif
+  for (int e0 = 0; e0 < nsure; e0 += 64) {
+    if (e0 + lane < nsure) {
+      const int ky = s_sure[wv][e0 + lane];
+      const float xq = ss * (float)s_sq[wv][e0 + lane];
+      const int row = wrow0 + ((ky >> 5) & 31), col = (u0 + ((ky >> 10) & 63)) * 32 + (ky & 31);
+      const long grow = (long)b * a.Lp + row, gcol = (long)b * a.Sp + col;
+      const int pr = atomicAdd(&a.rcount[grow], 1);
+      const int pc = atomicAdd(&a.ccount[gcol], 1);
+      if (pr < a.slots) { a.rlist_j[grow * a.slots + pr] = col | kDeferTag; a.rlist_x[grow * a.slots + pr] = xq; }
+      else overflow = 1;
+      if (pc < a.slots) { a.clist_i[gcol * a.slots + pc] = row | kDeferTag; a.clist_x[gcol * a.slots + pc] = xq; }
+      else overflow = 1;
+    }
+  }
+  if (x.count_defer && nsure && lane == 0) atomicAdd(&a.scal->defer_entries, nsure);
 
   // ---- the parked entries: exact float32 dot products (as in k_screen; stabilisers from k_thresh's arrays) ----
-  int overflow = 0;
 #ifdef FM_ABL_ROWS
   if (FM_ABL_ROWS & 2) nlist = 0;
 #endif
   {
     constexpr int NPASS = 4;
     const int sub = lane >> 4, l16 = lane & 15;
-    const int vpr = a.c_in >> 2;
     for (int e0 = 0; e0 < nlist; e0 += 4 * NPASS) {
       int myres = 0;
       float my_nmr = 0.f, my_nmc = 0.f;
@@ -396,36 +478,10 @@ __global__ __launch_bounds__(256, 3) void k_screen_rows(ScreenArgs a, RowsExtra 
           const int idx = e0 + 4 * p + sub;
           key[p] = s_list[wv][min(idx, nlist - 1)];
           const int row = wrow0 + ((key[p] >> 5) & 31), col = (u0 + ((key[p] >> 10) & 63)) * 32 + (key[p] & 31);
-          const long ro = ((long)b * a.L + row) * a.c_in, co = ((long)b * a.S + col) * a.c_in;
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const int v4 = l16 + 16 * q;
-            const bool in = v4 < vpr;
-            const int vc = in ? v4 : 0;
-            float4 ta, tb;
-            if (a.in_dtype == FM_F32) {
-              ta = reinterpret_cast<const float4*>((const float*)a.src0 + ro)[vc];
-              tb = reinterpret_cast<const float4*>((const float*)a.src1 + co)[vc];
-            } else {
-              ta = half4_to_float4(reinterpret_cast<const uint2*>((const unsigned short*)a.src0 + ro)[vc], a.in_dtype);
-              tb = half4_to_float4(reinterpret_cast<const uint2*>((const unsigned short*)a.src1 + co)[vc], a.in_dtype);
-            }
-            av[pp][q] = in ? ta : make_float4(0.f, 0.f, 0.f, 0.f);
-            bv[pp][q] = tb;
-          }
+          exact_dot16_load(a.desc, b, row, col, l16, av[pp], bv[pp]);
         }
 #pragma unroll
-        for (int pp = 0; pp < 2; ++pp) {
-          float sm = 0.f;
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            sm = __builtin_fmaf(av[pp][q].x, bv[pp][q].x, sm);
-            sm = __builtin_fmaf(av[pp][q].y, bv[pp][q].y, sm);
-            sm = __builtin_fmaf(av[pp][q].z, bv[pp][q].z, sm);
-            sm = __builtin_fmaf(av[pp][q].w, bv[pp][q].w, sm);
-          }
-          xs[h2 + pp] = row_sum16(sm);
-        }
+        for (int pp = 0; pp < 2; ++pp) xs[h2 + pp] = exact_dot16_sum(av[pp], bv[pp]);
         if (e0 + 4 * (h2 + 2) >= nlist) break;
       }
 #pragma unroll
@@ -479,13 +535,12 @@ hipError_t launch_stab(const CoarseWs& w, char* base, float inv_ct, float thr, i
 }
 
 hipError_t launch_screen(const void* feat0, const void* feat1, int in_dtype, int c_in, const CoarseWs& w, char* base,
-                         float inv_ct, float thr, int dense_enabled, int allow_dead, hipStream_t st) {
+                         float inv_ct, float thr, int dense_enabled, int allow_dead, bool defer, hipStream_t st) {
   ScreenArgs a;
   memset(&a, 0, sizeof(a));
   fill_screen_stats(a, w, base, inv_ct, thr, allow_dead);
-  a.in_dtype = in_dtype;
   a.q0 = w.q0.in(base); a.q1 = w.q1.in(base);
-  a.src0 = feat0; a.src1 = feat1; a.c_in = c_in;
+  a.desc = DescRows{feat0, feat1, c_in, in_dtype, w.L, w.S};
   a.rcount = w.cand.count.in(base); a.rlist_j = w.cand.idx.in(base); a.rlist_x = w.cand.x.in(base);
   a.ccount = w.ccand.count.in(base); a.clist_i = w.ccand.idx.in(base); a.clist_x = w.ccand.x.in(base);
   a.dense_enabled = dense_enabled;
@@ -496,6 +551,8 @@ hipError_t launch_screen(const void* feat0, const void* feat1, int in_dtype, int
   x.umax2 = w.umax2.in(base); x.upos = w.upos.in(base);
   x.look = g_unit_cert != 1;
   x.count_cert = g_unit_cert == 2;
+  x.defer = defer ? 1 : 0;
+  x.count_defer = defer && g_defer_exact == 2;
   x.chunk_units = w.units_s;
   x.nchunks = w.splits_s;
 #ifdef FM_TUNE_ENV

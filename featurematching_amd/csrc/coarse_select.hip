@@ -9,6 +9,7 @@
 // that is not a candidate has conf <= thr, so it can neither pass :99 nor beat a surviving
 // candidate in the row / column maxima of :105-106 - the maxima over candidates decide.
 // The border mask (:100-102) is applied last: border cells still compete in the maxima.
+#include "fm_exact_device.h"
 #include "fm_internal.h"
 #include "fm_maps_device.h"
 
@@ -25,6 +26,7 @@ struct SelArgs {
   const int* cand_count_b; const int* cand_j_b; const float* cand_x_b;    // the dense one's (samples with dense_cnt > 0)
   const int* ccand_count_b; const int* ccand_i_b; const float* ccand_x_b;
   const int* dense_cnt;
+  DescRows desc;                          // the caller's descriptors: exact dot products of the entries the screening deferred
   const float* rsum; const float* csum;   // softmax denominators of every row / column (k_reduce_sums), when sums_ready
   int sums_ready;                         // k_reduce_sums ran before this kernel (exact screening, conf_matrix, statistics,
                                           // FM_MODE_FLAT): a dense sample's denominators are ONE load each instead of a
@@ -103,6 +105,9 @@ __device__ __forceinline__ float entry_conf(float x, float k, float nmr, float r
 // a workgroup that does not see its predecessors within ~2^22 polls gives up and the call reports FM_E_INTERNAL
 // instead of hanging.  (Tickets - a returning atomic on one address before anything else can be loaded - made the
 // order a certainty at 1.2 us per launch and 146 us for the 9728 blocks of a 64-pair batch.)
+// DEFER: the screening kernel's lists may hold tagged entries (a common-path call with the deferral on, or the dense
+// resume of one).  Every other call runs the instantiation without a line of that code.
+template <bool DEFER>
 __global__ __launch_bounds__(256) void k_select(SelArgs a) {
   __shared__ int sm[4];
   __shared__ int rowoff[64], rowcnt[64];
@@ -148,6 +153,11 @@ __global__ __launch_bounds__(256) void k_select(SelArgs a) {
   //    per lane and round trip, a fixed order that every group evaluating the same row or column reproduces);
   //  * all other samples: the lists hold every SIGNIFICANT entry of the row / column with its exact dot product
   //    (k_screen), and a denominator is the sum of its list's terms in index order (list_sum).
+  //    An index with kDeferTag set (bit 30, masked wherever an index is read) names an entry the screening listed
+  //    WITHOUT that product: its x is a stand-in.  A stand-in is read by ONE expression only - the e / e = 1.0f of an
+  //    entry alone in its row's list and alone in its column's list, where the value cancels - and every other tagged
+  //    entry (a longer list of its row or its column, any list reached through another row or a column) is replaced by
+  //    the exact product first (resolve_deferred: the screening's own arithmetic), sums formed from the replaced value.
   const bool row_ok = b < a.N && i < a.L;
   const long grow_c = row_ok ? grow : 0;                      // (clamped: no load behind a branch)
   const int b_c = row_ok ? b : 0, i_c = row_ok ? i : 0;
@@ -172,20 +182,35 @@ __global__ __launch_bounds__(256) void k_select(SelArgs a) {
     const long g = (long)b_c * a.Lp + row;
     if (dense) return a.sums_ready ? a.rsum[g] : group_sum(share(a.rowB + (long)b_c * a.splits * a.Lp + row, a.splits, a.Lp));
     const int c2 = min(cand_count[g], a.slots);
-    const int k2 = cand_j[g * a.slots + slot];
-    const float x2 = cand_x[g * a.slots + slot];
+    const int k2t = cand_j[g * a.slots + slot];
+    const int k2 = DEFER ? (k2t & ~kDeferTag) : k2t;
+    float x2 = cand_x[g * a.slots + slot];
+    if constexpr (DEFER) {
+      bool any;
+      x2 = resolve_deferred(a.desc, b_c, slot < c2 && (k2t & kDeferTag) != 0, row, k2, x2, lane, any);
+    }
     return list_sum(__builtin_amdgcn_exp2f(__builtin_fmaf(x2, a.k, nm)), k2, slot < c2, a.slots, base, wave_max_int(c2));
   };
   // round trip 1: entry count, this lane's entry (speculatively), stabiliser, the row's denominator
   const int cnt_raw = cand_count[grow_c];
-  const int j_raw = cand_j[grow_c * a.slots + slot];
-  const float x_raw = cand_x[grow_c * a.slots + slot];
+  const int j_tag = cand_j[grow_c * a.slots + slot];
+  float x_raw = cand_x[grow_c * a.slots + slot];
   const float nmr_i = a.nmr[grow_c];
   const int cnt = row_ok ? min(cnt_raw, a.slots) : 0;
   const bool live = slot < cnt;
+  const int j_raw = DEFER ? (j_tag & ~kDeferTag) : j_tag;
+  bool tag_own = DEFER && !dense && live && (j_tag & kDeferTag) != 0;      // this lane's entry still holds a stand-in
   float rs;
   if (dense) rs = a.sums_ready ? a.rsum[grow_c] : group_sum(share(a.rowB + (long)b_c * a.splits * a.Lp + i_c, a.splits, a.Lp));
-  else rs = list_sum(__builtin_amdgcn_exp2f(__builtin_fmaf(x_raw, a.k, nmr_i)), j_raw, live, a.slots, base, wave_max_int(cnt));
+  else {
+    const int maxcnt = wave_max_int(cnt);
+    if (DEFER && maxcnt > 1) {                                    // (uniform) a row with several entries: all of them exact
+      bool any;
+      x_raw = resolve_deferred(a.desc, b_c, tag_own && cnt > 1, i_c, j_raw, x_raw, lane, any);
+      tag_own = tag_own && cnt == 1;
+    }
+    rs = list_sum(__builtin_amdgcn_exp2f(__builtin_fmaf(x_raw, a.k, nmr_i)), j_raw, live, a.slots, base, maxcnt);
+  }
   bool keep = false;
   int j = live ? j_raw : 0x7fffffff;
   float conf = 0.f, colbest = 0.f;
@@ -242,18 +267,38 @@ __global__ __launch_bounds__(256) void k_select(SelArgs a) {
     if (!__any(t < cnt)) break;                               // wave-uniform
     const bool act = t < cnt;                                 // (a row's lanes agree)
     const int jt = act ? __shfl(j_raw, base + t) : 0;
-    const float xt = __shfl(x_raw, base + t);
+    float xt = __shfl(x_raw, base + t);
+    bool tag_t = false;                                                 // the row's one entry still holds a stand-in
+    if constexpr (DEFER) tag_t = !dense && act && __shfl((int)tag_own, base + t) != 0;
     const long gcol = (long)b_c * a.Sp + jt;
     // round trip 2: the column's denominator, stabiliser, and its list - lane s the s-th entry
     const float nmc = a.nmc[gcol];
     const int ccnt = act ? min(ccand_count[gcol], a.slots) : 0;
-    const int ci = ccand_i[gcol * a.slots + slot];
-    const float cx = ccand_x[gcol * a.slots + slot];
+    const int ci_tag = ccand_i[gcol * a.slots + slot];
+    const int ci = DEFER ? (ci_tag & ~kDeferTag) : ci_tag;
+    float cx = ccand_x[gcol * a.slots + slot];
+    // the stand-in stays only where the entry is alone in its row's AND in its column's list
+    const bool standin = tag_t && ccnt == 1;
+    if (DEFER && !dense) {
+      bool any;
+      cx = resolve_deferred(a.desc, b_c, slot < ccnt && (ci_tag & kDeferTag) != 0 && !(standin && ci == i), ci, jt, cx, lane, any);
+      if (any) {                                                        // (uniform)
+        // a one-entry row whose column holds more: its entry was replaced in the column's list - the row takes that
+        // value and forms its denominator, the one term, again
+        for (int e = 0; e < a.slots; ++e) {
+          const int i2 = __shfl(ci, base + e);
+          const float x2 = __shfl(cx, base + e);
+          if (tag_t && !standin && e < ccnt && i2 == i) xt = x2;
+        }
+        if (tag_t && !standin) rs = __builtin_amdgcn_exp2f(__builtin_fmaf(xt, a.k, nmr_i));
+      }
+    }
     float cs;
     if (dense) cs = a.sums_ready ? a.csum[gcol] : group_sum(share(a.colB + (long)b_c * a.panels * a.Sp + jt, a.panels, a.Sp));
     else cs = list_sum(__builtin_amdgcn_exp2f(__builtin_fmaf(cx, a.k, nmc)), ci, slot < ccnt, a.slots, base, wave_max_int(ccnt));
     // (an entry that is negligible for its column - not in that column's list - has conf < 2^-32)
-    const bool col_sig = dense || __builtin_fmaf(xt, a.k, nmc) > -kSkipLog2;
+    // (a deferred entry is significant for its row and its column: that is what the screening proved)
+    const bool col_sig = dense || standin || __builtin_fmaf(xt, a.k, nmc) > -kSkipLog2;
     const float ct = (act && col_sig) ? entry_conf(xt, a.k, nmr_i, rs, nmc, cs) : 0.f;
     float cb = 0.f;
     const int cmax = wave_max_int(ccnt);
@@ -407,6 +452,7 @@ hipError_t launch_select(const CoarseWs& w, char* base, const CoarseCall& c, flo
   a.ccand_count_b = w.ccand_b.count.in(base); a.ccand_i_b = w.ccand_b.idx.in(base);
   a.ccand_x_b = w.ccand_b.x.in(base);
   a.dense_cnt = w.dense_cnt.in(base);
+  a.desc = DescRows{c.feat0, c.feat1, c.C, c.in_dtype, w.L, w.S};
   a.rsum = w.rsum.in(base); a.csum = w.csum.in(base);
   a.blocktot = w.blocktot.in(base);
   a.scal = w.scalars.in(base);
@@ -428,7 +474,8 @@ hipError_t launch_select(const CoarseWs& w, char* base, const CoarseCall& c, flo
     const long units = (long)((job->Wf + 63) / 64) * job->Hf * job->N;
     extra = (int)(units < 1024 ? units : 1024);
   }
-  hipLaunchKernelGGL(k_select, dim3(blocks + extra), dim3(256), 0, (hipStream_t)c.stream, a);
+  if (flags.deferred) hipLaunchKernelGGL(k_select<true>, dim3(blocks + extra), dim3(256), 0, (hipStream_t)c.stream, a);
+  else hipLaunchKernelGGL(k_select<false>, dim3(blocks + extra), dim3(256), 0, (hipStream_t)c.stream, a);
   return hipGetLastError();
 }
 

@@ -47,6 +47,16 @@ int fm_debug_unit_cert(int mode);
 /* Byte offsets in the coarse workspace of umax, umax2, upos, thr_r, thr_c, tmin_r, tmin_c and the counter of certified
  * units (int32, zeroed per call), then whether the launch plan of this shape uses the certificate (9 values). */
 int fm_debug_unit_cert_layout(int N, int L, int S, int C, int cand_slots, int64_t* out, int n_out);
+/* Test-only, process-global: the deferred exact dot products of the screening (k_screen_rows lists an entry whose
+ * integer screening product proves it significant for its row and its column with a tagged index and a stand-in value,
+ * without gathering the two descriptor rows; k_select forms the exact product of the few it needs).
+ * mode 0 = the launch plan decides (default: on the common path, where k_select is the lists' only reader), 1 = off,
+ * 2 = as 0, and k_screen_rows counts the deferred entries; any other value only reads.  Returns the previous mode.  Set
+ * it between complete calls only.  fm_debug_launch_screen, which knows no mode, defers unless the switch is 1. */
+int fm_debug_defer_exact(int mode);
+/* Byte offset in the coarse workspace of the counter of deferred entries (int32, zeroed per call), the tag bit of a list
+ * index, and whether a common-path call of this shape defers under the present switch (3 values). */
+int fm_debug_defer_exact_layout(int N, int L, int S, int C, int cand_slots, int64_t* out, int n_out);
 
 #ifdef __cplusplus
 }

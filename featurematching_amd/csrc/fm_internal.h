@@ -65,6 +65,8 @@ struct Scalars {          // lives at ws.scalars (zeroed per call)
   int dense_units;        // 32x32 units the sparse sum kernel left to the dense one (0: that kernel exits at once)
   int cert_units;         // live units k_screen_rows resolved from the max pass's certificate (counted only while
                           // fm_debug_unit_cert forces the certificate on)
+  int defer_entries;      // entries k_screen_rows listed without their exact dot product (counted only while
+                          // fm_debug_defer_exact forces the deferral on)
 };
 
 // Device workspace of the coarse stage; all offsets in bytes from the base.  The regions the common path uses come
@@ -140,6 +142,21 @@ inline bool unit_cert_on(const CoarseWs& w, bool common_path = true) {
   return g_unit_cert == 2 || (g_unit_cert == 0 && w.top2 != 0 && common_path);
 }
 
+// fm_debug_defer_exact: 0 = the launch plan decides, 1 = never, 2 = always where the plan allows it (and count).  The
+// screening may list a sure entry with a stand-in for its exact dot product (coarse_screen.hip: sure_slack) only where
+// k_select - which resolves a stand-in before any expression but e / e reads it - is the ONLY reader of the screening
+// kernel's lists: the common path.  Every other reader runs in a plan with `dense` set:
+//   k_reduce_sums (rescreen / every row's statistics / FM_MODE_FLAT), k_exact_lists + k_fix_sums and k_conf_patch (every
+//   row's statistics, conf_matrix) - and tools/gpu_bringup.py reads the lists of an FM_MODE_DENSE call.
+// The dense resume of fm_coarse_match_auto continues a common-path call: its plan is mode | FM_MODE_DENSE alone (a call
+// with FM_MODE_EXACT_SCREENING, statistics or a conf_matrix never reported FM_E_DENSE from the common path), so reduce,
+// exact_lists and conf are off and k_select alone reads the unflagged samples' lists, stand-ins included; the dense
+// kernels write and read the other set of lists (cand_b).  The tag needs bit 30 of an index to be free.
+extern int g_defer_exact;
+inline bool defer_exact_on(const CoarseWs& w, bool common_path = true) {
+  return g_defer_exact != 1 && common_path && w.Lp < 0x40000000 && w.Sp < 0x40000000;
+}
+
 // One coarse call as the C ABI takes it (fmatch.h: fm_coarse_match_dtype's arguments, in their order)
 struct CoarseCall {
   const void *feat0, *feat1; int in_dtype;
@@ -169,8 +186,10 @@ hipError_t launch_reduce(const CoarseWs& w, char* base, float inv_ct, hipStream_
 struct MapCopyJob {
   const float* src; float* dst; int N, Hf, Wf;
 };
-// what the assignment launch is told about the launches before it (SelArgs: exact, dense_enabled, cell_maps, sums_ready)
-struct SelectFlags { bool exact, dense, cell_maps, sums_ready; };
+// what the assignment launch is told about the launches before it (SelArgs: exact, dense_enabled, cell_maps, sums_ready;
+// deferred: the screening kernel's lists may hold tagged entries - k_select<true>)
+struct SelectFlags { bool exact, dense, cell_maps, sums_ready, deferred; };
+// (reads c.feat0 / c.feat1: the exact dot products of the entries the screening listed with a stand-in)
 hipError_t launch_select(const CoarseWs& w, char* base, const CoarseCall& c, float inv_ct, SelectFlags flags,
                          const MapCopyJob* job = nullptr);
 hipError_t launch_conf_patch(const CoarseWs& w, char* base, float inv_ct, float* conf, hipStream_t st);
@@ -179,7 +198,7 @@ hipError_t launch_exact_lists(const CoarseWs& w, char* base, float inv_ct, const
 // (the batched form of the screening - k_thresh + k_screen_rows, one wave per (row block, 64 units) - is chosen inside
 // launch_screen when the batch alone fills the chip with waves)
 hipError_t launch_screen(const void* feat0, const void* feat1, int in_dtype, int c_in, const CoarseWs& w, char* base,
-                             float inv_ct, float thr, int dense_enabled, int allow_dead, hipStream_t st);
+                             float inv_ct, float thr, int dense_enabled, int allow_dead, bool defer, hipStream_t st);
 
 // ---- backward of the dual softmax (dsm_grad.hip) and the matrix-free coarse loss on top of it (coarse_loss.hip) ----
 // Workspace of the backward entry points: v [N][L] row sums and u [N][S] column sums of g conf, one behind the other

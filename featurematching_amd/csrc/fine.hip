@@ -659,98 +659,149 @@ __global__ __launch_bounds__(256) void k_nchw_to_nhwc64(const T* __restrict__ sr
 
 using namespace fm;
 
-// ---- launch helpers shared by the plain and the merging entry points ----
-template <bool MERGE>
-static void launch_list64(int W, int blocks, hipStream_t st, const float* feat_f, int Hf, int Wf, int stride, int pad,
-                          int w_c, const int64_t* b_ids, const int64_t* ids, const int32_t* d_count, int m_max,
-                          float* out, const half8* wpack, const float* ctx, int ctx_cells) {
-  with_window(W, [&](auto w) {
-    hipLaunchKernelGGL((k_gather_nchw64<decltype(w)::value, MERGE>), dim3(blocks), dim3(256), 0, st, feat_f, Hf, Wf, stride,
-                       pad, w_c, b_ids, ids, d_count, m_max, out, wpack, ctx, ctx_cells);
-  });
+// ---- the window calls: every entry point fills a WindowCall (fm_internal.h); one status, one route, one launch site per
+// ---- kernel.  None: FM_E_UNSUPPORTED (a plain two-image crop in list order, say, is a hole in the table)
+enum class WindowRoute { None, Cells64, List64, List64Merge, Nhwc64Copy, Nhwc64Merge, Generic, FineMaps };
+
+static WindowRoute window_route(const WindowCall& c) {
+  using R = WindowRoute;
+  // the 64-channel kernels: the sizes they are instantiated for; the NCHW ones and the fine kernel address one sample's
+  // map with 31-bit byte offsets (buffer descriptor), counted in float32 whatever the element type
+  bool k64 = c.Cf == 64 && (c.W == 5 || c.W == 7), fits31 = true;
+  for (int i = 0; i < c.images; ++i) fits31 = fits31 && (long)c.im[i].Hf * c.im[i].Wf * 64 * 4 < (1L << 31);
+  const bool f32 = c.dtype == FM_F32, fast = f32 && k64 && fits31, one = c.images == 1, nchw = c.layout == 0;
+  if (!map_dtype_ok(c.dtype)) return R::None;
+  if (c.fine)      // (FM_LAYOUT_NCHW_PREPARED: image 1's channels-last copy was made by the coarse call - float32 maps only)
+    return (nchw || c.layout == 1 || (c.layout == FM_LAYOUT_NCHW_PREPARED && f32)) && k64 && fits31 ? R::FineMaps : R::None;
+  if (nchw && c.cells) return fast ? R::Cells64 : R::None;                            // one or two images, plain or merge
+  if (nchw && one && c.merge) return fast ? R::List64Merge : R::None;
+  if (nchw && one && fast) return R::List64;
+  if (c.layout == 1 && !c.cells && c.merge) return k64 ? R::Nhwc64Merge : R::None;    // one or two images, any element type
+  if (c.layout == 1 && !c.cells && one && f32 && k64) return R::Nhwc64Copy;           // one wave per window, 16-byte chunks
+  // the generic kernels: the NCHW one stages a window of every channel in LDS, the channels-last one loads 4 channels at once
+  const bool fits = nchw ? (size_t)c.W * c.W * (c.Cf + 1) * sizeof(float) <= 64 * 1024 : c.Cf % 4 == 0;
+  return !c.cells && !c.merge && one && generic_window_supported(c.Cf, c.W, c.layout) && fits ? R::Generic : R::None;
 }
-static CellImage cell_image(const float* feat, int N, int Hf, int Wf, int h_c, int w_c, const int32_t* map, int pitch,
-                            const int32_t* ties, const int64_t* ids, float* out, const float* ctx) {
-  CellImage im;
-  im.feat = feat; im.Hf = Hf; im.Wf = Wf; im.w_c = w_c; im.cells = h_c * w_c; im.total_cells = N * h_c * w_c;
-  im.cell_to_match = map; im.cell_pitch = pitch; im.ties = ties; im.ids = ids; im.out = out; im.ctx = ctx;
-  return im;
+
+// m_max == 0 is FM_OK before anything is looked at; then NULL, shape, unsupported
+static int window_status(const WindowCall& c) {
+  if (c.m_max == 0) return FM_OK;
+  if (c.missing || !c.b_ids || (c.merge && !c.wpack)) return FM_E_NULL;
+  for (int i = 0; i < c.images; ++i) {
+    const WindowImage& im = c.im[i];
+    if (!im.feat || !im.ids || !im.out || (c.cells && (!im.cell_map || !im.ties)) || (c.merge && !im.ctx)) return FM_E_NULL;
+  }
+  if (c.free_size && !map_dtype_ok(c.dtype)) return FM_E_UNSUPPORTED;
+  if (c.free_size && !generic_window_shape_ok(c.Cf, c.W)) return FM_E_SHAPE;
+  for (int i = 0; i < c.images; ++i) {
+    const WindowImage& im = c.im[i];
+    if (!crop_shape_ok(c.N, im.Hf, im.Wf, c.stride, c.m_max) || im.w_c <= 0 || ((c.cells || c.merge) && im.h_c <= 0) ||
+        (c.cells && im.cell_pitch < im.h_c * im.w_c))
+      return FM_E_SHAPE;
+  }
+  if (window_route(c) == WindowRoute::None) return FM_E_UNSUPPORTED;
+  return c.fine && c.layout != 1 && !c.scratch ? FM_E_NULL : FM_OK;      // (the channels-last copies of NCHW maps)
 }
-static CellArgs cell_args(const CellImage& im0, const CellImage& im1, int stride, int pad, int m_max, const int64_t* b_ids,
-                          const int32_t* d_count, const void* packed_w) {
-  CellArgs a;
-  a.im[0] = im0; a.im[1] = im1;
-  a.stride = stride; a.pad = pad; a.m_max = m_max; a.b_ids = b_ids; a.d_count = d_count; a.wpack = (const half8*)packed_w;
-  return a;
-}
-// the 64-channel kernels (crop and fine) address one sample's float32 map with 31-bit byte offsets (buffer descriptor)
-static bool fast_nchw64(int Cf, int Hf, int Wf, int W) {
-  return Cf == 64 && (W == 5 || W == 7) && (long)Hf * Wf * 64 * 4 < (1L << 31);
-}
+
 // 8 XCD ranges of ceil(M/8) windows, four windows (waves) per workgroup
 static int list_blocks(int m_max) { return 8 * (((m_max + 7) / 8 + 3) / 4); }
 // largest grid of the kernels of fm_fine_match_maps (a multiple of 8; they walk longer lists in grid strides)
 constexpr int kFineGridCap = 1 << 20;
 // one wave per cell, four per workgroup, grid a multiple of 8
 static int cell_blocks(long total) { return (int)(((total + 3) / 4 + 7) / 8 * 8); }
-// the cell-ordered crop of `nimg` images (the larger has `total` cells) in one launch; a.wpack != NULL: with the merge
-static int launch_cells64(int W, int nimg, long total, const CellArgs& a, hipStream_t st) {
-  with_window(W, [&](auto w) {
-    auto launch = [&](auto merge) {
-      hipLaunchKernelGGL((k_gather_cellorder64<decltype(w)::value, decltype(merge)::value>), dim3(cell_blocks(total), nimg),
-                         dim3(256), 0, st, a);
-    };
-    if (a.wpack) launch(std::true_type{});
-    else launch(std::false_type{});
-  });
-  return (int)hipGetLastError();
+
+// the kernels' argument structs from the record (a one-image call names image 0 twice)
+static CellArgs cell_args(const WindowCall& c) {
+  auto image = [&](const WindowImage& s) {
+    return CellImage{(const float*)s.feat, s.Hf, s.Wf, s.w_c, s.h_c * s.w_c, c.N * s.h_c * s.w_c, s.cell_map, s.cell_pitch,
+                     s.ties, s.ids, s.out, s.ctx};
+  };
+  return {{image(c.im[0]), image(c.im[c.images - 1])}, c.stride, c.pad, c.m_max, c.b_ids, c.d_count, (const half8*)c.wpack};
+}
+static MergeNhwcArgs merge_nhwc_args(const WindowCall& c) {
+  auto image = [](const WindowImage& s) {
+    return MergeNhwcImage{s.feat, s.Hf, s.Wf, s.w_c, s.h_c * s.w_c, s.ids, s.out, s.ctx};
+  };
+  return {{image(c.im[0]), image(c.im[c.images - 1])}, c.stride, c.pad, c.m_max, c.b_ids, c.d_count, (const half8*)c.wpack};
 }
 
+// the cell-ordered crop of every image of the call in one launch (grid.x: the larger image's cells)
+static void launch_cells64(const WindowCall& c) {
+  long total = 0;
+  for (int i = 0; i < c.images; ++i) total = std::max(total, (long)c.N * c.im[i].h_c * c.im[i].w_c);
+  with_window(c.W, [&](auto w) {
+    auto launch = [&](auto merge) {
+      hipLaunchKernelGGL((k_gather_cellorder64<decltype(w)::value, decltype(merge)::value>),
+                         dim3(cell_blocks(total), c.images), dim3(256), 0, (hipStream_t)c.stream, cell_args(c));
+    };
+    if (c.merge) launch(std::true_type{});
+    else launch(std::false_type{});
+  });
+}
+template <bool MERGE>
+static void launch_list64(const WindowCall& c) {
+  const WindowImage& im = c.im[0];
+  with_window(c.W, [&](auto w) {
+    hipLaunchKernelGGL((k_gather_nchw64<decltype(w)::value, MERGE>), dim3(list_blocks(c.m_max)), dim3(256), 0,
+                       (hipStream_t)c.stream, (const float*)im.feat, im.Hf, im.Wf, c.stride, c.pad, im.w_c, c.b_ids, im.ids,
+                       c.d_count, c.m_max, im.out, (const half8*)c.wpack, im.ctx, MERGE ? im.h_c * im.w_c : 0);
+  });
+}
+// half-precision maps (an autocast backbone's hand-over) are read as they are - every value is exact in float32 - by
+// the generic kernels; no up-cast pass over the whole map in front of the crop
 template <int DT>
-static void launch_generic_gather(const void* feat_f, int Cf, int Hf, int Wf, int layout, int W, int stride, int pad, int w_c,
-                                  const int64_t* b_ids, const int64_t* ids, const int32_t* d_count, int m_max, float* out,
-                                  hipStream_t st) {
-  using E = typename MapElem<DT>::type;
-  if (layout == 0) {
-    const size_t smem = (size_t)W * W * (Cf + 1) * sizeof(float);
-    hipLaunchKernelGGL(k_gather_nchw<DT>, dim3(m_max), dim3(256), smem, st, (const E*)feat_f, Cf, Hf, Wf, W, stride, pad, w_c,
-                       b_ids, ids, d_count, m_max, out);
-  } else {
-    hipLaunchKernelGGL(k_gather_nhwc<DT>, dim3(m_max), dim3(256), 0, st, (const E*)feat_f, Cf, Hf, Wf, W, stride, pad, w_c,
-                       b_ids, ids, d_count, m_max, out);
+static void launch_generic_gather(const WindowCall& c) {
+  const WindowImage& im = c.im[0];
+  auto launch = [&](auto kernel, size_t smem) {
+    hipLaunchKernelGGL(kernel, dim3(c.m_max), dim3(256), smem, (hipStream_t)c.stream,
+                       (const typename MapElem<DT>::type*)im.feat, c.Cf, im.Hf, im.Wf, c.W, c.stride, c.pad, im.w_c, c.b_ids,
+                       im.ids, c.d_count, c.m_max, im.out);
+  };
+  if (c.layout == 0) launch(k_gather_nchw<DT>, (size_t)c.W * c.W * (c.Cf + 1) * sizeof(float));
+  else launch(k_gather_nhwc<DT>, 0);
+}
+
+// What every crop entry point does with its record.  The cases stand in the order in which the kernels have always been
+// instantiated, the generic kernels' element types included (F32 first: not with_map_dtype's order), so that the device
+// code object keeps its layout.
+static int run_window_call(const WindowCall& c) {
+  const int status = window_status(c);
+  if (status != FM_OK || c.m_max == 0) return status;
+  const WindowImage& im = c.im[0];
+  switch (window_route(c)) {
+    case WindowRoute::Cells64: launch_cells64(c); break;
+    case WindowRoute::List64: launch_list64<false>(c); break;
+    case WindowRoute::Nhwc64Copy:
+      with_window(c.W, [&](auto w) {
+        hipLaunchKernelGGL(k_gather_nhwc64<decltype(w)::value>, dim3(list_blocks(c.m_max)), dim3(256), 0, (hipStream_t)c.stream,
+                           (const float*)im.feat, im.Hf, im.Wf, c.stride, c.pad, im.w_c, c.b_ids, im.ids, c.d_count, c.m_max,
+                           im.out);
+      });
+      break;
+    case WindowRoute::Generic:
+      if (c.dtype == FM_F32) launch_generic_gather<FM_F32>(c);
+      else if (c.dtype == FM_F16) launch_generic_gather<FM_F16>(c);
+      else launch_generic_gather<FM_BF16>(c);
+      break;
+    case WindowRoute::List64Merge: launch_list64<true>(c); break;
+    case WindowRoute::Nhwc64Merge:
+      with_window(c.W, [&](auto w) {
+        with_map_dtype(c.dtype, [&](auto dt) {
+          hipLaunchKernelGGL((k_gather_merge_nhwc64<decltype(w)::value, decltype(dt)::value>),
+                             dim3(list_blocks(c.m_max), c.images), dim3(256), 0, (hipStream_t)c.stream, merge_nhwc_args(c));
+        });
+      });
+      break;
+    default: break;       // (FineMaps: fm_fine_match_maps_dtype launches its own)
   }
+  return (int)hipGetLastError();
 }
 
 extern "C" int fm_gather_windows_dtype(const void* feat_f, int map_dtype, int N, int Cf, int Hf, int Wf, int layout, int W,
                                        int stride, int pad, int w_c, const int64_t* b_ids, const int64_t* ids,
                                        const int32_t* d_count, int m_max, float* out, void* stream) {
-  if (m_max == 0) return FM_OK;
-  if (!feat_f || !b_ids || !ids || !out) return FM_E_NULL;
-  if (map_dtype != FM_F32 && map_dtype != FM_F16 && map_dtype != FM_BF16) return FM_E_UNSUPPORTED;
-  if (!crop_shape_ok(N, Hf, Wf, stride, m_max) || Cf <= 0 || W <= 0 || w_c <= 0) return FM_E_SHAPE;
-  if (W > 15 || Cf > 512 || (layout == 1 && Cf % 4) || (layout != 0 && layout != 1)) return FM_E_UNSUPPORTED;
-  hipStream_t st = (hipStream_t)stream;
-  if (layout == 0 && (size_t)W * W * (Cf + 1) * sizeof(float) > 64 * 1024 &&
-      !(map_dtype == FM_F32 && fast_nchw64(Cf, Hf, Wf, W))) return FM_E_UNSUPPORTED;
-  if (map_dtype == FM_F32 && layout == 0 && fast_nchw64(Cf, Hf, Wf, W)) {
-    launch_list64<false>(W, list_blocks(m_max), st, (const float*)feat_f, Hf, Wf, stride, pad, w_c, b_ids, ids, d_count, m_max,
-                         out, nullptr, nullptr, 0);
-  } else if (map_dtype == FM_F32 && layout == 1 && Cf == 64 && (W == 5 || W == 7)) {
-    // channels-last fast path: one wave per window, 16-byte chunks
-    with_window(W, [&](auto w) {
-      hipLaunchKernelGGL(k_gather_nhwc64<decltype(w)::value>, dim3(list_blocks(m_max)), dim3(256), 0, st,
-                         (const float*)feat_f, Hf, Wf, stride, pad, w_c, b_ids, ids, d_count, m_max, out);
-    });
-  } else if (map_dtype == FM_F32) {
-    launch_generic_gather<FM_F32>(feat_f, Cf, Hf, Wf, layout, W, stride, pad, w_c, b_ids, ids, d_count, m_max, out, st);
-  } else if (map_dtype == FM_F16) {
-    // half-precision maps (an autocast backbone's hand-over): read as they are - every value is exact in float32 -
-    // by the generic kernels; no up-cast pass over the whole map in front of the crop
-    launch_generic_gather<FM_F16>(feat_f, Cf, Hf, Wf, layout, W, stride, pad, w_c, b_ids, ids, d_count, m_max, out, st);
-  } else {
-    launch_generic_gather<FM_BF16>(feat_f, Cf, Hf, Wf, layout, W, stride, pad, w_c, b_ids, ids, d_count, m_max, out, st);
-  }
-  return (int)hipGetLastError();
+  return run_window_call({1, {{feat_f, Hf, Wf, 0, w_c, ids, nullptr, 0, nullptr, out, nullptr}}, N, Cf, W, stride, pad, layout,
+                          map_dtype, b_ids, d_count, m_max, nullptr, stream, /*cells*/ false, /*merge*/ false, /*free_size*/ true});
 }
 
 extern "C" int fm_gather_windows(const float* feat_f, int N, int Cf, int Hf, int Wf, int layout, int W, int stride,
@@ -764,13 +815,8 @@ extern "C" int fm_gather_windows_cells(const float* feat_f, int N, int Cf, int H
                                        int h_c, int w_c, const int32_t* cell_to_match, int cell_pitch,
                                        const int32_t* ties, const int64_t* b_ids, const int64_t* ids,
                                        const int32_t* d_count, int m_max, float* out, void* stream) {
-  if (m_max == 0) return FM_OK;
-  if (!feat_f || !cell_to_match || !ties || !b_ids || !ids || !out) return FM_E_NULL;
-  if (!crop_shape_ok(N, Hf, Wf, stride, m_max) || h_c <= 0 || w_c <= 0 || cell_pitch < h_c * w_c) return FM_E_SHAPE;
-  if (!fast_nchw64(Cf, Hf, Wf, W)) return FM_E_UNSUPPORTED;
-  const CellImage im = cell_image(feat_f, N, Hf, Wf, h_c, w_c, cell_to_match, cell_pitch, ties, ids, out, nullptr);
-  return launch_cells64(W, 1, (long)N * h_c * w_c, cell_args(im, im, stride, pad, m_max, b_ids, d_count, nullptr),
-                        (hipStream_t)stream);
+  return run_window_call({1, {{feat_f, Hf, Wf, h_c, w_c, ids, cell_to_match, cell_pitch, ties, out, nullptr}}, N, Cf, W, stride,
+                          pad, 0, FM_F32, b_ids, d_count, m_max, nullptr, stream, /*cells*/ true});
 }
 
 // merge_feat.weight[:, :64] (row-major [64, 128], fine_preprocess.py:26) -> MFMA B fragments, f16 hi and lo:
@@ -805,20 +851,9 @@ extern "C" int fm_gather_merge_windows(const float* feat_f, int N, int Cf, int H
                                        const int32_t* ties, const void* packed_w, const float* ctx_bias,
                                        const int64_t* b_ids, const int64_t* ids, const int32_t* d_count, int m_max,
                                        float* out, void* stream) {
-  if (m_max == 0) return FM_OK;
-  if (!feat_f || !packed_w || !ctx_bias || !b_ids || !ids || !out) return FM_E_NULL;
-  if (cell_to_match && !ties) return FM_E_NULL;
-  if (!crop_shape_ok(N, Hf, Wf, stride, m_max) || h_c <= 0 || w_c <= 0 || (cell_to_match && cell_pitch < h_c * w_c))
-    return FM_E_SHAPE;
-  if (!fast_nchw64(Cf, Hf, Wf, W)) return FM_E_UNSUPPORTED;
-  hipStream_t st = (hipStream_t)stream;
-  if (cell_to_match) {
-    const CellImage im = cell_image(feat_f, N, Hf, Wf, h_c, w_c, cell_to_match, cell_pitch, ties, ids, out, ctx_bias);
-    return launch_cells64(W, 1, (long)N * h_c * w_c, cell_args(im, im, stride, pad, m_max, b_ids, d_count, packed_w), st);
-  }
-  launch_list64<true>(W, list_blocks(m_max), st, feat_f, Hf, Wf, stride, pad, w_c, b_ids, ids, d_count, m_max, out,
-                      (const half8*)packed_w, ctx_bias, h_c * w_c);
-  return (int)hipGetLastError();
+  return run_window_call({1, {{feat_f, Hf, Wf, h_c, w_c, ids, cell_to_match, cell_pitch, ties, out, ctx_bias}}, N, Cf, W, stride,
+                          pad, 0, FM_F32, b_ids, d_count, m_max, packed_w, stream,
+                          /*cells, else list order*/ cell_to_match != nullptr, /*merge*/ true});
 }
 
 extern "C" int fm_gather_windows_pair(const float* feat_f0, const float* feat_f1, int N, int Cf, int Hf0, int Wf0,
@@ -828,26 +863,10 @@ extern "C" int fm_gather_windows_pair(const float* feat_f0, const float* feat_f1
                                       const float* ctx1, const int64_t* b_ids, const int64_t* i_ids,
                                       const int64_t* j_ids, const int32_t* d_count, int m_max, float* out0,
                                       float* out1, void* stream) {
-  if (m_max == 0) return FM_OK;
-  if (!feat_f0 || !feat_f1 || !cell0 || !cell1 || !ties0 || !ties1 || !b_ids || !i_ids || !j_ids || !out0 || !out1)
-    return FM_E_NULL;
-  if (packed_w && (!ctx0 || !ctx1)) return FM_E_NULL;
-  if (!crop_shape_ok(N, Hf0, Wf0, stride, m_max) || !crop_shape_ok(N, Hf1, Wf1, stride, m_max) || h0c <= 0 || w0c <= 0 ||
-      h1c <= 0 || w1c <= 0 || pitch0 < h0c * w0c || pitch1 < h1c * w1c)
-    return FM_E_SHAPE;
-  if (!fast_nchw64(Cf, Hf0, Wf0, W) || !fast_nchw64(Cf, Hf1, Wf1, W)) return FM_E_UNSUPPORTED;
-  const CellArgs a = cell_args(cell_image(feat_f0, N, Hf0, Wf0, h0c, w0c, cell0, pitch0, ties0, i_ids, out0, ctx0),
-                               cell_image(feat_f1, N, Hf1, Wf1, h1c, w1c, cell1, pitch1, ties1, j_ids, out1, ctx1), stride,
-                               pad, m_max, b_ids, d_count, packed_w);
-  const long t0 = (long)N * h0c * w0c, t1 = (long)N * h1c * w1c;
-  return launch_cells64(W, 2, t0 > t1 ? t0 : t1, a, (hipStream_t)stream);
-}
-
-static MergeNhwcImage merge_nhwc_image(const void* feat, int Hf, int Wf, int h_c, int w_c, const int64_t* ids, float* out,
-                                       const float* ctx) {
-  MergeNhwcImage im;
-  im.feat = feat; im.Hf = Hf; im.Wf = Wf; im.w_c = w_c; im.cells = h_c * w_c; im.ids = ids; im.out = out; im.ctx = ctx;
-  return im;
+  return run_window_call({2, {{feat_f0, Hf0, Wf0, h0c, w0c, i_ids, cell0, pitch0, ties0, out0, ctx0},
+                              {feat_f1, Hf1, Wf1, h1c, w1c, j_ids, cell1, pitch1, ties1, out1, ctx1}},
+                          N, Cf, W, stride, pad, 0, FM_F32, b_ids, d_count, m_max, packed_w, stream,
+                          /*cells*/ true, /*merge, else the plain crop*/ packed_w != nullptr});
 }
 
 extern "C" int fm_gather_merge_windows_nhwc(const void* feat_f0, const void* feat_f1, int map_dtype, int N, int Cf, int Hf0,
@@ -855,28 +874,10 @@ extern "C" int fm_gather_merge_windows_nhwc(const void* feat_f0, const void* fea
                                             int h1c, int w1c, const void* packed_w, const float* ctx0, const float* ctx1,
                                             const int64_t* b_ids, const int64_t* i_ids, const int64_t* j_ids,
                                             const int32_t* d_count, int m_max, float* out0, float* out1, void* stream) {
-  if (m_max == 0) return FM_OK;
-  const bool pair = feat_f1 != nullptr;
-  if (!feat_f0 || !packed_w || !ctx0 || !b_ids || !i_ids || !out0) return FM_E_NULL;
-  if (pair && (!ctx1 || !j_ids || !out1)) return FM_E_NULL;
-  if (!crop_shape_ok(N, Hf0, Wf0, stride, m_max) || h0c <= 0 || w0c <= 0) return FM_E_SHAPE;
-  if (pair && (!crop_shape_ok(N, Hf1, Wf1, stride, m_max) || h1c <= 0 || w1c <= 0)) return FM_E_SHAPE;
-  if (map_dtype != FM_F32 && map_dtype != FM_F16 && map_dtype != FM_BF16) return FM_E_UNSUPPORTED;
-  if (Cf != 64 || (W != 5 && W != 7)) return FM_E_UNSUPPORTED;
-  MergeNhwcArgs a;
-  a.im[0] = merge_nhwc_image(feat_f0, Hf0, Wf0, h0c, w0c, i_ids, out0, ctx0);
-  a.im[1] = pair ? merge_nhwc_image(feat_f1, Hf1, Wf1, h1c, w1c, j_ids, out1, ctx1) : a.im[0];
-  a.stride = stride; a.pad = pad; a.m_max = m_max; a.b_ids = b_ids; a.d_count = d_count; a.wpack = (const half8*)packed_w;
-  with_window(W, [&](auto w) {
-    auto launch = [&](auto dt) {
-      hipLaunchKernelGGL((k_gather_merge_nhwc64<decltype(w)::value, decltype(dt)::value>),
-                         dim3(list_blocks(m_max), pair ? 2 : 1), dim3(256), 0, (hipStream_t)stream, a);
-    };
-    if (map_dtype == FM_F16) launch(int_c<FM_F16>{});
-    else if (map_dtype == FM_BF16) launch(int_c<FM_BF16>{});
-    else launch(int_c<FM_F32>{});
-  });
-  return (int)hipGetLastError();
+  return run_window_call({feat_f1 ? 2 : 1, {{feat_f0, Hf0, Wf0, h0c, w0c, i_ids, nullptr, 0, nullptr, out0, ctx0},
+                                            {feat_f1, Hf1, Wf1, h1c, w1c, j_ids, nullptr, 0, nullptr, out1, ctx1}},
+                          N, Cf, W, stride, pad, 1, map_dtype, b_ids, d_count, m_max, packed_w, stream, /*cells*/ false,
+                          /*merge*/ true});
 }
 
 extern "C" int fm_fine_match(const float* win0, const float* win1, int m_max, const int32_t* d_count, int WW, int Cf,
@@ -930,20 +931,13 @@ extern "C" int fm_fine_match_maps_dtype(const void* feat_f0, const void* feat_f1
                                         const int32_t* d_count, int m_max, const float* mix0, const float* mix1,
                                         const float* mkpts0_c, const float* mkpts1_c, float scale_f, void* scratch,
                                         float* out0, float* out1, void* stream) {
-  if (m_max == 0) return FM_OK;
-  if (!feat_f0 || !feat_f1 || !b_ids || !i_ids || !j_ids || !mix0 || !mix1 || !mkpts0_c || !mkpts1_c || !out0 || !out1)
-    return FM_E_NULL;
-  if (!crop_shape_ok(N, Hf0, Wf0, stride, m_max) || !crop_shape_ok(N, Hf1, Wf1, stride, m_max) || w0c <= 0 || w1c <= 0)
-    return FM_E_SHAPE;
-  if (map_dtype != FM_F32 && map_dtype != FM_F16 && map_dtype != FM_BF16) return FM_E_UNSUPPORTED;
-  if ((layout != 0 && layout != 1 && layout != FM_LAYOUT_NCHW_PREPARED) || !fast_nchw64(Cf, Hf0, Wf0, W) ||
-      !fast_nchw64(Cf, Hf1, Wf1, W))
-    return FM_E_UNSUPPORTED;
-  // (image 1's channels-last copy was made by the coarse call - fm_coarse_match_maps - into `scratch`: float32 maps only)
-  const bool prepared = layout == FM_LAYOUT_NCHW_PREPARED;
-  if (prepared && map_dtype != FM_F32) return FM_E_UNSUPPORTED;
-  if (prepared) layout = 0;
-  if (layout == 0 && !scratch) return FM_E_NULL;
+  const WindowCall c{2, {{feat_f0, Hf0, Wf0, 0, w0c, i_ids, nullptr, 0, nullptr, out0, nullptr},
+                         {feat_f1, Hf1, Wf1, 0, w1c, j_ids, nullptr, 0, nullptr, out1, nullptr}},
+                     N, Cf, W, stride, pad, layout, map_dtype, b_ids, d_count, m_max, nullptr, stream, /*cells*/ false,
+                     /*merge*/ false, /*free_size*/ false, /*fine*/ true, !mix0 || !mix1 || !mkpts0_c || !mkpts1_c, scratch};
+  const int status = window_status(c);
+  if (status != FM_OK || m_max == 0) return status;
+  const bool prepared = layout == FM_LAYOUT_NCHW_PREPARED, nchw = layout != 1;
   hipStream_t st = (hipStream_t)stream;
   const float* m0 = (const float*)feat_f0;
   const float* m1 = (const float*)feat_f1;
@@ -951,7 +945,7 @@ extern "C" int fm_fine_match_maps_dtype(const void* feat_f0, const void* feat_f1
 #ifdef FM_TUNE_ENV
   if (const char* e = getenv("FM_FINE_GRID")) grid_cap = atoi(e) > 0 ? atoi(e) / 8 * 8 : kFineGridCap;
 #endif
-  if (layout == 0) {   // NCHW: channels-last copies (coalesced on both sides), element type kept
+  if (nchw) {          // NCHW: channels-last copies (coalesced on both sides), element type kept
     const FineMapsScratch sc = fine_maps_layout(N, Cf, Hf0, Wf0, Hf1, Wf1, map_dtype);
     float* s0 = span_ptr<float>(scratch, sc.map[0]);
     float* s1 = span_ptr<float>(scratch, sc.map[1]);
@@ -966,15 +960,20 @@ extern "C" int fm_fine_match_maps_dtype(const void* feat_f0, const void* feat_f1
   }
   const int blocks = list_blocks(m_max) < grid_cap ? list_blocks(m_max) : grid_cap;
   with_window(W, [&](auto w) {
-    auto launch = [&](auto nchw0, auto dt) {
-      hipLaunchKernelGGL((k_fine_maps<decltype(w)::value, decltype(nchw0)::value, decltype(dt)::value>), dim3(blocks),
-                         dim3(256), 0, st, m0, m1, Hf0, Wf0, Hf1, Wf1, stride, pad, w0c, w1c, b_ids, i_ids, j_ids, d_count,
-                         m_max, mix0, mix1, mkpts0_c, mkpts1_c, scale_f, out0, out1);
-    };
-    if (map_dtype == FM_F16) launch(std::false_type{}, int_c<FM_F16>{});
-    else if (map_dtype == FM_BF16) launch(std::false_type{}, int_c<FM_BF16>{});
-    else if (layout == 0) launch(std::true_type{}, int_c<FM_F32>{});
-    else launch(std::false_type{}, int_c<FM_F32>{});
+    with_map_dtype(map_dtype, [&](auto dt) {
+      auto launch = [&](auto nchw0) {
+        hipLaunchKernelGGL((k_fine_maps<decltype(w)::value, decltype(nchw0)::value, decltype(dt)::value>), dim3(blocks),
+                           dim3(256), 0, st, m0, m1, Hf0, Wf0, Hf1, Wf1, stride, pad, w0c, w1c, b_ids, i_ids, j_ids, d_count,
+                           m_max, mix0, mix1, mkpts0_c, mkpts1_c, scale_f, out0, out1);
+      };
+      // float32 NCHW: image 0 straight from the map; every other form reads two channels-last maps
+      if constexpr (decltype(dt)::value == FM_F32) {
+        if (nchw) launch(std::true_type{});
+        else launch(std::false_type{});
+      } else {
+        launch(std::false_type{});
+      }
+    });
   });
   return (int)hipGetLastError();
 }

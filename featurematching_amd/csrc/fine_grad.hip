@@ -311,8 +311,8 @@ extern "C" int fm_gather_windows_backward(const float* d_win, const int64_t* b_i
                                           size_t workspace_bytes, float* d_feat, void* stream) {
   if (m_max == 0) return FM_OK;
   if (!d_win || !b_ids || !ids || !workspace || !d_feat) return FM_E_NULL;
-  if (!crop_shape_ok(N, Hf, Wf, stride, m_max) || Cf <= 0 || W <= 0 || h_c <= 0 || w_c <= 0) return FM_E_SHAPE;
-  if (W > 15 || Cf > 512 || (layout != 0 && layout != 1)) return FM_E_UNSUPPORTED;
+  if (!crop_shape_ok(N, Hf, Wf, stride, m_max) || !generic_window_shape_ok(Cf, W) || h_c <= 0 || w_c <= 0) return FM_E_SHAPE;
+  if (!generic_window_supported(Cf, W, layout)) return FM_E_UNSUPPORTED;
   if ((long)N * h_c * w_c >= (1L << 31) - 1 || (long)N * Hf >= (1L << 31) / ((Wf + 7) / 8)) return FM_E_UNSUPPORTED;
   const CropBwdWs ws = crop_bwd_layout(N, h_c, w_c, m_max);
   if (workspace_bytes < ws.total || ((uintptr_t)workspace & 255)) return FM_E_WORKSPACE;

@@ -60,6 +60,43 @@ inline bool crop_shape_ok(int N, int Hf, int Wf, int stride, int m_max) {
   return N > 0 && Hf > 0 && Wf > 0 && stride > 0 && m_max >= 0;
 }
 
+// the generic crop kernels and the crop's backward take any window up to 15 x 15 of up to 512 channels
+inline bool generic_window_shape_ok(int Cf, int W) { return Cf > 0 && W > 0; }
+inline bool generic_window_supported(int Cf, int W, int layout) {
+  return W <= 15 && Cf <= 512 && (layout == 0 || layout == 1);
+}
+inline bool map_dtype_ok(int dt) { return dt == FM_F32 || dt == FM_F16 || dt == FM_BF16; }
+// f(int_c<dt>) for a fine map's element type (map_dtype_ok(dt) is the caller's to have checked: anything else is float32)
+template <typename F>
+inline void with_map_dtype(int dt, F&& f) {
+  if (dt == FM_F16) f(int_c<FM_F16>{});
+  else if (dt == FM_BF16) f(int_c<FM_BF16>{});
+  else f(int_c<FM_F32>{});
+}
+
+// One window call as the crop ABI takes it: which W x W windows of which one or two fine maps, named by a match list.
+// Every forward entry point of fine.hip fills one and hands it on (window_status, window_route); what an entry point
+// does not have stays NULL / 0.
+struct WindowImage {
+  const void* feat; int Hf, Wf, h_c, w_c;
+  const int64_t* ids;
+  const int32_t* cell_map; int cell_pitch; const int32_t* ties;     // cell order: this image's cell -> match map, tie list
+  float* out; const float* ctx;                                     // ctx: the merge's per-cell context table
+};
+struct WindowCall {
+  int images; WindowImage im[2];                                    // im[1] is not looked at when images == 1
+  int N, Cf, W, stride, pad, layout, dtype;
+  const int64_t* b_ids; const int32_t* d_count; int m_max;
+  const void* wpack;                                                // packed merge weights
+  void* stream;
+  bool cells, merge;    // cell order (else list order); crop + context merge.  h_c is looked at only where one is set
+  bool free_size;       // fm_gather_windows*: Cf and W are the caller's (not positive: FM_E_SHAPE, where every other
+                        // entry point answers FM_E_UNSUPPORTED), and the element type is looked at before the shape
+  bool fine;            // fm_fine_match_maps*: crop + fine stage; layout may be FM_LAYOUT_NCHW_PREPARED, NCHW needs `scratch`
+  bool missing;         // ... one of the pointers only that entry point has (mix0 .. mkpts1_c) is NULL
+  void* scratch;
+};
+
 struct Scalars {          // lives at ws.scalars (zeroed per call)
   unsigned flags;         // FM_DEV_* bits
   int dense_units;        // 32x32 units the sparse sum kernel left to the dense one (0: that kernel exits at once)

@@ -269,12 +269,7 @@ class FinePreprocess(nn.Module):
         wants_grad = _wants_grad(feat_f0, feat_f1, feat_c0, feat_c1)
         nchw = feat_f0.is_contiguous() and feat_f1.is_contiguous()
         return self.fused_merge and not self.training and not wants_grad and self.d_model_f == 64 and W in (5, 7) \
-            and feat_f0.shape[1] == 64 and (nchw or self._both_channels_last(feat_f0, feat_f1))
-
-    @staticmethod
-    def _both_channels_last(feat_f0, feat_f1) -> bool:
-        return feat_f0.is_cuda and feat_f0.dtype == feat_f1.dtype and ops.merge_reads_in_place(feat_f0) \
-            and ops.merge_reads_in_place(feat_f1)
+            and feat_f0.shape[1] == 64 and (nchw or ops.maps_read_in_place(feat_f0, feat_f1))
 
     def _merge_constants(self):
         """(packed W_w fragments, E = W_c . down_proj.weight [64, C], e = W_c . down_proj.bias + merge bias),
@@ -336,7 +331,7 @@ class FinePreprocess(nn.Module):
                     ctx1 = F.linear(feat_c1.float(), e_w, e_b)
                 # one launch for both images: cell order on NCHW maps (needs this coarse call's cell maps), list order on
                 # channels-last maps (fm_gather_merge_windows_nhwc reads them in place and needs no cell map)
-                nhwc = self._both_channels_last(feat_f0, feat_f1)
+                nhwc = ops.maps_read_in_place(feat_f0, feat_f1)
                 if (cells0 is not None or nhwc) and feat_f1.shape[1] == 64:
                     win0, win1 = ops.gather_windows_pair(feat_f0, feat_f1, b_ids, i_ids, j_ids, W, stride, hw0_c, hw1_c,
                                                          None if nhwc else (cells0, cells1), packed_w=packed, ctx0=ctx0,

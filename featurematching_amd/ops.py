@@ -684,17 +684,83 @@ def fine_loss(expec0: torch.Tensor, expec1: torch.Tensor, gt0: torch.Tensor, gt1
     return loss
 
 
+def _stored_layout(t: torch.Tensor) -> Optional[int]:
+    """0 = NCHW-contiguous, 1 = channels-last storage (and not also NCHW-contiguous), None = any other strides"""
+    if t.is_contiguous():
+        return 0
+    return 1 if t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last) else None
+
+
 def _map_layout(t: torch.Tensor):
     """(tensor, layout) of a logical [N,Cf,Hf,Wf] fine map as the crop and fine kernels read it: 0 = NCHW-contiguous
     (any other strides are copied to it), 1 = channels-last storage.  float32, float16 and bfloat16 maps are taken as
     they are (no up-cast pass)."""
     if t.dtype not in _DTYPES:
         t = t.float()
-    if t.is_contiguous():
-        return t, 0
-    if t.is_contiguous(memory_format=torch.channels_last):
-        return t, 1
-    return t.contiguous(), 0
+    layout = _stored_layout(t)
+    return (t.contiguous(), 0) if layout is None else (t, layout)
+
+
+def merge_reads_in_place(feat_f: torch.Tensor) -> bool:
+    """A channels-last float32 / float16 / bfloat16 map goes to fm_gather_merge_windows_nhwc as it is (no layout
+    copy, no up-cast pass); every other map takes the NCHW float32 kernels."""
+    return feat_f.dim() == 4 and feat_f.dtype in _DTYPES and _stored_layout(feat_f) == 1
+
+
+def maps_read_in_place(feat_f0: torch.Tensor, feat_f1: torch.Tensor) -> bool:
+    """... both maps, in one element type (what gather_windows_pair and modules.FinePreprocess both ask)"""
+    return feat_f0.is_cuda and feat_f0.dtype == feat_f1.dtype and merge_reads_in_place(feat_f0) \
+        and merge_reads_in_place(feat_f1)
+
+
+def _fast_nchw64(cf: int, hf: int, wf: int, w: int) -> bool:
+    """what the 64-channel NCHW float32 kernels serve (csrc/fine.hip, window_route): sizes and 31-bit byte offsets"""
+    return cf == 64 and w in (5, 7) and hf * wf * 64 * 4 < 1 << 31
+
+
+class _Windows:
+    """One window call prepared: the map(s) as the kernels read them (one layout and element type per call: image 1
+    follows image 0), the outputs [M, *out_tail], m_max, each image's coarse grid, its cell map (cells[i] = one entry of
+    CoarseBuffers.cell_maps(), or None: list order) as ctypes values and its checked context table.  nchw_f32: the
+    call's kernels read NCHW float32 only (anything else is copied to it); otherwise _map_layout decides."""
+
+    def __init__(self, feats, b_ids, out_tail, outs, hw_c, nchw_f32=False, cells=None, ctx=None):
+        names = ("feat_f",) if len(feats) == 1 else ("feat_f0", "feat_f1")
+        _on_gpu(feats[0], names[0])
+        if nchw_f32:
+            self.maps, self.layout = [_f32c(f, nm) for f, nm in zip(feats, names)], 0
+        else:
+            f0, self.layout = _map_layout(feats[0])
+            mf = torch.channels_last if self.layout else torch.contiguous_format
+            self.maps = [f0] + [_map_layout(f)[0].to(f0.dtype).contiguous(memory_format=mf) for f in feats[1:]]
+        self.n, self.cf = self.maps[0].shape[:2]
+        self.sizes = [tuple(f.shape[2:]) for f in self.maps]
+        self.dev, self.dt = self.maps[0].device, _DTYPES[self.maps[0].dtype]
+        self.m_max = int(b_ids.shape[0])
+        self.outs = [torch.empty(self.m_max, *out_tail, dtype=torch.float32, device=self.dev) if o is None else o
+                     for o in outs]
+        self.hw_c = [(int(h or 0), int(w)) for h, w in hw_c]
+        self.cells = [(None, 0, None) if c is None else (C.c_void_p(c[0]), int(c[1]), C.c_void_p(c[2]))
+                      for c in cells or [None] * len(feats)]
+        self.ctx = []
+        for i, t in enumerate(ctx or ()):
+            t, want = _f32c(t, f"ctx{i}"), (self.n, self.hw_c[i][0] * self.hw_c[i][1], 64)
+            if tuple(t.shape) != want:
+                raise ValueError(f"ctx{i} must be {list(want)}, got {tuple(t.shape)}")
+            self.ctx.append(t)
+
+    def run(self, name: str, *args) -> None:
+        """the C call `name` on the maps' stream (its last argument); a status raises"""
+        _lib.check(getattr(_lib.load(), name)(*args, _stream(self.dev)), name)
+
+    def merge_nhwc(self, w, stride, pad, packed_w, b_ids, ids, count) -> None:
+        """fm_gather_merge_windows_nhwc on the call's one or two channels-last maps (list order; image 1 absent: NULL / 0)"""
+        def of(xs, k, absent=None):
+            return xs[k] if k < len(self.maps) else absent
+        f, c, i, o = ([_ptr(of(xs, k)) for k in (0, 1)] for xs in (self.maps, self.ctx, ids, self.outs))
+        self.run("fm_gather_merge_windows_nhwc", f[0], f[1], self.dt, self.n, self.cf, *self.sizes[0], *of(self.sizes, 1, (0, 0)),
+                 w, stride, pad, *self.hw_c[0], *of(self.hw_c, 1, (0, 0)), _ptr(packed_w), c[0], c[1], _ptr(b_ids), i[0], i[1],
+                 _ptr(count), self.m_max, o[0], o[1])
 
 
 def gather_windows(feat_f: torch.Tensor, b_ids: torch.Tensor, ids: torch.Tensor, w: int, stride: int,
@@ -703,32 +769,22 @@ def gather_windows(feat_f: torch.Tensor, b_ids: torch.Tensor, ids: torch.Tensor,
     """Window crop (fine_preprocess.py:43-50) of the selected coarse cells only.
     feat_f is the logical [N,Cf,Hf,Wf] tensor, stored NCHW-contiguous or channels_last.
     cells = (map address, pitch, tie-list address) of this image (CoarseBuffers.cell_maps())
-    selects the cell-ordered kernel when the shape allows it (NCHW, Cf 64, W 5/7): the windows are
-    visited in raster order of THIS image's cells, which keeps each XCD's reads inside a band of the map."""
-    lib = _lib.load()
-    n, cf, hf, wf = _on_gpu(feat_f, "feat_f").shape
-    feat_f, layout = _map_layout(feat_f)
-    m_max = int(b_ids.shape[0])
-    if out is None:
-        out = torch.empty(m_max, w * w, cf, dtype=torch.float32, device=feat_f.device)
-    if m_max == 0:
-        return out
-    if feat_f.dtype != torch.float32:
-        st = lib.fm_gather_windows_dtype(_ptr(feat_f), _DTYPES[feat_f.dtype], n, cf, hf, wf, layout, w, stride, pad, w_c,
-                                         _ptr(b_ids), _ptr(ids), _ptr(count), m_max, _ptr(out), _stream(feat_f.device))
-        _lib.check(st, "fm_gather_windows_dtype")
-        return out
-    if cells is not None and layout == 0 and cf == 64 and w in (5, 7) and h_c:
-        st = lib.fm_gather_windows_cells(_ptr(feat_f), n, cf, hf, wf, w, stride, pad, int(h_c), int(w_c),
-                                         C.c_void_p(cells[0]), int(cells[1]), C.c_void_p(cells[2]), _ptr(b_ids), _ptr(ids),
-                                         _ptr(count), m_max, _ptr(out), _stream(feat_f.device))
-        if st != _lib.FM_E_UNSUPPORTED:    # fall through to the per-window kernel
-            _lib.check(st, "fm_gather_windows_cells")
-            return out
-    st = lib.fm_gather_windows(_ptr(feat_f), n, cf, hf, wf, layout, w, stride, pad, w_c, _ptr(b_ids), _ptr(ids),
-                               _ptr(count), m_max, _ptr(out), _stream(feat_f.device))
-    _lib.check(st, "fm_gather_windows")
-    return out
+    selects the cell-ordered kernel when the shape allows it (NCHW float32, Cf 64, W 5/7, h_c given): the windows are
+    visited in raster order of THIS image's cells, which keeps each XCD's reads inside a band of the map.  Any other
+    shape takes the per-window kernels, silently."""
+    p = _Windows([feat_f], b_ids, (w * w, feat_f.shape[1]), [out], [(h_c, w_c)], cells=[cells])
+    if p.m_max == 0:
+        return p.outs[0]
+    (hf, wf), (h_c, w_c) = p.sizes[0], p.hw_c[0]
+    head = (_ptr(p.maps[0]), p.n, p.cf, hf, wf)
+    tail = (_ptr(b_ids), _ptr(ids), _ptr(count), p.m_max, _ptr(p.outs[0]))
+    if p.dt != _lib.FM_F32:
+        p.run("fm_gather_windows_dtype", head[0], p.dt, *head[1:], p.layout, w, stride, pad, w_c, *tail)
+    elif cells is not None and h_c and p.layout == 0 and _fast_nchw64(p.cf, hf, wf, w):
+        p.run("fm_gather_windows_cells", *head, w, stride, pad, h_c, w_c, *p.cells[0], *tail)
+    else:
+        p.run("fm_gather_windows", *head, p.layout, w, stride, pad, w_c, *tail)
+    return p.outs[0]
 
 
 def pack_merge_weights(merge_w: torch.Tensor) -> torch.Tensor:
@@ -742,13 +798,6 @@ def pack_merge_weights(merge_w: torch.Tensor) -> torch.Tensor:
     return packed
 
 
-def merge_reads_in_place(feat_f: torch.Tensor) -> bool:
-    """A channels-last float32 / float16 / bfloat16 map goes to fm_gather_merge_windows_nhwc as it is (no layout
-    copy, no up-cast pass); every other map takes the NCHW float32 kernels."""
-    return (feat_f.dim() == 4 and feat_f.dtype in _DTYPES and not feat_f.is_contiguous()
-            and feat_f.is_contiguous(memory_format=torch.channels_last))
-
-
 def gather_merge_windows(feat_f: torch.Tensor, packed_w: torch.Tensor, ctx_bias: torch.Tensor, b_ids: torch.Tensor,
                          ids: torch.Tensor, w: int, stride: int, h_c: int, w_c: int, pad: int = 2,
                          count: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
@@ -756,34 +805,18 @@ def gather_merge_windows(feat_f: torch.Tensor, packed_w: torch.Tensor, ctx_bias:
     """Window crop fused with FinePreprocess's context merge (fine_preprocess.py:43-60): returns
     merge_feat(cat[window, down_proj(feat_c)]) for the selected cells, [M, WW, 64].  ctx_bias [N, h_c*w_c, 64]
     is the position-independent half (W_c . down_proj(feat_c) + bias) per coarse cell.
-    A channels-last map (float32, float16 or bfloat16) is read in place, in list order (`cells` is ignored); the
-    result is bit-identical to the call on the same float32 values stored NCHW."""
-    lib = _lib.load()
-    n, cf, hf, wf = _on_gpu(feat_f, "feat_f").shape
-    nhwc = merge_reads_in_place(feat_f)
-    if not nhwc:
-        feat_f = _f32c(feat_f, "feat_f")
-    ctx_bias = _f32c(ctx_bias, "ctx_bias")
-    if tuple(ctx_bias.shape) != (n, h_c * w_c, 64):
-        raise ValueError(f"ctx_bias must be [{n}, {h_c * w_c}, 64], got {tuple(ctx_bias.shape)}")
-    m_max = int(b_ids.shape[0])
-    if out is None:
-        out = torch.empty(m_max, w * w, cf, dtype=torch.float32, device=feat_f.device)
-    if m_max == 0:
-        return out
-    if nhwc:        # list order (`cells` is not needed: a channels-last window is W contiguous runs wherever it lies)
-        st = lib.fm_gather_merge_windows_nhwc(_ptr(feat_f), None, _DTYPES[feat_f.dtype], n, cf, hf, wf, 0, 0, w, stride,
-                                              pad, int(h_c), int(w_c), 0, 0, _ptr(packed_w), _ptr(ctx_bias), None,
-                                              _ptr(b_ids), _ptr(ids), None, _ptr(count), m_max, _ptr(out), None,
-                                              _stream(feat_f.device))
-        _lib.check(st, "fm_gather_merge_windows_nhwc")
-        return out
-    cm, cp, ct = (C.c_void_p(cells[0]), int(cells[1]), C.c_void_p(cells[2])) if cells is not None else (None, 0, None)
-    st = lib.fm_gather_merge_windows(_ptr(feat_f), n, cf, hf, wf, w, stride, pad, int(h_c), int(w_c), cm, cp, ct,
-                                     _ptr(packed_w), _ptr(ctx_bias), _ptr(b_ids), _ptr(ids), _ptr(count), m_max,
-                                     _ptr(out), _stream(feat_f.device))
-    _lib.check(st, "fm_gather_merge_windows")
-    return out
+    A channels-last map (float32, float16 or bfloat16) is read in place, in list order (`cells` is ignored: such a
+    window is W contiguous runs wherever it lies); the result is bit-identical to the call on the same float32 values
+    stored NCHW."""
+    nhwc = merge_reads_in_place(_on_gpu(feat_f, "feat_f"))
+    p = _Windows([feat_f], b_ids, (w * w, feat_f.shape[1]), [out], [(h_c, w_c)], nchw_f32=not nhwc,
+                 cells=[None if nhwc else cells], ctx=[ctx_bias])
+    if p.m_max and nhwc:
+        p.merge_nhwc(w, stride, pad, packed_w, b_ids, [ids], count)
+    elif p.m_max:
+        p.run("fm_gather_merge_windows", _ptr(p.maps[0]), p.n, p.cf, *p.sizes[0], w, stride, pad, *p.hw_c[0], *p.cells[0],
+              _ptr(packed_w), _ptr(p.ctx[0]), _ptr(b_ids), _ptr(ids), _ptr(count), p.m_max, _ptr(p.outs[0]))
+    return p.outs[0]
 
 
 def gather_windows_pair(feat_f0: torch.Tensor, feat_f1: torch.Tensor, b_ids, i_ids, j_ids, w: int, stride: int,
@@ -793,39 +826,18 @@ def gather_windows_pair(feat_f0: torch.Tensor, feat_f1: torch.Tensor, b_ids, i_i
     packed_w / ctx0 / ctx1 the crop is fused with the context merge.  NCHW maps, Cf = 64, W in {5,7}.
     The fused form also reads two channels-last maps of one element type (float32, float16, bfloat16) in place, in
     list order (`cells` is ignored, may be None): same outputs, bit for bit."""
-    lib = _lib.load()
-    nhwc = packed_w is not None and feat_f0.is_cuda and feat_f0.dtype == feat_f1.dtype \
-        and merge_reads_in_place(feat_f0) and merge_reads_in_place(feat_f1)
-    f0, f1 = (feat_f0, feat_f1) if nhwc else (_f32c(feat_f0, "feat_f0"), _f32c(feat_f1, "feat_f1"))
-    n, cf, hf0, wf0 = f0.shape
-    hf1, wf1 = f1.shape[2:]
-    m_max = int(b_ids.shape[0])
-    if out0 is None:
-        out0 = torch.empty(m_max, w * w, cf, dtype=torch.float32, device=f0.device)
-    if out1 is None:
-        out1 = torch.empty(m_max, w * w, cf, dtype=torch.float32, device=f0.device)
-    if m_max == 0:
-        return out0, out1
-    if packed_w is not None:
-        ctx0, ctx1 = _f32c(ctx0, "ctx0"), _f32c(ctx1, "ctx1")
-    if nhwc:
-        for name, ctx, hw in (("ctx0", ctx0, hw0_c), ("ctx1", ctx1, hw1_c)):
-            if tuple(ctx.shape) != (n, int(hw[0]) * int(hw[1]), 64):
-                raise ValueError(f"{name} must be [{n}, {int(hw[0]) * int(hw[1])}, 64], got {tuple(ctx.shape)}")
-        st = lib.fm_gather_merge_windows_nhwc(_ptr(f0), _ptr(f1), _DTYPES[f0.dtype], n, cf, hf0, wf0, hf1, wf1, w, stride,
-                                              pad, int(hw0_c[0]), int(hw0_c[1]), int(hw1_c[0]), int(hw1_c[1]),
-                                              _ptr(packed_w), _ptr(ctx0), _ptr(ctx1), _ptr(b_ids), _ptr(i_ids),
-                                              _ptr(j_ids), _ptr(count), m_max, _ptr(out0), _ptr(out1), _stream(f0.device))
-        _lib.check(st, "fm_gather_merge_windows_nhwc")
-        return out0, out1
-    (m0, p0, t0), (m1, p1, t1) = cells
-    st = lib.fm_gather_windows_pair(_ptr(f0), _ptr(f1), n, cf, hf0, wf0, hf1, wf1, w, stride, pad, int(hw0_c[0]),
-                                    int(hw0_c[1]), int(hw1_c[0]), int(hw1_c[1]), C.c_void_p(m0), int(p0), C.c_void_p(t0),
-                                    C.c_void_p(m1), int(p1), C.c_void_p(t1), _ptr(packed_w), _ptr(ctx0), _ptr(ctx1),
-                                    _ptr(b_ids), _ptr(i_ids), _ptr(j_ids), _ptr(count), m_max, _ptr(out0), _ptr(out1),
-                                    _stream(f0.device))
-    _lib.check(st, "fm_gather_windows_pair")
-    return out0, out1
+    merge = packed_w is not None
+    nhwc = merge and maps_read_in_place(feat_f0, feat_f1)
+    p = _Windows([feat_f0, feat_f1], b_ids, (w * w, feat_f0.shape[1]), [out0, out1], [hw0_c, hw1_c], nchw_f32=not nhwc,
+                 cells=None if nhwc else cells, ctx=[ctx0, ctx1] if merge else None)
+    if p.m_max and nhwc:
+        p.merge_nhwc(w, stride, pad, packed_w, b_ids, [i_ids, j_ids], count)
+    elif p.m_max:
+        c0, c1 = p.ctx or (None, None)
+        p.run("fm_gather_windows_pair", _ptr(p.maps[0]), _ptr(p.maps[1]), p.n, p.cf, *p.sizes[0], *p.sizes[1], w, stride, pad,
+              *p.hw_c[0], *p.hw_c[1], *p.cells[0], *p.cells[1], _ptr(packed_w), _ptr(c0), _ptr(c1), _ptr(b_ids),
+              _ptr(i_ids), _ptr(j_ids), _ptr(count), p.m_max, _ptr(p.outs[0]), _ptr(p.outs[1]))
+    return p.outs[0], p.outs[1]
 
 
 def fine_match(win0: torch.Tensor, win1: torch.Tensor, mix0: torch.Tensor, mix1: torch.Tensor,
@@ -953,36 +965,23 @@ def fine_match_maps(feat_f0: torch.Tensor, feat_f1: torch.Tensor, b_ids, i_ids, 
     `prepared`: the scratch buffer a coarse_match_async(side_map=feat_f1) call filled (FM_LAYOUT_NCHW_PREPARED: NCHW
     float32 maps, image 1's copy exists already - no transpose launch here).
     Returns (mkpts0_f, mkpts1_f), float32."""
-    lib = _lib.load()
-    f0, lay0 = _map_layout(_on_gpu(feat_f0, "feat_f0"))
-    f1, lay1 = _map_layout(feat_f1)
-    if f1.dtype != f0.dtype:
-        f1 = f1.to(f0.dtype)
-    if lay0 != lay1:                                 # one layout per call
-        f1, lay1 = (f1.contiguous(), 0) if lay0 == 0 else (f1.contiguous(memory_format=torch.channels_last), 1)
-    n, cf, hf0, wf0 = f0.shape
-    hf1, wf1 = f1.shape[2:]
-    dev = f0.device
-    dt = _DTYPES[f0.dtype]
-    m_max = int(b_ids.shape[0])
-    out0 = torch.empty(m_max, 3, dtype=torch.float32, device=dev)
-    out1 = torch.empty(m_max, 3, dtype=torch.float32, device=dev)
-    if m_max == 0:
+    p = _Windows([feat_f0, feat_f1], b_ids, (3,), [None, None], [(0, w0c), (0, w1c)])
+    out0, out1 = p.outs
+    if p.m_max == 0:
         return out0, out1
-    need = int(lib.fm_fine_maps_scratch_bytes_dtype(n, cf, hf0, wf0, hf1, wf1, lay0, dt))
+    layout = p.layout
+    need = int(_lib.load().fm_fine_maps_scratch_bytes_dtype(p.n, p.cf, *p.sizes[0], *p.sizes[1], layout, p.dt))
     if prepared is not None:
-        if lay0 != 0 or dt != _lib.FM_F32 or prepared.numel() * prepared.element_size() < need:
+        if layout != 0 or p.dt != _lib.FM_F32 or prepared.numel() * prepared.element_size() < need:
             raise ValueError("prepared: NCHW float32 maps and the scratch a coarse_match_async(side_map=...) call filled")
-        scratch, lay0 = prepared, _lib.FM_LAYOUT_NCHW_PREPARED
+        scratch, layout = prepared, _lib.FM_LAYOUT_NCHW_PREPARED
     if need and (scratch is None or scratch.numel() * scratch.element_size() < need):
-        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
-    st = lib.fm_fine_match_maps_dtype(_ptr(f0), _ptr(f1), dt, lay0, n, cf, hf0, wf0, hf1, wf1, w, stride, pad, int(w0c),
-                                      int(w1c), _ptr(b_ids), _ptr(i_ids), _ptr(j_ids), _ptr(count), m_max,
-                                      _ptr(_f32c(mix0, "mix0")), _ptr(_f32c(mix1, "mix1")), _ptr(_f32c(mkpts0_c, "mkpts0_c")),
-                                      _ptr(_f32c(mkpts1_c, "mkpts1_c")), float(scale_f), _ptr(scratch) if need else None,
-                                      _ptr(out0), _ptr(out1), _stream(dev))
-    _lib.check(st, "fm_fine_match_maps_dtype")
-    out0._keep = (f0, f1, scratch)
+        scratch = torch.empty(need, dtype=torch.uint8, device=p.dev)
+    p.run("fm_fine_match_maps_dtype", _ptr(p.maps[0]), _ptr(p.maps[1]), p.dt, layout, p.n, p.cf, *p.sizes[0], *p.sizes[1], w,
+          stride, pad, p.hw_c[0][1], p.hw_c[1][1], _ptr(b_ids), _ptr(i_ids), _ptr(j_ids), _ptr(count), p.m_max,
+          _ptr(_f32c(mix0, "mix0")), _ptr(_f32c(mix1, "mix1")), _ptr(_f32c(mkpts0_c, "mkpts0_c")),
+          _ptr(_f32c(mkpts1_c, "mkpts1_c")), float(scale_f), _ptr(scratch) if need else None, _ptr(out0), _ptr(out1))
+    out0._keep = (*p.maps, scratch)
     return out0, out1
 
 

@@ -128,5 +128,25 @@ m = side.read_count()
 so = side.sliced(m)
 sha("fine_prepared", *ops.fine_match_maps(ff0, ff1, so["b_ids"], so["i_ids"], so["j_ids"], 7, 4, HW[1], HW[1], mix0, mix1,
                                           so["mkpts0_c"], so["mkpts1_c"], 2.0, prepared=side.side_scratch))
+print("# gather_merge_windows, gather_windows_pair, more gather_windows, gather_windows_backward, fine_match_maps float16")
+gen = torch.Generator().manual_seed(11)
+packed = ops.pack_merge_weights((torch.randn(64, 128, generator=gen) * 0.1).to(DEV))
+ctx0, ctx1 = ((torch.randn(2, HW[0] * HW[1], 64, generator=gen) * 0.5).to(DEV) for _ in range(2))
+cells0, cells1 = buf.cell_maps()
+merge_maps = {"nchw_f32": ff0, "nhwc_f32": ff0.contiguous(memory_format=cl), "nhwc_f16": ff0.half().contiguous(memory_format=cl)}
+for tag, m in merge_maps.items():
+    for how, cm in (("list", None), ("cells", cells0)):
+        sha(f"merge_{tag}_{how}", ops.gather_merge_windows(m, packed, ctx0, b, i, 7, 4, *HW, cells=cm))
+sha("pair_plain", *ops.gather_windows_pair(ff0, ff1, b, i, j, 7, 4, HW, HW, (cells0, cells1)))
+sha("pair_merge", *ops.gather_windows_pair(ff0, ff1, b, i, j, 7, 4, HW, HW, (cells0, cells1), packed_w=packed, ctx0=ctx0,
+                                           ctx1=ctx1))
+sha("pair_merge_nhwc", *ops.gather_windows_pair(ff0.contiguous(memory_format=cl), ff1.contiguous(memory_format=cl), b, i, j, 7,
+                                                4, HW, HW, None, packed_w=packed, ctx0=ctx0, ctx1=ctx1))
+sha("crop_nchw_bf16", ops.gather_windows(ff0.bfloat16(), b, i, 7, 4, HW[1]))
+sha("crop_nhwc_f16", ops.gather_windows(ff0.half().contiguous(memory_format=cl), b, i, 7, 4, HW[1]))
+d_win = torch.randn(b.shape[0], 49, 64, generator=gen).to(DEV)
+for layout in (0, 1):
+    sha(f"crop_backward_layout{layout}", ops.gather_windows_backward(d_win, b, i, (2, 64, *HWF), 7, 4, HW[1], HW[0], layout=layout))
+sha("fine_nchw_f16", *ops.fine_match_maps(ff0.half(), ff1.half(), b, i, j, 7, 4, HW[1], HW[1], mix0, mix1, k0, k1, 2.0))
 torch.cuda.synchronize()
 print("# done")

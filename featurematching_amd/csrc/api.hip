@@ -163,9 +163,6 @@ extern "C" int fm_default_cand_slots(float thr) {
   return s;
 }
 
-// 1 / (C temperature): what scales a dot product into a similarity
-static float inv_ct_of(int C, float temperature) { return 1.0f / ((float)C * temperature); }
-
 // a power of two in [4, 64]: a row's slots are adjacent lanes of one wave and k_keep_emit keeps 256/slots <= 64 rows
 static bool valid_slots(int s) { return s >= 4 && s <= 64 && (s & (s - 1)) == 0; }
 

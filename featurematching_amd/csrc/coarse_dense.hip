@@ -20,10 +20,12 @@
 // Structure otherwise as before: one workgroup = 8 waves = a 256-row panel x a range of columns; each wave keeps its 32
 // rows' hi and lo A fragments (128 VGPRs at C = 256) for the whole sweep; the 8 waves' column sums of a unit meet in
 // LDS and one wave folds them in a fixed order (deterministic) into the panel's partial.
+//
+// At the end of this file: what makes the dense kernel's lists exact and patches its conf_matrix when a forward call
+// reads every entry (conf_matrix requests, FM_MODE_STATS) - k_exact_lists, k_fix_sums, k_conf_patch, their two launchers.
 #include <type_traits>
 
-#include "fm_device.h"
-#include "fm_wave_device.h"
+#include "fm_exact_device.h"
 
 namespace fm {
 
@@ -524,7 +526,7 @@ hipError_t launch_dense(const CoarseWs& w, char* base, float inv_ct, float thr, 
     a.pgroup = pgr < 1 ? 1 : (pgr > w.panels ? w.panels : pgr);
     if (a.splits == 1) a.pgroup = w.panels;
   }
-  a.k = inv_ct * kLog2e;
+  a.k = k2_of(inv_ct);
   a.lt = log2f(thr) - (rescreen ? 2e-4f : 0.f);      // the re-screening compares rounded log-softmax values: small guard
   const int blocks = w.N * a.splits * w.panels;
   return with_padded_channels(w.C, [&](auto cc) {
@@ -551,6 +553,140 @@ hipError_t launch_dense(const CoarseWs& w, char* base, float inv_ct, float thr, 
     }
     return hipGetLastError();
   });
+}
+
+// Dense data['conf_matrix'] (k_dense<C, CONF>: hi/lo-split float16 products, 22 significant bits - 2e-4 in a conf near 1 at
+// |sim| ~ 200): every entry that matters takes the exact float32 route.  For the samples the screening kernel served,
+// the rows' lists hold every entry with a row term above 2^-32 (all entries with conf > 2.4e-10 are among them) together
+// with its exact dot product; their conf is rewritten from that number and the same log-softmax offsets.
+// One thread per (row, slot).
+__global__ __launch_bounds__(256) void k_conf_patch(const int* __restrict__ rcount, const int* __restrict__ rlist_j,
+                                                    const float* __restrict__ rlist_x, const int* __restrict__ rcount_d,
+                                                    const int* __restrict__ rlist_j_d, const float* __restrict__ rlist_x_d,
+                                                    const float* __restrict__ nm_r,
+                                                    const float* __restrict__ sum_r, const float* __restrict__ nm_c,
+                                                    const float* __restrict__ sum_c, const int* __restrict__ dense_cnt, int N,
+                                                    int L, int S, int Lp, int Sp, int slots, float k2, float* __restrict__ conf) {
+  const long gid = (long)blockIdx.x * 256 + threadIdx.x;
+  const long grow = gid / slots;
+  const int slot = (int)(gid - grow * slots);
+  if (grow >= (long)N * Lp) return;
+  const int b = (int)(grow / Lp), i = (int)(grow - (long)b * Lp);
+  if (i >= L) return;
+  const bool dense = dense_cnt[b] > 0;         // the dense kernel's lists, made exact by k_exact_lists
+  if (slot >= min((dense ? rcount_d : rcount)[grow], slots)) return;
+  const float x = (dense ? rlist_x_d : rlist_x)[grow * slots + slot];
+  if (!(x > -INFINITY)) return;                    // a reserved but empty place
+  const int j = (dense ? rlist_j_d : rlist_j)[grow * slots + slot];
+  const long gcol = (long)b * Sp + j;
+  conf[((long)b * L + i) * S + j] = (__builtin_amdgcn_exp2f(__builtin_fmaf(x, k2, nm_r[grow])) / sum_r[grow]) *
+                                    (__builtin_amdgcn_exp2f(__builtin_fmaf(x, k2, nm_c[gcol])) / sum_c[gcol]);
+}
+
+// The samples the DENSE kernel served (flat similarity somewhere in the sample), when every entry is read (conf_matrix,
+// softmax statistics): the hi/lo-split float16 products carry 22 bits, 2^-22 |sim| ~ 4e-5 at similarities of ~170 - and
+// a peaked row of such a sample (conf ~ 1: the entry IS its row's and its column's denominator) is only right when the
+// entry and the two denominators hold the SAME x.  So the lists of such a sample - with a conf_matrix request they are
+// formed with min(thr, 0.1): every entry whose two softmax factors both exceed 0.1, i.e. every entry with conf > 0.1 -
+// are resolved exactly, entries and denominators together:
+//   k_exact_lists : 16 lanes per row list and per column list, its entries in turn: the exact float32 dot product of the caller's
+//                   descriptors (fm_exact_device.h: the screening's, and k_conf_at's) replaces the list's x; the term's change
+//                   exp2(k x + nm) - exp2(k x22 + nm) goes to the screening kernel's list region of the sample (idle)
+//   k_fix_sums    : one thread per row / column: adds the changes in index order (same bits every run) to the
+//                   denominator, refreshes the log-softmax offset
+// The assignment then reads exact x and matching denominators (mconf = the conf_matrix entry), k_conf_patch rewrites the
+// listed entries of the dense matrix.  What stays 22-bit has conf <= 0.1: 2 * 2^-22 |sim| conf <= 8e-6 at |sim| ~ 170.
+__global__ __launch_bounds__(256) void k_exact_lists(const void* __restrict__ f0, const void* __restrict__ f1, int in_dtype, int c_in,
+                                                     const int* __restrict__ rcount, const int* __restrict__ rkey, float* __restrict__ rx,
+                                                     float* __restrict__ rdelta, const int* __restrict__ ccount,
+                                                     const int* __restrict__ ckey, float* __restrict__ cx, float* __restrict__ cdelta,
+                                                     const float* __restrict__ nm_r, const float* __restrict__ nm_c,
+                                                     const int* __restrict__ dense_cnt, int N, int L, int S, int Lp, int Sp,
+                                                     int slots, float k2) {
+  const int side = blockIdx.z;
+  const int len = side ? Sp : Lp;
+  const long gl = (long)blockIdx.x * 16 + (threadIdx.x >> 4);           // one 16-lane group per list, its slots in turn
+  const int l16 = threadIdx.x & 15;
+  if (gl >= (long)N * len) return;
+  const int b = (int)(gl / len), own = (int)(gl - (long)b * len);
+  if (own >= (side ? S : L) || dense_cnt[b] == 0) return;              // (uniform over the group)
+  const int n = min((side ? ccount : rcount)[gl], slots);
+  const DescRows d = {f0, f1, c_in, in_dtype, L, S};
+  for (int slot = 0; slot < n; ++slot) {
+    const long at = gl * slots + slot;
+    const int other = (side ? ckey : rkey)[at];
+    const long ro = desc_row0(d, b, side ? other : own), co = desc_row1(d, b, side ? own : other);
+    float s = 0.f;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      float4 va, vb;
+      exact_dot16_load1(d, ro, co, l16, q, va, vb);
+      s = exact_dot16_link(s, va, vb);
+    }
+    const float x = row_sum16(s);
+    if (l16 == 0) {
+      float* xs = side ? cx : rx;
+      const float nm = (side ? nm_c : nm_r)[gl];
+      (side ? cdelta : rdelta)[at] = __builtin_amdgcn_exp2f(__builtin_fmaf(x, k2, nm)) - __builtin_amdgcn_exp2f(__builtin_fmaf(xs[at], k2, nm));
+      xs[at] = x;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void k_fix_sums(const int* __restrict__ rcount, const int* __restrict__ rkey,
+                                                  const float* __restrict__ rdelta, const int* __restrict__ ccount,
+                                                  const int* __restrict__ ckey, const float* __restrict__ cdelta,
+                                                  const float* __restrict__ nm_r, const float* __restrict__ nm_c,
+                                                  float* __restrict__ sum_r, float* __restrict__ sum_c, float* __restrict__ nm2_r,
+                                                  float* __restrict__ nm2_c, const int* __restrict__ dense_cnt, int Lp, int Sp,
+                                                  int slots) {
+  const int side = blockIdx.z, b = blockIdx.y;
+  const int len = side ? Sp : Lp;
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= len || dense_cnt[b] == 0) return;
+  const long gl = (long)b * len + idx;
+  const int n = min((side ? ccount : rcount)[gl], slots);
+  if (n == 0) return;
+  const int* key = (side ? ckey : rkey) + gl * slots;
+  const float* d = (side ? cdelta : rdelta) + gl * slots;
+  float acc = 0.f;
+  int last = -1;
+  for (int t = 0; t < n; ++t) {           // in index order (the lists are filled in the order the waves arrive)
+    int best = 0x7fffffff, at = 0;
+    for (int q = 0; q < n; ++q) { const int kq = key[q]; if (kq > last && kq < best) { best = kq; at = q; } }
+    acc += d[at];
+    last = best;
+  }
+  float* sum = side ? sum_c : sum_r;
+  const float v = sum[gl] + acc;
+  sum[gl] = v;
+  (side ? nm2_c : nm2_r)[gl] = (side ? nm_c : nm_r)[gl] - __log2f(v);
+}
+
+hipError_t launch_exact_lists(const CoarseWs& w, char* base, float inv_ct, const void* feat0, const void* feat1, int in_dtype,
+                              int c_in, hipStream_t st) {
+  // the dense kernel's lists; every term's change goes to the same slot of the sparse kernel's x arrays (idle for the
+  // samples the dense kernel redid), where k_fix_sums reads it
+  const CandList &rows = w.cand_b, &cols = w.ccand_b;
+  float *rdelta = w.cand.x.in(base), *cdelta = w.ccand.x.in(base);
+  const long groups = (long)w.N * max(w.Lp, w.Sp);
+  hipLaunchKernelGGL(k_exact_lists, dim3((unsigned)((groups + 15) / 16), 1, 2), dim3(256), 0, st, feat0, feat1, in_dtype, c_in,
+                     rows.count.in(base), rows.idx.in(base), rows.x.in(base), rdelta, cols.count.in(base), cols.idx.in(base),
+                     cols.x.in(base), cdelta, w.nmr.in(base), w.nmc.in(base), w.dense_cnt.in(base), w.N, w.L, w.S, w.Lp, w.Sp,
+                     w.slots, k2_of(inv_ct));
+  hipLaunchKernelGGL(k_fix_sums, dim3((max(w.Lp, w.Sp) + 255) / 256, w.N, 2), dim3(256), 0, st, rows.count.in(base),
+                     rows.idx.in(base), rdelta, cols.count.in(base), cols.idx.in(base), cdelta, w.nmr.in(base), w.nmc.in(base),
+                     w.rsum.in(base), w.csum.in(base), w.nmr2.in(base), w.nmc2.in(base), w.dense_cnt.in(base), w.Lp, w.Sp, w.slots);
+  return hipGetLastError();
+}
+
+hipError_t launch_conf_patch(const CoarseWs& w, char* base, float inv_ct, float* conf, hipStream_t st) {
+  const long total = (long)w.N * w.Lp * w.slots;
+  hipLaunchKernelGGL(k_conf_patch, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, w.cand.count.in(base),
+                     w.cand.idx.in(base), w.cand.x.in(base), w.cand_b.count.in(base), w.cand_b.idx.in(base), w.cand_b.x.in(base),
+                     w.nmr.in(base), w.rsum.in(base), w.nmc.in(base), w.csum.in(base), w.dense_cnt.in(base), w.N, w.L, w.S, w.Lp,
+                     w.Sp, w.slots, k2_of(inv_ct), conf);
+  return hipGetLastError();
 }
 
 }  // namespace fm

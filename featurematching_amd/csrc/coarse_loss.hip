@@ -6,7 +6,7 @@
 //     loss = wn ( sum_all l_neg(c) - sum_P l_neg(c_e) ) + wp sum_P l_pos(c_e)
 //     G    = dloss/dconf = wn l_neg'(c) [lo <= conf <= hi]                               at every entry
 //                        + ( wp l_pos'(c_e) - wn l_neg'(c_e) ) [lo <= conf_e <= hi]      at e in P
-// The dense part of G is a function of conf alone, so the tiled sweep of dsm_grad.hip (a workgroup owns 32 rows, sweeps
+// The dense part of G is a function of conf alone, so the tiled sweep of fm_sweep_device.h (a workgroup owns 32 rows, sweeps
 // the other image in 32-descriptor tiles, conf = A B from exact float32 dot products and the forward call's softmax
 // statistics) forms it in registers; the correction at P is a sparse g_e of the kind fm_dual_softmax_backward takes.
 // The backward of the dual softmax is linear in G: both parts land in the same row sums v and column sums u, and one
@@ -245,72 +245,34 @@ __global__ __launch_bounds__(256) void k_closs_scale(const float* __restrict__ g
   if (e < K) out[e] = gc[e] * d_loss[0];
 }
 
-// Workspace: the dual softmax backward's (v, u, part: fm_internal.h) | one loss partial (double) per workgroup of the kSums sweep |
-// the ids (0, 0, 0) of the stand-in entry of an empty supervision | per entry l_pos, l_neg, gc and gc * d_loss
-struct ClossWs { DsmBwdWs dsm; Span loss_part, zero_ids, l_pos, l_neg, gc, gcs; int Ke; size_t total; };
-static ClossWs closs_layout(int N, int L, int S, int C, int K) {
-  ClossWs w;
-  w.dsm = dsm_bwd_layout(N, L, S, C);
-  w.Ke = K > 0 ? K : 1;
-  const size_t per = align256((size_t)w.Ke * 4);
-  w.loss_part = {align256(w.dsm.total), align256((size_t)4 * N * ((L + 31) / 32) * 8)};
-  w.zero_ids = {w.loss_part.at + w.loss_part.bytes, 256};
-  w.l_pos = {w.zero_ids.at + w.zero_ids.bytes, per};
-  w.l_neg = {w.l_pos.at + per, per};
-  w.gc = {w.l_neg.at + per, per};
-  w.gcs = {w.gc.at + per, per};
-  w.total = w.gcs.at + per;
-  return w;
-}
-
-// one call of either entry point after its checks
+// one call of either entry point past its status (dsm_status) and carve: the loss's own arithmetic
 struct ClossCall {
-  DsmProblem p;
-  DsmStats s;
-  ClossWs w;
+  ClossWs w;                                  // (layout: fm_internal.h)
   LossParams lp;
   int kind;                                   // kCeLoss / kFocal2 / kFocalG
-  const int64_t *b_ids, *i_ids, *j_ids;       // Ke entries (the workspace's zeros when the supervision is empty)
+  DsmEntries e;                               // Ke entries (the workspace's zeros when the supervision is empty), no gc yet
   float pos_weight, neg_weight;               // as they count: 0 where the reference's degenerate cases set them to 0
   double inv_pos, inv_neg;
   bool stand_in;                              // empty supervision: the one listed entry is loss.py:38's (0, 0, 0)
 };
 
-static int closs_begin(const float* feat0, const float* feat1, int N, int L, int S, int C, float temperature, const DsmStats& s,
-                       int kind, float alpha, float gamma, float pos_weight, float neg_weight, const int64_t* b_ids,
-                       const int64_t* i_ids, const int64_t* j_ids, int K, void* workspace, size_t workspace_bytes,
-                       bool forward, hipStream_t st, ClossCall* c) {
-  if (!feat0 || !feat1 || !s.ofs_r || !s.ofs_c || !s.sum_r || !s.sum_c || !workspace) return FM_E_NULL;
-  if (K > 0 && (!b_ids || !i_ids || !j_ids)) return FM_E_NULL;
-  if (K < 0 || !(N > 0 && L > 0 && S > 0) || s.pitch_r < L || s.pitch_c < S) return FM_E_SHAPE;
-  if (!valid_channels(C) || !(temperature > 0.f)) return FM_E_UNSUPPORTED;
-  if ((kind != FM_LOSS_CROSS_ENTROPY && kind != FM_LOSS_FOCAL) || !(gamma > 0.f)) return FM_E_UNSUPPORTED;
-  const double total = (double)N * L * S;
-  if ((double)K > total) return FM_E_SHAPE;
-  c->w = closs_layout(N, L, S, C, K);
-  if (workspace_bytes < c->w.total || ((uintptr_t)workspace & 255)) return FM_E_WORKSPACE;
-  c->s = s;
-  // (the backward's v and u are the forward call's)
-  const int r = forward ? dsm_begin(feat0, feat1, N, L, S, C, temperature, s, workspace, workspace_bytes, st, &c->p)
-                        : dsm_carve(feat0, feat1, N, L, S, C, temperature, s, workspace, workspace_bytes, &c->p);
-  if (r != FM_OK) return r;
+static ClossCall closs_begin(const DsmCall& c) {
+  ClossCall q;
+  const LossSpec& l = c.loss; const int K = c.e.K;
+  q.w = closs_layout(c.N, c.L, c.S, c.C, K);
   // loss.py:37-42: without a positive, entry (0, 0, 0) stands in with weight 0 - in pos_mask only: neg_mask was taken
   // before, so the entry stays among the negatives; without a negative the negatives' weight is 0
-  c->stand_in = K == 0;
-  c->pos_weight = K > 0 ? pos_weight : 0.f;
-  const double n_neg = total - (double)K;
-  c->neg_weight = n_neg > 0 ? neg_weight : 0.f;
-  c->inv_pos = 1.0 / (double)c->w.Ke;
-  c->inv_neg = n_neg > 0 ? 1.0 / n_neg : 0.0;
-  c->kind = kind == FM_LOSS_CROSS_ENTROPY ? kCeLoss : (gamma == 2.0f ? kFocal2 : kFocalG);
-  c->lp = {alpha, gamma, (float)(c->neg_weight * c->inv_neg), (float)(c->pos_weight * c->inv_pos), 1e-6f, 1.0f - 1e-6f};
-  if (K > 0) {
-    c->b_ids = b_ids; c->i_ids = i_ids; c->j_ids = j_ids;
-  } else {
-    c->b_ids = c->i_ids = c->j_ids = span_ptr<const int64_t>(workspace, c->w.zero_ids);
-    if (forward) return (int)hipMemsetAsync(span_ptr<char>(workspace, c->w.zero_ids), 0, c->w.zero_ids.bytes, st);
-  }
-  return FM_OK;
+  q.stand_in = K == 0;
+  q.pos_weight = K > 0 ? l.pos_weight : 0.f;
+  const double n_neg = (double)c.N * c.L * c.S - (double)K;
+  q.neg_weight = n_neg > 0 ? l.neg_weight : 0.f;
+  q.inv_pos = 1.0 / (double)q.w.Ke;
+  q.inv_neg = n_neg > 0 ? 1.0 / n_neg : 0.0;
+  q.kind = l.kind == FM_LOSS_CROSS_ENTROPY ? kCeLoss : (l.gamma == 2.0f ? kFocal2 : kFocalG);
+  q.lp = {l.alpha, l.gamma, (float)(q.neg_weight * q.inv_neg), (float)(q.pos_weight * q.inv_pos), 1e-6f, 1.0f - 1e-6f};
+  const int64_t* zeros = span_ptr<const int64_t>(c.workspace, q.w.zero_ids);
+  q.e = q.stand_in ? DsmEntries{zeros, zeros, zeros, nullptr, 1} : DsmEntries{c.e.b_ids, c.e.i_ids, c.e.j_ids, nullptr, K};
+  return q;
 }
 
 template <typename F>
@@ -318,33 +280,25 @@ static hipError_t with_kind(int kind, F&& f) {
   return kind == kCeLoss ? f(int_c<kCeLoss>{}) : kind == kFocal2 ? f(int_c<kFocal2>{}) : f(int_c<kFocalG>{});
 }
 
-// the tiled sweep of one side (0: owner = image 0, 1: owner = image 1), as dsm_sweep in dsm_grad.hip
-static int closs_sweep(int mode, int side, const ClossCall& c, void* workspace, const float* d_loss, float* d_out,
-                       hipStream_t st) {
-  const DsmSide o = dsm_side(c.p, c.s, side);
+// the tiled sweep of one side (0: owner = image 0, 1: image 1), then the combine of its partials (kGrad) or loss_out (kSums)
+static int closs_sweep(int mode, int side, const DsmCall& c, const DsmProblem& p, const ClossCall& q) {
+  const DsmSide o = dsm_side(p, c.s, side);
   const dim3 grid = dsm_sweep_grid(o);
-  double* loss_part = span_ptr<double>(workspace, c.w.loss_part);
-  auto launch = [&](auto cc, auto mm, auto kk) -> hipError_t {
+  double* loss_part = span_ptr<double>(c.workspace, q.w.loss_part);
+  auto launch = [&](auto cc, auto mm, auto kk) {
     constexpr int CC = decltype(cc)::value, MM = decltype(mm)::value, KK = decltype(kk)::value;
-    constexpr int smem = sweep_lds_bytes(CC, false);
-    static unsigned long long lds_set = 0;      // (one per instantiation of this lambda, that is, per kernel)
-    const hipError_t e = ensure_dynamic_lds(&k_closs_sweep<CC, MM, KK>, smem, &lds_set);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_closs_sweep<CC, MM, KK>), grid, dim3(256), smem, st, o.p.feat0, o.p.feat1, o.p.L, o.p.S, c.p.C,
-                       o.s.ofs_r, o.s.sum_r, o.s.pitch_r, o.s.ofs_c, o.s.sum_c, o.s.pitch_c, o.p.v, o.p.u, c.p.k2, c.lp,
-                       c.p.part, c.p.v, c.p.u, loss_part);
-    return hipSuccess;
+    return launch_sweep<&k_closs_sweep<CC, MM, KK>>(o, sweep_lds_bytes(CC, false), c.st(), q.lp, p.part, p.v, p.u, loss_part);
   };
-  const hipError_t e = with_padded_channels(c.p.C, [&](auto cc) {
-    return with_kind(c.kind, [&](auto kk) {
+  const hipError_t e = with_padded_channels(p.C, [&](auto cc) {
+    return with_kind(q.kind, [&](auto kk) {
       return mode == kSums ? launch(cc, int_c<kSums>{}, kk) : launch(cc, int_c<kGrad>{}, kk);
     });
   });
   if (e != hipSuccess) return (int)e;
-  if (mode != kSums) return (int)launch_sweep_combine(o, grid.z, d_loss, d_out, st);
-  hipLaunchKernelGGL(k_closs_finish, dim3(1), dim3(256), 0, st, (const double*)loss_part, (long)grid.x * grid.y * grid.z,
-                     span_ptr<const float>(workspace, c.w.l_pos), span_ptr<const float>(workspace, c.w.l_neg), c.w.Ke,
-                     c.inv_pos, c.inv_neg, c.pos_weight, c.neg_weight, c.stand_in ? 0 : 1, d_out);
+  if (mode != kSums) return (int)launch_sweep_combine(o, grid.z, c.d_loss, side ? c.d_feat1 : c.d_feat0, c.st());
+  hipLaunchKernelGGL(k_closs_finish, dim3(1), dim3(256), 0, c.st(), (const double*)loss_part, (long)grid.x * grid.y * grid.z,
+                     span_ptr<const float>(c.workspace, q.w.l_pos), span_ptr<const float>(c.workspace, q.w.l_neg), q.w.Ke,
+                     q.inv_pos, q.inv_neg, q.pos_weight, q.neg_weight, q.stand_in ? 0 : 1, c.loss_out);
   return (int)hipGetLastError();
 }
 
@@ -361,25 +315,31 @@ extern "C" int fm_coarse_loss_forward(const float* feat0, const float* feat1, in
                                       const float* sum_c, int pitch_c, int kind, float alpha, float gamma, float pos_weight,
                                       float neg_weight, const int64_t* b_ids, const int64_t* i_ids, const int64_t* j_ids, int K,
                                       void* workspace, size_t workspace_bytes, float* loss_out, void* stream) {
-  if (!loss_out) return FM_E_NULL;
-  hipStream_t st = (hipStream_t)stream;
-  ClossCall c;
-  int r = closs_begin(feat0, feat1, N, L, S, C, temperature, {nm_r, sum_r, pitch_r, nm_c, sum_c, pitch_c}, kind, alpha, gamma,
-                      pos_weight, neg_weight, b_ids, i_ids, j_ids, K, workspace, workspace_bytes, true, st, &c);
+  DsmCall c = {feat0, feat1, N, L, S, C, temperature, {nm_r, sum_r, pitch_r, nm_c, sum_c, pitch_c}, {b_ids, i_ids, j_ids, nullptr, K},
+               nullptr, workspace, workspace_bytes, stream, nullptr, loss_out};
+  c.listed = c.needs_ws = c.is_loss = true; c.loss = {kind, alpha, gamma, pos_weight, neg_weight}; c.missing = !loss_out;
+  int r = dsm_status(c);
   if (r != FM_OK) return r;
-  float* gc = span_ptr<float>(workspace, c.w.gc);
-  LossParams lp_e = c.lp;                     // the listed entries leave the negatives - the stand-in does not
-  if (c.stand_in) lp_e.wn = 0.f;
-  const hipError_t e = with_kind(c.kind, [&](auto kk) {
-    hipLaunchKernelGGL((k_closs_entries<decltype(kk)::value>), dim3((c.w.Ke + 255) / 256), dim3(256), 0, st, feat0, feat1, L, S, C,
-                       c.p.k2, nm_r, sum_r, pitch_r, nm_c, sum_c, pitch_c, c.b_ids, c.i_ids, c.j_ids, c.w.Ke, lp_e,
-                       span_ptr<float>(workspace, c.w.l_pos), span_ptr<float>(workspace, c.w.l_neg), gc);
+  DsmProblem p;
+  r = dsm_begin(c, &p);
+  if (r != FM_OK) return r;
+  ClossCall q = closs_begin(c);
+  if (q.stand_in) r = (int)hipMemsetAsync(span_ptr<char>(workspace, q.w.zero_ids), 0, q.w.zero_ids.bytes, c.st());
+  if (r != FM_OK) return r;
+  float* gc = span_ptr<float>(workspace, q.w.gc);
+  LossParams lp_e = q.lp;                     // the listed entries leave the negatives - the stand-in does not
+  if (q.stand_in) lp_e.wn = 0.f;
+  const hipError_t e = with_kind(q.kind, [&](auto kk) {
+    hipLaunchKernelGGL((k_closs_entries<decltype(kk)::value>), dim3((q.e.K + 255) / 256), dim3(256), 0, c.st(), feat0, feat1, L, S,
+                       C, p.k2, nm_r, sum_r, pitch_r, nm_c, sum_c, pitch_c, q.e.b_ids, q.e.i_ids, q.e.j_ids, q.e.K, lp_e,
+                       span_ptr<float>(workspace, q.w.l_pos), span_ptr<float>(workspace, q.w.l_neg), gc);
     return hipGetLastError();
   });
   if (e != hipSuccess) return (int)e;
-  r = (int)launch_dsm_uv(c.b_ids, c.i_ids, c.j_ids, gc, c.w.Ke, L, S, c.p.v, c.p.u, st);
+  q.e.gc = gc;
+  r = (int)launch_dsm_uv(q.e, L, S, p.v, p.u, c.st());
   if (r != FM_OK) return r;
-  return closs_sweep(kSums, 0, c, workspace, nullptr, loss_out, st);
+  return closs_sweep(kSums, 0, c, p, q);
 }
 
 extern "C" int fm_coarse_loss_backward(const float* feat0, const float* feat1, int N, int L, int S, int C, float temperature,
@@ -388,18 +348,21 @@ extern "C" int fm_coarse_loss_backward(const float* feat0, const float* feat1, i
                                        float neg_weight, const int64_t* b_ids, const int64_t* i_ids, const int64_t* j_ids,
                                        int K, void* workspace, size_t workspace_bytes, const float* d_loss, float* d_feat0,
                                        float* d_feat1, void* stream) {
-  if (!d_loss || !d_feat0 || !d_feat1) return FM_E_NULL;
-  hipStream_t st = (hipStream_t)stream;
-  ClossCall c;
-  int r = closs_begin(feat0, feat1, N, L, S, C, temperature, {nm_r, sum_r, pitch_r, nm_c, sum_c, pitch_c}, kind, alpha, gamma,
-                      pos_weight, neg_weight, b_ids, i_ids, j_ids, K, workspace, workspace_bytes, false, st, &c);
+  DsmCall c = {feat0, feat1, N, L, S, C, temperature, {nm_r, sum_r, pitch_r, nm_c, sum_c, pitch_c}, {b_ids, i_ids, j_ids, nullptr, K},
+               nullptr, workspace, workspace_bytes, stream, nullptr, nullptr, d_loss, d_feat0, d_feat1};
+  c.listed = c.needs_ws = c.is_loss = true; c.loss = {kind, alpha, gamma, pos_weight, neg_weight};
+  c.missing = !d_loss || !d_feat0 || !d_feat1;
+  int r = dsm_status(c);
   if (r != FM_OK) return r;
+  const DsmProblem p = dsm_carve(c);          // (v and u are the forward call's)
+  ClossCall q = closs_begin(c);
   for (int side = 0; side < 2; ++side) {
-    r = closs_sweep(kGrad, side, c, workspace, d_loss, side ? d_feat1 : d_feat0, st);
+    r = closs_sweep(kGrad, side, c, p, q);
     if (r != FM_OK) return r;
   }
-  float* gcs = span_ptr<float>(workspace, c.w.gcs);
-  hipLaunchKernelGGL(k_closs_scale, dim3((c.w.Ke + 255) / 256), dim3(256), 0, st, span_ptr<const float>(workspace, c.w.gc),
-                     c.w.Ke, d_loss, gcs);
-  return (int)launch_dsm_entries(c.p, c.b_ids, c.i_ids, c.j_ids, gcs, c.w.Ke, d_feat0, d_feat1, st);
+  float* gcs = span_ptr<float>(workspace, q.w.gcs);
+  hipLaunchKernelGGL(k_closs_scale, dim3((q.e.K + 255) / 256), dim3(256), 0, c.st(), span_ptr<const float>(workspace, q.w.gc),
+                     q.e.K, d_loss, gcs);
+  q.e.gc = gcs;
+  return (int)launch_dsm_entries(p, q.e, d_feat0, d_feat1, c.st());
 }

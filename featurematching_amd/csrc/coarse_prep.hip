@@ -494,7 +494,7 @@ hipError_t launch_reduce(const CoarseWs& w, char* base, float inv_ct, hipStream_
   const int chunks = (max(w.Lp, w.Sp) + 15) / 16;
   const dim3 grid(chunks, w.N, 2);
   hipLaunchKernelGGL(k_reduce_sums, grid, dim3(256), 0, st, w.rowB.in(base), w.colB.in(base), w.rsum.in(base), w.csum.in(base),
-                     w.Lp, w.Sp, w.splits, w.panels, w.slots, inv_ct * kLog2e, w.nmr.in(base), w.nmc.in(base), w.nmr2.in(base),
+                     w.Lp, w.Sp, w.splits, w.panels, w.slots, k2_of(inv_ct), w.nmr.in(base), w.nmc.in(base), w.nmr2.in(base),
                      w.nmc2.in(base), w.cand.count.in(base), w.cand.idx.in(base), w.cand.x.in(base), w.ccand.count.in(base),
                      w.ccand.idx.in(base), w.ccand.x.in(base), w.cand_b.count.in(base), w.ccand_b.count.in(base),
                      w.dense_cnt.in(base), w.scalars.in(base));

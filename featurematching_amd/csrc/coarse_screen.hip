@@ -522,7 +522,7 @@ static void fill_screen_stats(ScreenArgs& a, const CoarseWs& w, char* base, floa
   a.dense_cnt = w.dense_cnt.in(base); a.scal = w.scalars.in(base);
   a.L = w.L; a.S = w.S; a.Lp = w.Lp; a.Sp = w.Sp;
   a.slots = w.slots; a.allow_dead = allow_dead;
-  a.k = inv_ct * kLog2e; a.lt = log2f(thr); a.inv_ct = inv_ct; a.cpad = (float)w.C;
+  a.k = k2_of(inv_ct); a.lt = log2f(thr); a.inv_ct = inv_ct; a.cpad = (float)w.C;
 }
 
 hipError_t launch_stab(const CoarseWs& w, char* base, float inv_ct, float thr, int allow_dead, hipStream_t st) {

@@ -458,7 +458,7 @@ hipError_t launch_select(const CoarseWs& w, char* base, const CoarseCall& c, flo
   a.scal = w.scalars.in(base);
   a.N = w.N; a.L = w.L; a.S = w.S; a.C = w.C; a.Lp = w.Lp; a.Sp = w.Sp; a.splits = w.splits; a.splits_s = w.splits_s; a.panels = w.panels;
   a.slots = w.slots; a.h0c = c.h0c; a.w0c = c.w0c; a.h1c = c.h1c; a.w1c = c.w1c; a.border = c.border_rm;
-  a.k = inv_ct * kLog2e; a.thr = c.thr; a.scale_px = c.scale_px; a.scale0 = c.scale0; a.scale1 = c.scale1;
+  a.k = k2_of(inv_ct); a.thr = c.thr; a.scale_px = c.scale_px; a.scale0 = c.scale0; a.scale1 = c.scale1;
   a.b_ids = c.b_ids; a.i_ids = c.i_ids; a.j_ids = c.j_ids; a.k0 = c.mkpts0_c; a.k1 = c.mkpts1_c; a.mconf = c.mconf;
   a.cap = c.cap; a.d_count = c.d_count;
   a.cell0 = w.cell0.in(base); a.cell1 = w.cell1.in(base);

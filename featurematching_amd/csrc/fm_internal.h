@@ -237,7 +237,35 @@ hipError_t launch_exact_lists(const CoarseWs& w, char* base, float inv_ct, const
 hipError_t launch_screen(const void* feat0, const void* feat1, int in_dtype, int c_in, const CoarseWs& w, char* base,
                              float inv_ct, float thr, int dense_enabled, int allow_dead, bool defer, hipStream_t st);
 
-// ---- backward of the dual softmax (dsm_grad.hip) and the matrix-free coarse loss on top of it (coarse_loss.hip) ----
+// 1 / (C temperature) scales a dot product into a similarity, k2 = log2(e) / (C temperature) into an exponent of 2.  The
+// ONE definition of both: every launch of the coarse stage and of its training calls must hold the SAME two roundings -
+// the stabilisers are -k2 x_max, and a k2 one ulp away leaves (k2 - k2') x in both exponents: 4.5e-5 of a conf near 1 at
+// |sim| ~ 160 and C = 36 or 100, where kLog2e / (C T) and kLog2e * (1 / (C T)) round differently.
+inline float inv_ct_of(int C, float temperature) { return 1.0f / ((float)C * temperature); }
+inline float k2_of(float inv_ct) { return inv_ct * kLog2e; }
+
+// ---- the coarse training entry points: the dual softmax at entries, its two backwards (dsm_grad.hip), the coarse loss (coarse_loss.hip)
+// the softmax statistics the forward pass kept: -stabiliser*log2e and denominator of every row / column
+struct DsmStats { const float *ofs_r, *sum_r; int pitch_r; const float *ofs_c, *sum_c; int pitch_c; };
+// K listed entries (b, i, j) and, where the call has one, gc[e] = g_e conf_e
+struct DsmEntries { const int64_t *b_ids, *i_ids, *j_ids; const float* gc; int K; };
+struct LossSpec { int kind; float alpha, gamma, pos_weight, neg_weight; };
+// One call of the five entry points as the C ABI takes it (fmatch.h, in its order).  Each of them fills one and hands
+// it on (dsm_status, then dsm_carve / dsm_begin); what an entry point does not have stays NULL / 0.
+struct DsmCall {
+  const float *feat0, *feat1; int N, L, S, C; float temperature;
+  DsmStats s; DsmEntries e;
+  const float* G;                    // the dense dL/dconf [N, L, S]
+  void* workspace; size_t workspace_bytes; void* stream;
+  float *conf, *loss_out; const float* d_loss; float *d_feat0, *d_feat1;
+  // where the entry points differ
+  bool listed, with_gc;              // there is an entry list; it carries gc
+  bool empty_ok;                     // K == 0 is FM_OK before anything is looked at (and the lists before K's sign)
+  bool needs_ws, is_loss; LossSpec loss;     // every call but conf_at has a workspace; the two loss calls
+  bool missing;                      // one of the pointers only this entry point has (its outputs, d_loss) is NULL
+  hipStream_t st() const { return (hipStream_t)stream; }
+};
+
 // Workspace of the backward entry points: v [N][L] row sums and u [N][S] column sums of g conf, one behind the other
 // (sums: the two, zeroed per call) | part, 256-byte aligned: up to 4 (dsm_zsplit) partial gradients [N][max(L, S)][C]
 struct DsmBwdWs { Span v, u, sums, part; size_t total; };
@@ -250,24 +278,31 @@ inline DsmBwdWs dsm_bwd_layout(int N, int L, int S, int C) {
   w.total = w.part.at + w.part.bytes;
   return w;
 }
-// the softmax statistics the forward pass kept: -stabiliser*log2e and denominator of every row / column
-struct DsmStats {
-  const float *ofs_r, *sum_r; int pitch_r;
-  const float *ofs_c, *sum_c; int pitch_c;
-};
-// one backward call: the descriptors, the shape, the temperature terms and the carved workspace
-struct DsmProblem {
-  const float *feat0, *feat1;
-  int N, L, S, C;
-  float k2, inv_ct;
-  float *v, *u, *part;
-};
-// what every backward entry point does after its NULL checks: dsm_carve = the remaining argument checks, then *p;
-// dsm_begin = dsm_carve, then v and u zeroed (the coarse loss's backward takes v and u from its forward call)
-int dsm_carve(const float* feat0, const float* feat1, int N, int L, int S, int C, float temperature, const DsmStats& s,
-              void* workspace, size_t workspace_bytes, DsmProblem* p);
-int dsm_begin(const float* feat0, const float* feat1, int N, int L, int S, int C, float temperature, const DsmStats& s,
-              void* workspace, size_t workspace_bytes, hipStream_t st, DsmProblem* p);
+// Workspace of the coarse loss: the dual softmax backward's | one loss partial (double) per workgroup of the kSums sweep |
+// the ids (0, 0, 0) of the stand-in entry of an empty supervision | per entry l_pos, l_neg, gc and gc * d_loss
+struct ClossWs { DsmBwdWs dsm; Span loss_part, zero_ids, l_pos, l_neg, gc, gcs; int Ke; size_t total; };
+inline ClossWs closs_layout(int N, int L, int S, int C, int K) {
+  ClossWs w;
+  w.dsm = dsm_bwd_layout(N, L, S, C);
+  w.Ke = K > 0 ? K : 1;
+  const size_t per = align256((size_t)w.Ke * 4);
+  w.loss_part = {align256(w.dsm.total), align256((size_t)4 * N * ((L + 31) / 32) * 8)};
+  w.zero_ids = {w.loss_part.at + w.loss_part.bytes, 256};
+  w.l_pos = {w.zero_ids.at + w.zero_ids.bytes, per};
+  w.l_neg = {w.l_pos.at + per, per};
+  w.gc = {w.l_neg.at + per, per};
+  w.gcs = {w.gc.at + per, per};
+  w.total = w.gcs.at + per;
+  return w;
+}
+
+int dsm_status(const DsmCall& c);   // the ONLY copy of the five entry points' argument checks (the table: DESIGN.md 6g)
+// one call past its status: the descriptors, the shape, the temperature terms and the carved workspace
+struct DsmProblem { const float *feat0, *feat1; int N, L, S, C; float k2, inv_ct; float *v, *u, *part; };
+// dsm_carve: a pure function of a call (with a workspace) that passed dsm_status; dsm_begin: the same, and v and u zeroed
+// on the call's stream (the coarse loss's backward takes v and u from its forward call).  Neither checks anything.
+DsmProblem dsm_carve(const DsmCall& c);
+int dsm_begin(const DsmCall& c, DsmProblem* p);
 int dsm_zsplit(int N, int R);      // z slices of a sweep's column range, so that N * ceil(R / 32) * z fills the chip
 // the problem as the owner image of side `side` sees it (0: image 0, 1: image 1): its own descriptors, length, statistics
 // and sums come first; part is shared
@@ -286,11 +321,9 @@ inline hipError_t with_padded_channels(int C, F&& f) {
 }
 // d_out [N][o.p.L][C] = inv_ct (* d_loss[0], if given: on the device) * sum over the Z partials of a gradient sweep
 hipError_t launch_sweep_combine(const DsmSide& o, int Z, const float* d_loss, float* d_out, hipStream_t st);
-// v / u contributions and own term 2 g c of K listed entries (k_dsm_uv, k_dsm_entries), gc[e] = g_e conf_e
-hipError_t launch_dsm_uv(const int64_t* b_ids, const int64_t* i_ids, const int64_t* j_ids, const float* gc, int K, int L, int S,
-                         float* v, float* u, hipStream_t st);
-hipError_t launch_dsm_entries(const DsmProblem& p, const int64_t* b_ids, const int64_t* i_ids, const int64_t* j_ids,
-                              const float* gc, int K, float* d_feat0, float* d_feat1, hipStream_t st);
+// v / u contributions and own term 2 g c of the listed entries (k_dsm_uv, k_dsm_entries)
+hipError_t launch_dsm_uv(const DsmEntries& e, int L, int S, float* v, float* u, hipStream_t st);
+hipError_t launch_dsm_entries(const DsmProblem& p, const DsmEntries& e, float* d_feat0, float* d_feat1, hipStream_t st);
 
 // Raises a kernel's dynamic-LDS limit once per (kernel, device) instead of on every launch: the
 // attribute call costs tens of host microseconds, which an eager (non-graph) caller would pay per step.
@@ -304,6 +337,18 @@ inline hipError_t ensure_dynamic_lds(K kernel, int bytes, unsigned long long* do
   e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
   if (e == hipSuccess) __atomic_fetch_or(done_mask, bit, __ATOMIC_RELEASE);
   return e;
+}
+
+// The launch site of a tiled sweep (fm_sweep_device.h) of one side, for both of its kernels: KERNEL = an instantiation of
+// k_dsm_bwd or k_closs_sweep, smem = its dynamic LDS, tail = the kernel's arguments behind the 14 the two share.
+template <auto KERNEL, typename... Tail>
+inline hipError_t launch_sweep(const DsmSide& o, int smem, hipStream_t st, Tail... tail) {
+  static unsigned long long lds_set = 0;        // (one per instantiation, that is, per kernel)
+  const hipError_t e = ensure_dynamic_lds(KERNEL, smem, &lds_set);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(KERNEL, dsm_sweep_grid(o), dim3(256), smem, st, o.p.feat0, o.p.feat1, o.p.L, o.p.S, o.p.C, o.s.ofs_r,
+                     o.s.sum_r, o.s.pitch_r, o.s.ofs_c, o.s.sum_c, o.s.pitch_c, o.p.v, o.p.u, o.p.k2, tail...);
+  return hipSuccess;
 }
 
 }  // namespace fm

@@ -1,5 +1,6 @@
 // The tiled sweep of the coarse level's training kernels, once: k_dsm_bwd (dsm_grad.hip) and k_closs_sweep
-// (coarse_loss.hip) are instantiations of sweep_tiles below and differ in their policy type alone.
+// (coarse_loss.hip) are instantiations of sweep_tiles below, differ in their policy type alone and are launched from one
+// site, launch_sweep (fm_internal.h).
 //
 // A workgroup of 256 threads owns 32 rows of the "owner" image (X, R rows) and sweeps the z-th share of the other image
 // (Y, T rows) in tiles of 32 descriptors; grid (ceil(R / 32), N, Z).  Per tile it recomputes the 32 x 32 dot products in

@@ -374,49 +374,69 @@ def _i64c(t: torch.Tensor) -> torch.Tensor:
     return t.to(torch.int64).contiguous()
 
 
-def _desc_pair(f0, f1):
-    """(x0, x1, N, L, S, C): both descriptor sets as contiguous float32 and their sizes"""
-    x0, x1 = _f32c(f0, "feat_c0"), _f32c(f1, "feat_c1")
-    n, l, c = x0.shape
-    return x0, x1, n, l, x1.shape[1], c
+def _d_loss(grad: torch.Tensor) -> torch.Tensor:
+    """the upstream gradient of a loss's scalar as its backward call reads it on the device: float32 [1]"""
+    return grad.detach().to(torch.float32).reshape(1).contiguous()
 
 
-def _desc_side(f0, f1, buffers):
-    """what the dual-softmax and coarse-loss calls open with: _desc_pair and the softmax statistics of `buffers`"""
-    return (*_desc_pair(f0, f1), buffers.softmax_stats())
+class _DualSoftmax:
+    """One dual-softmax / coarse-loss call prepared: the descriptors as the kernels read them (float32, contiguous), the
+    callers' element types, shape = (N, L, S, C), the device, and `head`: the 13 leading arguments every entry point of
+    the family takes - descriptors, sizes, temperature, the softmax statistics of `buffers` (asked for on first use)."""
+
+    def __init__(self, feat_c0, feat_c1, temperature, buffers):
+        self.x0, self.x1 = _f32c(feat_c0, "feat_c0"), _f32c(feat_c1, "feat_c1")
+        self.dtypes, self.dev = (feat_c0.dtype, feat_c1.dtype), self.x0.device
+        self.shape = (*self.x0.shape[:2], self.x1.shape[1], self.x0.shape[2])
+        self.temperature, self.buffers = float(temperature), buffers
+
+    @functools.cached_property
+    def head(self):
+        return (_ptr(self.x0), _ptr(self.x1), *self.shape, self.temperature, *self.buffers.softmax_stats())
+
+    ids = staticmethod(lambda *lists: [_i64c(t) for t in lists])        # the id lists as the library reads them
+
+    def workspace(self, query: str, *more):                              # (buffer, aligned address, bytes) of what `query` asks for
+        need = int(getattr(_lib.load(), query)(*self.shape, *more))
+        return (*_aligned_workspace(need, self.dev), need)
+
+    def grads(self):                                                     # (d_feat0, d_feat1), uninitialised
+        return torch.empty_like(self.x0), torch.empty_like(self.x1)
+
+    def run(self, name: str, *args) -> None:                             # `name`(*head, *args, current stream); a status raises
+        _lib.check(getattr(_lib.load(), name)(*self.head, *args, _stream(self.dev)), name)
+
+    def finish(self, d0, d1, *keep):
+        """The gradients in the callers' element types.  The kernels run on the current stream and torch's caching
+        allocator is stream-ordered: a block freed here is reused only by later work on that stream.  d0 still keeps
+        alive what the enqueued kernels read and ANOTHER stream's work could otherwise take over: the float32 descriptors,
+        `buffers` (its workspace holds the statistics) and `keep` - the call's workspace, id lists, gradient inputs."""
+        d0._keep = (self.x0, self.x1, self.buffers, *keep)
+        return d0.to(self.dtypes[0]), d1.to(self.dtypes[1])
 
 
 def _dsm_backward(f0, f1, temperature, buffers, b_ids, i_ids, j_ids, gc):
     """(dL/df0, dL/df1) of sum_e g_e conf_e from gc = g * conf at the entries (fm_dual_softmax_backward): two launches of
     one tiled kernel that recomputes the similarities tile by tile - no [N, L, S] array."""
-    lib = _lib.load()
-    x0, x1, n, l, s, c, stats = _desc_side(f0, f1, buffers)
-    need = int(lib.fm_dual_softmax_backward_workspace_bytes(n, l, s, c))
-    ws, wsp = _aligned_workspace(need, x0.device)
-    d0, d1 = torch.empty_like(x0), torch.empty_like(x1)
-    k = int(b_ids.shape[0])
-    bb, ii, jj, g = _i64c(b_ids), _i64c(i_ids), _i64c(j_ids), _f32c(gc, "gc")
-    _lib.check(lib.fm_dual_softmax_backward(_ptr(x0), _ptr(x1), n, l, s, c, float(temperature), *stats,
-                                            _ptr(bb), _ptr(ii), _ptr(jj), _ptr(g), k,
-                                            wsp, need, _ptr(d0), _ptr(d1), _stream(x0.device)),
-               "fm_dual_softmax_backward")
-    d0._keep = (ws, bb, ii, jj, g, buffers)
-    return d0.to(f0.dtype), d1.to(f1.dtype)
+    p = _DualSoftmax(f0, f1, temperature, buffers)
+    _, (ws, wsp, need) = p.head, p.workspace("fm_dual_softmax_backward_workspace_bytes")      # (statistics first, as ever)
+    d0, d1 = p.grads()
+    bb, ii, jj = p.ids(b_ids, i_ids, j_ids)
+    g = _f32c(gc, "gc")
+    p.run("fm_dual_softmax_backward", _ptr(bb), _ptr(ii), _ptr(jj), _ptr(g), int(bb.shape[0]), wsp, need, _ptr(d0), _ptr(d1))
+    return p.finish(d0, d1, ws, bb, ii, jj, g)
 
 
 class _DualSoftmaxAt(torch.autograd.Function):
     @staticmethod
     def forward(ctx, feat_c0, feat_c1, b_ids, i_ids, j_ids, temperature, buffers):
-        lib = _lib.load()
-        x0, x1, n, l, s, c, stats = _desc_side(feat_c0, feat_c1, buffers)
-        k = int(b_ids.shape[0])
-        bb, ii, jj = _i64c(b_ids), _i64c(i_ids), _i64c(j_ids)
-        conf = torch.empty(k, dtype=torch.float32, device=x0.device)
-        _lib.check(lib.fm_dual_softmax_conf_at(_ptr(x0), _ptr(x1), n, l, s, c, float(temperature), *stats,
-                                               _ptr(bb), _ptr(ii), _ptr(jj), k, _ptr(conf),
-                                               _stream(x0.device)), "fm_dual_softmax_conf_at")
+        p = _DualSoftmax(feat_c0, feat_c1, temperature, buffers)
+        bb, ii, jj = p.ids(b_ids, i_ids, j_ids)
+        k = int(bb.shape[0])
+        conf = torch.empty(k, dtype=torch.float32, device=p.dev)
+        p.run("fm_dual_softmax_conf_at", _ptr(bb), _ptr(ii), _ptr(jj), k, _ptr(conf))
         ctx.save_for_backward(feat_c0, feat_c1, bb, ii, jj, conf)
-        ctx.temperature, ctx.buffers = float(temperature), buffers
+        ctx.temperature, ctx.buffers = p.temperature, buffers
         return conf
 
     @staticmethod
@@ -437,17 +457,12 @@ def dual_softmax_at(feat_c0: torch.Tensor, feat_c1: torch.Tensor, b_ids, i_ids, 
 def _dsm_backward_dense(f0, f1, temperature, buffers, grad):
     """(dL/df0, dL/df1) for a DENSE dL/dconf (fm_dual_softmax_backward_dense): three tiled sweeps that recompute conf from
     exact float32 dot products and the forward call's softmax statistics - no [N, L, S] temporary."""
-    lib = _lib.load()
-    x0, x1, n, l, s, c, stats = _desc_side(f0, f1, buffers)
+    p = _DualSoftmax(f0, f1, temperature, buffers)
     g = _f32c(grad, "grad")
-    need = int(lib.fm_dual_softmax_backward_workspace_bytes(n, l, s, c))
-    ws, wsp = _aligned_workspace(need, x0.device)
-    d0, d1 = torch.empty_like(x0), torch.empty_like(x1)
-    _lib.check(lib.fm_dual_softmax_backward_dense(_ptr(x0), _ptr(x1), n, l, s, c, float(temperature), *stats, _ptr(g),
-                                                  wsp, need, _ptr(d0), _ptr(d1), _stream(x0.device)),
-               "fm_dual_softmax_backward_dense")
-    d0._keep = (ws, g, buffers)
-    return d0.to(f0.dtype), d1.to(f1.dtype)
+    _, (ws, wsp, need) = p.head, p.workspace("fm_dual_softmax_backward_workspace_bytes")      # (statistics first, as ever)
+    d0, d1 = p.grads()
+    p.run("fm_dual_softmax_backward_dense", _ptr(g), wsp, need, _ptr(d0), _ptr(d1))
+    return p.finish(d0, d1, ws, g)
 
 
 def _count_nonzero_bounded(t: torch.Tensor, chunk_elems: int = 1 << 20) -> int:
@@ -535,31 +550,23 @@ class _CoarseLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, feat_c0, feat_c1, bb, ii, jj, buffers, kind, alpha, gamma, pos_weight, neg_weight):
-        lib = _lib.load()
-        x0, x1, n, l, s, c = _desc_pair(feat_c0, feat_c1)
+        p = _DualSoftmax(feat_c0, feat_c1, buffers._temperature, buffers)
         k = int(bb.shape[0])
-        need = int(lib.fm_coarse_loss_workspace_bytes(n, l, s, c, k))
-        ws, wsp = _aligned_workspace(need, x0.device)
-        out = torch.empty(3, dtype=torch.float32, device=x0.device)
+        ws, wsp, need = p.workspace("fm_coarse_loss_workspace_bytes", k)
+        out = torch.empty(3, dtype=torch.float32, device=p.dev)
         ids = (_ptr(bb), _ptr(ii), _ptr(jj)) if k else (None, None, None)
-        problem = (_ptr(x0), _ptr(x1), n, l, s, c, float(buffers._temperature), *buffers.softmax_stats(), kind, float(alpha),
-                   float(gamma), float(pos_weight), float(neg_weight), *ids, k, wsp, need)
-        _lib.check(lib.fm_coarse_loss_forward(*problem, _ptr(out), _stream(x0.device)), "fm_coarse_loss_forward")
-        ctx.problem, ctx.keep = problem, (x0, x1, bb, ii, jj, ws, buffers)
-        ctx.dtypes = (feat_c0.dtype, feat_c1.dtype)
+        ctx.problem = (kind, float(alpha), float(gamma), float(pos_weight), float(neg_weight), *ids, k, wsp, need)
+        p.run("fm_coarse_loss_forward", *ctx.problem, _ptr(out))
+        ctx.call, ctx.keep = p, (bb, ii, jj, ws)
         ctx.mark_non_differentiable(out)
         return out[0].clone(), out
 
     @staticmethod
     def backward(ctx, grad, _):
-        lib = _lib.load()
-        x0, x1 = ctx.keep[0], ctx.keep[1]
-        d_loss = grad.detach().to(torch.float32).reshape(1).contiguous()
-        d0, d1 = torch.empty_like(x0), torch.empty_like(x1)
-        _lib.check(lib.fm_coarse_loss_backward(*ctx.problem, _ptr(d_loss), _ptr(d0), _ptr(d1), _stream(x0.device)),
-                   "fm_coarse_loss_backward")
-        d0._keep = (ctx.keep, d_loss)
-        return (d0.to(ctx.dtypes[0]), d1.to(ctx.dtypes[1])) + (None,) * 9
+        p, d_loss = ctx.call, _d_loss(grad)
+        d0, d1 = p.grads()
+        p.run("fm_coarse_loss_backward", *ctx.problem, _ptr(d_loss), _ptr(d0), _ptr(d1))
+        return p.finish(d0, d1, ctx.keep, d_loss) + (None,) * 9
 
 
 def coarse_loss(feat_c0: torch.Tensor, feat_c1: torch.Tensor, b_ids, i_ids, j_ids, buffers: CoarseBuffers,
@@ -655,7 +662,7 @@ class _FineLoss(torch.autograd.Function):
     def backward(ctx, grad, _):
         lib = _lib.load()
         e0 = ctx.keep[0]
-        d_loss = grad.detach().to(torch.float32).reshape(1).contiguous()
+        d_loss = _d_loss(grad)
         d0, d1 = torch.empty_like(e0), torch.empty_like(e0)
         _lib.check(lib.fm_fine_loss_backward(*ctx.problem, _ptr(d_loss), _ptr(d0), _ptr(d1), _stream(e0.device)),
                    "fm_fine_loss_backward")

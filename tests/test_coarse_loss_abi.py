@@ -49,6 +49,7 @@ def test_argument_checks():
         assert call(ids=None) == FM_E_NULL                         # K > 0 needs the id lists
         assert call(k=-1) == FM_E_SHAPE
         assert call(k=100 * 90 + 1) == FM_E_SHAPE                  # more distinct entries than the matrix has
+        assert call(k=100 * 90 + 1, kind=2) == FM_E_UNSUPPORTED    # ... which is looked at behind the kind
         for bad in (dict(n=0), dict(l=0), dict(s=-3), dict(pitch_r=99), dict(pitch_c=89)):
             assert call(**bad) == FM_E_SHAPE, bad
         for bad in (dict(c=6), dict(c=260), dict(c=0), dict(t=0.0), dict(t=-1.0), dict(kind=2), dict(kind=-1), dict(gamma=0.0),

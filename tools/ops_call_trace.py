@@ -10,7 +10,10 @@ import sys
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ap.add_argument("--all-bits", action="store_true", help="a SHA also for the gradients that depend on the arrival order of "
+                "float atomics (to show that two runs of ONE build differ there)")
 sys.path.insert(0, os.path.abspath(ap.parse_args().root))
+ALL_BITS = ap.parse_args().all_bits
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
@@ -47,7 +50,9 @@ HW, HWF, SCALE = (15, 20), (60, 80), 8.0
 
 def sha(name, *ts):
     for t in ts:
-        print(f"  {name} {tuple(t.shape)} {hashlib.sha256(t.detach().cpu().contiguous().numpy().tobytes()).hexdigest()}")
+        t = t.detach().cpu().contiguous()
+        t = t.view(torch.int16) if t.dtype == torch.bfloat16 else t             # (numpy has no bfloat16: the same bytes)
+        print(f"  {name} {tuple(t.shape)} {hashlib.sha256(t.numpy().tobytes()).hexdigest()}")
 
 
 def lists(tag, d, count=None):
@@ -148,5 +153,41 @@ d_win = torch.randn(b.shape[0], 49, 64, generator=gen).to(DEV)
 for layout in (0, 1):
     sha(f"crop_backward_layout{layout}", ops.gather_windows_backward(d_win, b, i, (2, 64, *HWF), 7, 4, HW[1], HW[0], layout=layout))
 sha("fine_nchw_f16", *ops.fine_match_maps(ff0.half(), ff1.half(), b, i, j, 7, 4, HW[1], HW[1], mix0, mix1, k0, k1, 2.0))
+
+
+def train(tag, fn, a0=f0, a1=f1, bits=True):
+    """fn(leaf0, leaf1) -> scalar, then .backward(); the SHA of the value and of the two gradients where their bits are
+    the same every run (bits=False: the value's alone - the dense row / column sums the gradients are formed from are
+    float atomics in arrival order)"""
+    x0, x1 = (a.detach().clone().requires_grad_(True) for a in (a0, a1))
+    val = fn(x0, x1)
+    val.backward()
+    sha(tag, val)
+    if bits or ALL_BITS:
+        sha(tag + ("" if bits else "_arrival_order"), x0.grad, x1.grad)
+    else:
+        print(f"  {tag} {tuple(x0.grad.shape)} {x0.grad.dtype} {tuple(x1.grad.shape)} {x1.grad.dtype} (no SHA)")
+
+
+# the supervision is the stats=True call's own matches: mutual nearest neighbours, no two share a row or a column, so the
+# sparse routes' float atomics meet no second addend and their outputs are the same bits every run
+print("# training: dual_softmax_at, coarse_loss, attach_conf_matrix_grad, bfloat16, fine_loss - each with .backward()")
+w = torch.linspace(0.5, 1.5, b.shape[0], device=DEV)
+train("dsm_at", lambda x0, x1: (ops.dual_softmax_at(x0, x1, b, i, j, buf) * w).sum())
+train("closs_focal", lambda x0, x1: ops.coarse_loss(x0, x1, b, i, j, buf), bits=False)
+train("closs_xent", lambda x0, x1: ops.coarse_loss(x0, x1, b, i, j, buf, coarse_type="cross_entropy"), bits=False)
+train("closs_focal_sparse", lambda x0, x1: ops.coarse_loss(x0, x1, b, i, j, buf, sparse_spvs=True))
+train("closs_empty", lambda x0, x1: ops.coarse_loss(x0, x1, b[:0], i[:0], j[:0], buf), bits=False)
+cbuf = ops.coarse_match_async(f0, f1, HW, HW, SCALE, conf_matrix=True)
+cbuf.read_count()
+gsel = torch.zeros_like(cbuf.conf_matrix)
+gsel[b, i, j] = w
+train("conf_grad_sparse", lambda x0, x1: (ops.attach_conf_matrix_grad(x0, x1, cbuf.conf_matrix, 0.1, cbuf) * gsel).sum())
+gall = torch.rand(cbuf.conf_matrix.shape, generator=gen).to(DEV)
+train("conf_grad_dense", lambda x0, x1: (ops.attach_conf_matrix_grad(x0, x1, cbuf.conf_matrix, 0.1, cbuf) * gall).sum(), bits=False)
+train("dsm_at_bf16", lambda x0, x1: (ops.dual_softmax_at(x0, x1, b, i, j, buf) * w).sum(), f0.bfloat16(), f1.bfloat16())
+e0, e1 = (torch.randn(b.shape[0], 3, generator=gen).to(DEV) for _ in range(2))
+gt0, gt1 = (torch.randn(b.shape[0], 2, generator=gen).to(DEV) for _ in range(2))
+train("fine_loss", lambda x0, x1: ops.fine_loss(x0, x1, gt0, gt1), e0, e1)
 torch.cuda.synchronize()
 print("# done")

@@ -83,6 +83,10 @@ SIGNATURES = {
     "fm_fine_loss_workspace_bytes": (C.c_size_t, [_i]),
     "fm_fine_loss_forward": (_i, [_p, _p, _i, _p, _p, _i, _p, _p, C.c_size_t, _p, _p]),
     "fm_fine_loss_backward": (_i, [_p, _p, _i, _p, _p, _i, _p, C.c_size_t, _p, _p, _p, _p]),
+    "fm_linear_attention_state_bytes": (C.c_size_t, [_i, _i, _i, _i, _i]),
+    "fm_linear_attention_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i]),
+    "fm_linear_attention_forward": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p, C.c_size_t, _p, _p, _p]),
+    "fm_linear_attention_backward": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p, C.c_size_t, _p, _p, _p, _p]),
     "fm_gather_windows": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p, _p]),
     "fm_gather_windows_dtype": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p, _p]),
     "fm_coarse_cell_maps": (_i, [_p, _i, _i, _i, _i, _i, C.POINTER(_p), C.POINTER(_i), C.POINTER(_p),

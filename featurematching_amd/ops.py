@@ -961,6 +961,76 @@ def gather_windows_grad(feat_f: torch.Tensor, b_ids: torch.Tensor, ids: torch.Te
     return _GatherWindows.apply(feat_f, b_ids, ids, w, stride, w_c, h_c, pad, cells)
 
 
+def linear_attention_supported(q: torch.Tensor, k: torch.Tensor) -> bool:
+    """Whether linear_attention serves q [N,L,H,D] / k [N,S,H,D]: float32 GPU tensors of 8 heads, D = 8 with L, S <= 64
+    (the window route) or D = 32 with any L, S (the long route) - la_route of csrc/linear_attn.hip."""
+    if not (q.is_cuda and k.is_cuda and q.dtype == torch.float32 and k.dtype == torch.float32 and q.dim() == 4
+            and k.dim() == 4):
+        return False
+    n, l, h, d = q.shape
+    s = k.shape[1]
+    if k.shape[0] != n or tuple(k.shape[2:]) != (h, d) or min(n, l, s) < 1 or h != 8:
+        return False
+    return (d == 8 and l <= 64 and s <= 64) or (d == 32 and n <= 65535)
+
+
+def _mask_bytes(mask: Optional[torch.Tensor], rows: int, cols: int, name: str) -> Optional[torch.Tensor]:
+    if mask is None:
+        return None
+    if tuple(mask.shape) != (rows, cols):
+        raise ValueError(f"{name} must be [{rows}, {cols}], got {tuple(mask.shape)}")
+    return (_on_gpu(mask, name) != 0).to(torch.uint8).contiguous()
+
+
+class _LinearAttention(torch.autograd.Function):
+    """fm_linear_attention_forward / fm_linear_attention_backward: q, k, v, the masks and the forward call's state stay
+    on ctx; each call has a workspace of its own."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, q_mask, kv_mask, eps):
+        lib = _lib.load()
+        qc, kc, vc = _f32c(q, "q"), _f32c(k, "k"), _f32c(v, "v")
+        n, l, h, d = qc.shape
+        s, dev = kc.shape[1], qc.device
+        qm, km = _mask_bytes(q_mask, n, l, "q_mask"), _mask_bytes(kv_mask, n, s, "kv_mask")
+        dims = (n, l, s, h, d)
+        state_bytes = int(lib.fm_linear_attention_state_bytes(*dims))
+        need = int(lib.fm_linear_attention_workspace_bytes(*dims))
+        state = torch.empty(state_bytes // 4, dtype=torch.float32, device=dev) if state_bytes else None
+        ws, wsp = _aligned_workspace(need, dev) if need else (None, None)
+        out = torch.empty_like(qc)
+        _lib.check(lib.fm_linear_attention_forward(_ptr(qc), _ptr(kc), _ptr(vc), _ptr(qm), _ptr(km), *dims, float(eps), wsp,
+                                                   need, _ptr(state), _ptr(out), _stream(dev)), "fm_linear_attention_forward")
+        ctx.save_for_backward(qc, kc, vc, qm, km, state)
+        ctx.call = (dims, float(eps), need, (q.dtype, k.dtype, v.dtype))
+        return out.to(q.dtype)
+
+    @staticmethod
+    def backward(ctx, grad):
+        lib = _lib.load()
+        qc, kc, vc, qm, km, state = ctx.saved_tensors
+        dims, eps, need, dtypes = ctx.call
+        dev = qc.device
+        g = _f32c(grad, "grad")
+        ws, wsp = _aligned_workspace(need, dev) if need else (None, None)
+        d_q, d_k, d_v = torch.empty_like(qc), torch.empty_like(kc), torch.empty_like(vc)
+        _lib.check(lib.fm_linear_attention_backward(_ptr(qc), _ptr(kc), _ptr(vc), _ptr(qm), _ptr(km), _ptr(g), _ptr(state),
+                                                    *dims, eps, wsp, need, _ptr(d_q), _ptr(d_k), _ptr(d_v), _stream(dev)),
+                   "fm_linear_attention_backward")
+        return d_q.to(dtypes[0]), d_k.to(dtypes[1]), d_v.to(dtypes[2]), None, None, None
+
+
+def linear_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, q_mask: Optional[torch.Tensor] = None,
+                     kv_mask: Optional[torch.Tensor] = None, eps: float = 1e-6) -> torch.Tensor:
+    """transformer.linear_attention (the reference's LinearAttention, attentions.py:19-46) as a differentiable HIP op:
+    q [N,L,H,D], k / v [N,S,H,D] -> [N,L,H,D]; q_mask [N,L] / kv_mask [N,S] (any dtype, 0 = padded) get no gradient.
+    Forward fm_linear_attention_forward, backward fm_linear_attention_backward, both deterministic.  Shapes that
+    linear_attention_supported refuses raise (FM_E_UNSUPPORTED); so do CPU tensors."""
+    if q.dim() != 4 or k.dim() != 4 or k.shape != v.shape or k.shape[0] != q.shape[0] or k.shape[2:] != q.shape[2:]:
+        raise ValueError(f"q [N,L,H,D] and k, v [N,S,H,D] expected, got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}")
+    return _LinearAttention.apply(q, k, v, q_mask, kv_mask, eps)
+
+
 def fine_match_maps(feat_f0: torch.Tensor, feat_f1: torch.Tensor, b_ids, i_ids, j_ids, w: int, stride: int, w0c: int,
                     w1c: int, mix0: torch.Tensor, mix1: torch.Tensor, mkpts0_c: torch.Tensor, mkpts1_c: torch.Tensor,
                     scale_f: float, pad: int = 2, count: Optional[torch.Tensor] = None,

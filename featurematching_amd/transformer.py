@@ -55,11 +55,13 @@ def full_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, q_mask=Non
 
 class EncoderLayer(nn.Module):
     """x <- x + LN2(MLP([x, LN1(merge(attn(q(x), k(src), v(src))))]))   (transformer.py:34-57); attention = 'linear'
-    (the default) or 'full' (:22)"""
+    (the default) or 'full' (:22).  hip_attention=True sends the 'linear' attention of shapes that
+    ops.linear_attention_supported accepts through ops.linear_attention (HIP forward and backward) instead of the torch
+    function above; every other call is the torch function, as with hip_attention=False."""
 
-    def __init__(self, d_model: int, nhead: int, attention: str = 'linear'):
+    def __init__(self, d_model: int, nhead: int, attention: str = 'linear', hip_attention: bool = False):
         super().__init__()
-        self.attention = attention
+        self.attention, self.hip_attention = attention, hip_attention
         self.nhead, self.dim = nhead, d_model // nhead
         self.q_proj = nn.Linear(d_model, d_model, bias=False)
         self.k_proj = nn.Linear(d_model, d_model, bias=False)
@@ -74,8 +76,12 @@ class EncoderLayer(nn.Module):
         n, l, _ = x.shape
         heads = lambda t: t.view(n, -1, self.nhead, self.dim)
         attn = linear_attention if self.attention == 'linear' else full_attention
-        msg = attn(heads(self.q_proj(x)), heads(self.k_proj(source)), heads(self.v_proj(source)),
-                   q_mask=x_mask, kv_mask=source_mask)
+        q, k, v = heads(self.q_proj(x)), heads(self.k_proj(source)), heads(self.v_proj(source))
+        if self.hip_attention and self.attention == 'linear':
+            from . import ops
+            if ops.linear_attention_supported(q, k):
+                attn = ops.linear_attention
+        msg = attn(q, k, v, q_mask=x_mask, kv_mask=source_mask)
         msg = self.norm1(self.merge(msg.reshape(n, l, -1)))
         msg = self.norm2(self.mlp(torch.cat([x, msg], dim=2)))
         return x + msg
@@ -94,20 +100,25 @@ class LocalFeatureTransformer(nn.Module):
     counts the calls that were redone.
     inference_only=True (default) lets the eval-mode HIP path run even when the layers' own parameters require grad -
     the outputs then carry no graph through the parameters (a warning says so once); False sends such calls through
-    the torch layers, as a fine-tuning run that freezes batch norm with .eval() needs."""
+    the torch layers, as a fine-tuning run that freezes batch norm with .eval() needs.
+    hip_attention=True (default False) gives the torch layers - training mode, inputs that require grad, masks at the
+    fine level - the HIP attention core with its HIP backward (EncoderLayer); the eval-mode kernels are not affected."""
 
     _warned_detached = False
 
-    def __init__(self, config, use_hip: bool = True, check_range: bool = True, inference_only: bool = True):
+    def __init__(self, config, use_hip: bool = True, check_range: bool = True, inference_only: bool = True,
+                 hip_attention: bool = False):
         super().__init__()
         self.use_hip, self.check_range, self.inference_only = use_hip, check_range, inference_only
+        self.hip_attention = hip_attention
         self.range_fallbacks = 0
         self.last_status = None
         self.attention = config.get('attention', 'linear')
         if self.attention not in ('linear', 'full'):
             raise ValueError(f"attention must be 'linear' or 'full' (transformer.py:22), got {self.attention!r}")
         self.d_model, self.layer_names = config['d_model'], list(config['layer_names'])
-        self.layers = nn.ModuleList(EncoderLayer(config['d_model'], config['nhead'], self.attention) for _ in self.layer_names)
+        self.layers = nn.ModuleList(EncoderLayer(config['d_model'], config['nhead'], self.attention, hip_attention)
+                                    for _ in self.layer_names)
         for p in self.parameters():
             if p.dim() > 1:
                 nn.init.xavier_uniform_(p)

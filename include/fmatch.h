@@ -676,6 +676,39 @@ int fm_fine_loss_backward(const float* expec0, const float* expec1, int row_stri
                           int m_max, void* workspace, size_t workspace_bytes, const float* d_loss, float* d_expec0,
                           float* d_expec1, void* stream);
 
+/*
+ * Linear attention with the elu(x) + 1 feature map (the reference's LinearAttention, network/module/attentions.py:19-46)
+ * and its gradient: the attention core of the context layers when they are trained.  q [dev] float32 [N, L, H*D], k / v
+ * [dev] float32 [N, S, H*D], head h in channels [h*D, (h+1)*D), all (and d_out, state) 16-byte aligned; q_mask [dev] [N, L],
+ * kv_mask [dev] [N, S]: one byte per token, 0 = padded (as fm_coarse_transformer_masked takes them), or NULL.  Per sample
+ * and head, phi(x) = x + 1 for x > 0, else exp(x), Q = phi(q) q_mask, K = phi(k) kv_mask, V = v kv_mask:
+ *     out[l] = (Q_l . sum_s K_s V_s^T) / (Q_l . sum_s K_s + eps)
+ * (the reference's division of V by S and multiplication by S afterwards, a float16 precaution, is left out).  float32
+ * arithmetic.  Two routes, chosen from the shape, both with H = 8:
+ *     D = 8,  1 <= L, S <= 64 : one launch per call, one wave per sample; no state, no workspace (both byte queries
+ *                               answer 0 and the two pointers may be NULL).  The fine level: [M, 25 | 49, 64].
+ *     D = 32, L, S >= 1       : three launches per call (N <= 65535).  The coarse level: [N, 4800, 256].
+ *   fm_linear_attention_forward  : out [dev] float32 [N, L, H*D]; `state` [dev] receives
+ *                                  fm_linear_attention_state_bytes bytes (the K V^T and sum K of every sample and head).
+ *   fm_linear_attention_backward : d_q [N, L, H*D], d_k, d_v [N, S, H*D] from d_out [N, L, H*D] and the `state` the
+ *                                  forward call of the same arguments wrote.  Every element is written; the masks get
+ *                                  no gradient.
+ * workspace: fm_linear_attention_workspace_bytes bytes [dev], 256-byte aligned; the same size serves both calls and
+ * nothing is kept in it between them.  Both byte queries answer 0 for a shape no route serves.  No atomics - every
+ * output is the same bits on every run - and no host synchronisation or allocation.  Statuses: FM_E_NULL, FM_E_SHAPE (a
+ * non-positive size), FM_E_UNSUPPORTED ((H, D, L, S) that neither route serves, eps <= 0), FM_E_WORKSPACE (too small /
+ * misaligned), a hipError_t; every check returns before anything is launched.
+ */
+size_t fm_linear_attention_state_bytes(int N, int L, int S, int H, int D);
+size_t fm_linear_attention_workspace_bytes(int N, int L, int S, int H, int D);
+int fm_linear_attention_forward(const float* q, const float* k, const float* v, const unsigned char* q_mask,
+                                const unsigned char* kv_mask, int N, int L, int S, int H, int D, float eps,
+                                void* workspace, size_t workspace_bytes, float* state, float* out, void* stream);
+int fm_linear_attention_backward(const float* q, const float* k, const float* v, const unsigned char* q_mask,
+                                 const unsigned char* kv_mask, const float* d_out, const float* state, int N, int L,
+                                 int S, int H, int D, float eps, void* workspace, size_t workspace_bytes, float* d_q,
+                                 float* d_k, float* d_v, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -87,6 +87,10 @@ SIGNATURES = {
     "fm_linear_attention_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i]),
     "fm_linear_attention_forward": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p, C.c_size_t, _p, _p, _p]),
     "fm_linear_attention_backward": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p, C.c_size_t, _p, _p, _p, _p]),
+    "fm_encoder_tail_state_bytes": (C.c_size_t, [_i, _i]),
+    "fm_encoder_tail_workspace_bytes": (C.c_size_t, [_i, _i]),
+    "fm_encoder_tail_forward": (_i, [_p] * 9 + [_i, _i, _f, _f, _p, C.c_size_t, _p, _p, _p]),
+    "fm_encoder_tail_backward": (_i, [_p] * 11 + [_i, _i, _f, _f, _p, C.c_size_t] + [_p] * 9 + [_p]),
     "fm_gather_windows": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p, _p]),
     "fm_gather_windows_dtype": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p, _p]),
     "fm_coarse_cell_maps": (_i, [_p, _i, _i, _i, _i, _i, C.POINTER(_p), C.POINTER(_i), C.POINTER(_p),

@@ -1031,6 +1031,73 @@ def linear_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, q_mask: 
     return _LinearAttention.apply(q, k, v, q_mask, kv_mask, eps)
 
 
+def encoder_tail_supported(x: torch.Tensor, a: torch.Tensor) -> bool:
+    """Whether encoder_tail serves x, a [..., 64]: float32 GPU tensors of equal shape, 64 channels, at least one token (and
+    at most 2^24) - et_route of csrc/encoder_tail.hip."""
+    if not (x.is_cuda and a.is_cuda and x.dtype == torch.float32 and a.dtype == torch.float32 and x.dim() >= 1):
+        return False
+    return x.shape == a.shape and x.shape[-1] == 64 and 1 <= x.numel() // 64 <= 1 << 24
+
+
+class _EncoderTail(torch.autograd.Function):
+    """fm_encoder_tail_forward / fm_encoder_tail_backward: x, a, the seven parameters and the forward call's state (none
+    on the present route) stay on ctx; each call has a workspace of its own."""
+
+    @staticmethod
+    def forward(ctx, x, a, eps1, eps2, *params):
+        lib = _lib.load()
+        xc, ac = x.reshape(-1, 64).contiguous(), a.reshape(-1, 64).contiguous()
+        pc = [_f32c(p.detach(), "parameter") for p in params]
+        t, dev = xc.shape[0], xc.device
+        state_bytes = int(lib.fm_encoder_tail_state_bytes(t, 64))
+        need = int(lib.fm_encoder_tail_workspace_bytes(t, 64))
+        state = torch.empty(state_bytes // 4, dtype=torch.float32, device=dev) if state_bytes else None
+        ws, wsp = _aligned_workspace(need, dev)
+        y = torch.empty_like(xc)
+        _lib.check(lib.fm_encoder_tail_forward(_ptr(xc), _ptr(ac), *[_ptr(p) for p in pc], t, 64, float(eps1), float(eps2), wsp,
+                                               need, _ptr(state), _ptr(y), _stream(dev)), "fm_encoder_tail_forward")
+        ctx.save_for_backward(xc, ac, state, *pc)
+        ctx.call = (t, float(eps1), float(eps2), need, x.shape)
+        return y.view(x.shape)
+
+    @staticmethod
+    def backward(ctx, grad):
+        lib = _lib.load()
+        xc, ac, state, *pc = ctx.saved_tensors
+        t, eps1, eps2, need, shape = ctx.call
+        dev = xc.device
+        g = _f32c(grad, "grad").reshape(-1, 64).contiguous()
+        ws, wsp = _aligned_workspace(need, dev)
+        d_x, d_a = torch.empty_like(xc), torch.empty_like(ac)
+        # parameter gradients: all seven or none (the kernels then skip that work)
+        d_p = [torch.empty_like(p) for p in pc] if any(ctx.needs_input_grad[4:]) else [None] * 7
+        _lib.check(lib.fm_encoder_tail_backward(_ptr(xc), _ptr(ac), *[_ptr(p) for p in pc], _ptr(g), _ptr(state), t, 64, eps1,
+                                                eps2, wsp, need, _ptr(d_x), _ptr(d_a), *[_ptr(p) for p in d_p],
+                                                _stream(dev)), "fm_encoder_tail_backward")
+        d_p = [d if want else None for d, want in zip(d_p, ctx.needs_input_grad[4:])]
+        return (d_x.view(shape), d_a.view(shape), None, None, *d_p)
+
+
+def encoder_tail(x: torch.Tensor, a: torch.Tensor, merge_w: torch.Tensor, ln1_w: torch.Tensor, ln1_b: torch.Tensor,
+                 mlp0_w: torch.Tensor, mlp2_w: torch.Tensor, ln2_w: torch.Tensor, ln2_b: torch.Tensor, eps1: float = 1e-5,
+                 eps2: float = 1e-5) -> torch.Tensor:
+    """The tail of transformer.EncoderLayer.forward as a differentiable HIP op (float32 on the exact-float32 matrix
+    instructions, forward and backward, both deterministic):
+        n1 = LayerNorm1(a merge_w^T);  y = x + LayerNorm2(relu([x, n1] mlp0_w^T) mlp2_w^T)
+    x (the layer's input), a (the attention's output) [..., 64] -> [..., 64].  The backward recomputes the chain from x and
+    a: only they and the parameters are kept.  Inputs that encoder_tail_supported refuses raise; so do CPU tensors."""
+    _on_gpu(x, "x"), _on_gpu(a, "a")
+    if not encoder_tail_supported(x, a):
+        raise ValueError(f"encoder_tail serves float32 x, a of one shape [..., 64] with at least one token, got "
+                         f"{tuple(x.shape)} {x.dtype}, {tuple(a.shape)} {a.dtype}")
+    params = (merge_w, ln1_w, ln1_b, mlp0_w, mlp2_w, ln2_w, ln2_b)
+    want = ((64, 64), (64,), (64,), (128, 128), (64, 128), (64,), (64,))
+    for p, shape in zip(params, want):
+        if tuple(p.shape) != shape or p.dtype != torch.float32 or not p.is_cuda:
+            raise ValueError(f"encoder_tail parameters are float32 GPU tensors of shapes {want}, got {tuple(p.shape)} {p.dtype}")
+    return _EncoderTail.apply(x, a, eps1, eps2, *params)
+
+
 def fine_match_maps(feat_f0: torch.Tensor, feat_f1: torch.Tensor, b_ids, i_ids, j_ids, w: int, stride: int, w0c: int,
                     w1c: int, mix0: torch.Tensor, mix1: torch.Tensor, mkpts0_c: torch.Tensor, mkpts1_c: torch.Tensor,
                     scale_f: float, pad: int = 2, count: Optional[torch.Tensor] = None,

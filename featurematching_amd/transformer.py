@@ -57,11 +57,15 @@ class EncoderLayer(nn.Module):
     """x <- x + LN2(MLP([x, LN1(merge(attn(q(x), k(src), v(src))))]))   (transformer.py:34-57); attention = 'linear'
     (the default) or 'full' (:22).  hip_attention=True sends the 'linear' attention of shapes that
     ops.linear_attention_supported accepts through ops.linear_attention (HIP forward and backward) instead of the torch
-    function above; every other call is the torch function, as with hip_attention=False."""
+    function above; every other call is the torch function, as with hip_attention=False.  hip_tail=True likewise sends
+    the three lines behind the attention (merge, norm1, mlp, norm2, the residual) through ops.encoder_tail - one fused HIP
+    kernel forward, one backward that recomputes the chain - wherever ops.encoder_tail_supported accepts (float32 GPU
+    tensors, d_model 64; masked calls too: the tail is token-wise); every other call takes the torch lines as they are."""
 
-    def __init__(self, d_model: int, nhead: int, attention: str = 'linear', hip_attention: bool = False):
+    def __init__(self, d_model: int, nhead: int, attention: str = 'linear', hip_attention: bool = False,
+                 hip_tail: bool = False):
         super().__init__()
-        self.attention, self.hip_attention = attention, hip_attention
+        self.attention, self.hip_attention, self.hip_tail = attention, hip_attention, hip_tail
         self.nhead, self.dim = nhead, d_model // nhead
         self.q_proj = nn.Linear(d_model, d_model, bias=False)
         self.k_proj = nn.Linear(d_model, d_model, bias=False)
@@ -82,6 +86,12 @@ class EncoderLayer(nn.Module):
             if ops.linear_attention_supported(q, k):
                 attn = ops.linear_attention
         msg = attn(q, k, v, q_mask=x_mask, kv_mask=source_mask)
+        if self.hip_tail:
+            from . import ops
+            msg = msg.reshape(n, l, -1)
+            if ops.encoder_tail_supported(x, msg):
+                return ops.encoder_tail(x, msg, self.merge.weight, self.norm1.weight, self.norm1.bias, self.mlp[0].weight,
+                                        self.mlp[2].weight, self.norm2.weight, self.norm2.bias, self.norm1.eps, self.norm2.eps)
         msg = self.norm1(self.merge(msg.reshape(n, l, -1)))
         msg = self.norm2(self.mlp(torch.cat([x, msg], dim=2)))
         return x + msg
@@ -102,22 +112,24 @@ class LocalFeatureTransformer(nn.Module):
     the outputs then carry no graph through the parameters (a warning says so once); False sends such calls through
     the torch layers, as a fine-tuning run that freezes batch norm with .eval() needs.
     hip_attention=True (default False) gives the torch layers - training mode, inputs that require grad, masks at the
-    fine level - the HIP attention core with its HIP backward (EncoderLayer); the eval-mode kernels are not affected."""
+    fine level - the HIP attention core with its HIP backward (EncoderLayer); the eval-mode kernels are not affected.
+    hip_tail=True (default False) gives them the fused HIP tail with its HIP backward (EncoderLayer; d_model 64 only)."""
 
     _warned_detached = False
 
     def __init__(self, config, use_hip: bool = True, check_range: bool = True, inference_only: bool = True,
-                 hip_attention: bool = False):
+                 hip_attention: bool = False, hip_tail: bool = False):
         super().__init__()
         self.use_hip, self.check_range, self.inference_only = use_hip, check_range, inference_only
-        self.hip_attention = hip_attention
+        self.hip_attention, self.hip_tail = hip_attention, hip_tail
         self.range_fallbacks = 0
         self.last_status = None
         self.attention = config.get('attention', 'linear')
         if self.attention not in ('linear', 'full'):
             raise ValueError(f"attention must be 'linear' or 'full' (transformer.py:22), got {self.attention!r}")
         self.d_model, self.layer_names = config['d_model'], list(config['layer_names'])
-        self.layers = nn.ModuleList(EncoderLayer(config['d_model'], config['nhead'], self.attention, hip_attention)
+        self.layers = nn.ModuleList(EncoderLayer(config['d_model'], config['nhead'], self.attention, hip_attention,
+                                                 hip_tail)
                                     for _ in self.layer_names)
         for p in self.parameters():
             if p.dim() > 1:

@@ -709,6 +709,41 @@ int fm_linear_attention_backward(const float* q, const float* k, const float* v,
                                  int S, int H, int D, float eps, void* workspace, size_t workspace_bytes, float* d_q,
                                  float* d_k, float* d_v, void* stream);
 
+/*
+ * The tail of an encoder layer of the context transformer (everything behind the attention) and its gradient, fused:
+ * the fine level's training path, d = 64.  x, a [dev] float32 [T, d] (the layer's input and the attention's output, T
+ * tokens, no token needs another); w_merge [d, d], w_mlp0 [2d, 2d], w_mlp2 [d, 2d] (nn.Linear weights, [out, in]);
+ * ln1_w, ln1_b, ln2_w, ln2_b [d]; eps1, eps2 the LayerNorms' eps.  All pointers 16-byte aligned.  Per token:
+ *     n1 = LN1(a w_merge^T)      o = max([x, n1] w_mlp0^T, 0) w_mlp2^T      y = x + LN2(o)
+ * (biased variance).  float32 on the exact-float32 matrix instructions: one rounding per product, no reduced precision.
+ *   fm_encoder_tail_forward  : y [dev] float32 [T, d].  Two launches.
+ *   fm_encoder_tail_backward : d_x, d_a [T, d] and the seven parameter gradients, shaped as their parameters, from d_y
+ *                              [T, d]; the forward chain is recomputed from x and a.  Every element is written.  The
+ *                              seven parameter-gradient pointers are all non-NULL or all NULL; all NULL = d_x and d_a
+ *                              only, and no parameter-gradient work is done.  Three launches (two without).
+ * state: fm_encoder_tail_state_bytes answers 0 - nothing is kept between the calls - and `state` may be NULL.
+ * workspace: fm_encoder_tail_workspace_bytes(T, d) bytes [dev], 256-byte aligned, at most 30 MiB whatever T is (the
+ * weights in the kernels' operand order and one slab of partial parameter gradients per workgroup, at most 256); the same
+ * size serves both calls and nothing is kept in it between them.  Supported: d = 64, 1 <= T <= 2^24 = 16 777 216.  Both
+ * byte queries answer 0 for a shape that is not served.  No [T, d] or [T, 2d] intermediate reaches memory.  No atomics,
+ * grids that depend on T alone: every output is the same bits on every run.  No host synchronisation or allocation.
+ * Statuses, checked in this order before anything is launched: FM_E_NULL (a required pointer; some but not all of the
+ * seven gradient pointers), FM_E_SHAPE (T <= 0 or d <= 0), FM_E_UNSUPPORTED (d != 64, an eps that is not > 0, T > 2^24),
+ * FM_E_WORKSPACE (NULL, too small or misaligned); then a hipError_t.
+ */
+size_t fm_encoder_tail_state_bytes(int T, int d);
+size_t fm_encoder_tail_workspace_bytes(int T, int d);
+int fm_encoder_tail_forward(const float* x, const float* a, const float* w_merge, const float* ln1_w, const float* ln1_b,
+                            const float* w_mlp0, const float* w_mlp2, const float* ln2_w, const float* ln2_b, int T, int d,
+                            float eps1, float eps2, void* workspace, size_t workspace_bytes, float* state, float* y,
+                            void* stream);
+int fm_encoder_tail_backward(const float* x, const float* a, const float* w_merge, const float* ln1_w, const float* ln1_b,
+                             const float* w_mlp0, const float* w_mlp2, const float* ln2_w, const float* ln2_b,
+                             const float* d_y, const float* state, int T, int d, float eps1, float eps2, void* workspace,
+                             size_t workspace_bytes, float* d_x, float* d_a, float* d_w_merge, float* d_ln1_w,
+                             float* d_ln1_b, float* d_w_mlp0, float* d_w_mlp2, float* d_ln2_w, float* d_ln2_b,
+                             void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -79,56 +79,53 @@ CoarseWs coarse_layout(int N, int L, int S, int C, int slots, bool alone) {
   w.splits_s = choose_screen_chunks(N, w.Lp, w.Sp / 32, &w.units_s, alone);
   const size_t rows = (size_t)N * w.Lp, cols = (size_t)N * w.Sp;
   const size_t nblk = (rows * slots + 255) / 256;
-  size_t o = 0;
-  // (r = the next `count` elements of r's type, from a 256-byte boundary on)
-  auto take = [&](auto& r, size_t count) { r.at = o; o = align256(o + r.bytes(count)); };
-  auto since = [&](size_t at) { return Span{at, o - at}; };      // what was taken from `at` on
+  Carver c;      // (every region starts on a 256-byte boundary, and the spans and totals run on to the next one)
   // ---- the common path ----
-  take(w.cand.count, rows);
-  take(w.ccand.count, cols);
-  take(w.cand_b.count, rows);
-  take(w.ccand_b.count, cols);
-  take(w.dense_cnt, N);
-  w.counters[0] = since(w.cand.count.at);
-  take(w.cell0, rows);
-  take(w.cell1, cols);
-  take(w.ties0, kTieCap + 1);
-  take(w.ties1, kTieCap + 1);
-  w.reassign[0] = since(w.cell0.at);
-  take(w.rowmax_u, rows);
-  take(w.colmax_u, cols);
-  take(w.blocktot, nblk);
-  w.reassign[1] = since(w.blocktot.at);
-  take(w.scalars, 1);
+  c.take(w.cand.count, rows);
+  c.take(w.ccand.count, cols);
+  c.take(w.cand_b.count, rows);
+  c.take(w.ccand_b.count, cols);
+  c.take(w.dense_cnt, N);
+  w.counters[0] = c.since(w.cand.count.at, 256);
+  c.take(w.cell0, rows);
+  c.take(w.cell1, cols);
+  c.take(w.ties0, kTieCap + 1);
+  c.take(w.ties1, kTieCap + 1);
+  w.reassign[0] = c.since(w.cell0.at, 256);
+  c.take(w.rowmax_u, rows);
+  c.take(w.colmax_u, cols);
+  c.take(w.blocktot, nblk);
+  w.reassign[1] = c.since(w.blocktot.at, 256);
+  c.take(w.scalars, 1);
   w.reassign[2] = Span{w.scalars.at, sizeof(Scalars::flags)};     // (dense_units stays: the dense kernels read it)
   w.counters[1] = Span{w.scalars.at, sizeof(Scalars)};
-  w.prep_zero = since(w.cand.count.at);
-  take(w.q0, rows * C); take(w.q1, cols * C);
-  take(w.sigimg, (size_t)N * 2);
-  take(w.imgstat, (size_t)N * 8);
-  take(w.l1_0, rows); take(w.l1_1, cols);
-  take(w.bstat0, rows / 32); take(w.bstat1, cols / 32);
-  take(w.emarg, N);
-  take(w.nmr, rows); take(w.nmc, cols);
-  take(w.umax, rows / 32 * (cols / N / 32));
-  take(w.cand.idx, rows * slots); take(w.cand.x, rows * slots);
-  take(w.ccand.idx, cols * slots); take(w.ccand.x, cols * slots);
-  take(w.thr_r, rows); take(w.thr_c, cols);
-  take(w.wmaxb, rows / 32); take(w.cmaxu, cols / 32);
-  take(w.tmin_r, rows / 32); take(w.tmin_c, cols / 32);
-  take(w.umax2, rows / 32 * (cols / N / 32));
-  take(w.upos, rows / 32 * (cols / N / 32));
-  w.common_total = o;
+  w.prep_zero = c.since(w.cand.count.at, 256);
+  c.take(w.q0, rows * C); c.take(w.q1, cols * C);
+  c.take(w.sigimg, (size_t)N * 2);
+  c.take(w.imgstat, (size_t)N * 8);
+  c.take(w.l1_0, rows); c.take(w.l1_1, cols);
+  c.take(w.bstat0, rows / 32); c.take(w.bstat1, cols / 32);
+  c.take(w.emarg, N);
+  c.take(w.nmr, rows); c.take(w.nmc, cols);
+  c.take(w.umax, rows / 32 * (cols / N / 32));
+  c.take(w.cand.idx, rows * slots); c.take(w.cand.x, rows * slots);
+  c.take(w.ccand.idx, cols * slots); c.take(w.ccand.x, cols * slots);
+  c.take(w.thr_r, rows); c.take(w.thr_c, cols);
+  c.take(w.wmaxb, rows / 32); c.take(w.cmaxu, cols / 32);
+  c.take(w.tmin_r, rows / 32); c.take(w.tmin_c, cols / 32);
+  c.take(w.umax2, rows / 32 * (cols / N / 32));
+  c.take(w.upos, rows / 32 * (cols / N / 32));
+  w.common_total = c.pad();
   // ---- FM_MODE_DENSE / FM_MODE_EXACT_SCREENING / conf_matrix ----
-  take(w.hi0, rows * C); take(w.lo0, rows * C);
-  take(w.hi1, cols * C); take(w.lo1, cols * C);
-  take(w.f16inv, N);
-  take(w.rowB, rows * w.splits); take(w.colB, cols * w.panels);
-  take(w.rsum, rows); take(w.csum, cols);
-  take(w.nmr2, rows); take(w.nmc2, cols);
-  take(w.cand_b.idx, rows * slots); take(w.cand_b.x, rows * slots);
-  take(w.ccand_b.idx, cols * slots); take(w.ccand_b.x, cols * slots);
-  w.total = o;
+  c.take(w.hi0, rows * C); c.take(w.lo0, rows * C);
+  c.take(w.hi1, cols * C); c.take(w.lo1, cols * C);
+  c.take(w.f16inv, N);
+  c.take(w.rowB, rows * w.splits); c.take(w.colB, cols * w.panels);
+  c.take(w.rsum, rows); c.take(w.csum, cols);
+  c.take(w.nmr2, rows); c.take(w.nmc2, cols);
+  c.take(w.cand_b.idx, rows * slots); c.take(w.cand_b.x, rows * slots);
+  c.take(w.ccand_b.idx, cols * slots); c.take(w.ccand_b.x, cols * slots);
+  w.total = c.pad();
   return w;
 }
 
@@ -290,7 +287,7 @@ static int coarse_match_impl(const CoarseCall& c, const MapCopyJob* job, bool re
   if (c.mode & ~kKnownModes) return FM_E_UNSUPPORTED;
   const CoarsePlan p = plan_coarse(c.mode, c.conf_matrix != nullptr, c.cand_slots);
   const CoarseWs w = coarse_layout(c.N, c.L, c.S, c.C, c.cand_slots, p.alone);
-  if (c.workspace_bytes < p.workspace_bytes(w) || ((uintptr_t)c.workspace & 255)) return FM_E_WORKSPACE;
+  if (!workspace_ok(c.workspace, c.workspace_bytes, p.workspace_bytes(w))) return FM_E_WORKSPACE;
   char* base = (char*)c.workspace;
   hipStream_t st = (hipStream_t)c.stream;
   const float inv_ct = inv_ct_of(c.C, c.temperature);

@@ -270,7 +270,7 @@ static ClossCall closs_begin(const DsmCall& c) {
   q.inv_neg = n_neg > 0 ? 1.0 / n_neg : 0.0;
   q.kind = l.kind == FM_LOSS_CROSS_ENTROPY ? kCeLoss : (l.gamma == 2.0f ? kFocal2 : kFocalG);
   q.lp = {l.alpha, l.gamma, (float)(q.neg_weight * q.inv_neg), (float)(q.pos_weight * q.inv_pos), 1e-6f, 1.0f - 1e-6f};
-  const int64_t* zeros = span_ptr<const int64_t>(c.workspace, q.w.zero_ids);
+  const int64_t* zeros = q.w.zero_ids.in(c.workspace);
   q.e = q.stand_in ? DsmEntries{zeros, zeros, zeros, nullptr, 1} : DsmEntries{c.e.b_ids, c.e.i_ids, c.e.j_ids, nullptr, K};
   return q;
 }
@@ -284,7 +284,7 @@ static hipError_t with_kind(int kind, F&& f) {
 static int closs_sweep(int mode, int side, const DsmCall& c, const DsmProblem& p, const ClossCall& q) {
   const DsmSide o = dsm_side(p, c.s, side);
   const dim3 grid = dsm_sweep_grid(o);
-  double* loss_part = span_ptr<double>(c.workspace, q.w.loss_part);
+  double* loss_part = q.w.loss_part.in(c.workspace);
   auto launch = [&](auto cc, auto mm, auto kk) {
     constexpr int CC = decltype(cc)::value, MM = decltype(mm)::value, KK = decltype(kk)::value;
     return launch_sweep<&k_closs_sweep<CC, MM, KK>>(o, sweep_lds_bytes(CC, false), c.st(), q.lp, p.part, p.v, p.u, loss_part);
@@ -296,9 +296,9 @@ static int closs_sweep(int mode, int side, const DsmCall& c, const DsmProblem& p
   });
   if (e != hipSuccess) return (int)e;
   if (mode != kSums) return (int)launch_sweep_combine(o, grid.z, c.d_loss, side ? c.d_feat1 : c.d_feat0, c.st());
-  hipLaunchKernelGGL(k_closs_finish, dim3(1), dim3(256), 0, c.st(), (const double*)loss_part, (long)grid.x * grid.y * grid.z,
-                     span_ptr<const float>(c.workspace, q.w.l_pos), span_ptr<const float>(c.workspace, q.w.l_neg), q.w.Ke,
-                     q.inv_pos, q.inv_neg, q.pos_weight, q.neg_weight, q.stand_in ? 0 : 1, c.loss_out);
+  hipLaunchKernelGGL(k_closs_finish, dim3(1), dim3(256), 0, c.st(), loss_part, (long)grid.x * grid.y * grid.z,
+                     q.w.l_pos.in(c.workspace), q.w.l_neg.in(c.workspace), q.w.Ke, q.inv_pos, q.inv_neg, q.pos_weight,
+                     q.neg_weight, q.stand_in ? 0 : 1, c.loss_out);
   return (int)hipGetLastError();
 }
 
@@ -324,15 +324,15 @@ extern "C" int fm_coarse_loss_forward(const float* feat0, const float* feat1, in
   r = dsm_begin(c, &p);
   if (r != FM_OK) return r;
   ClossCall q = closs_begin(c);
-  if (q.stand_in) r = (int)hipMemsetAsync(span_ptr<char>(workspace, q.w.zero_ids), 0, q.w.zero_ids.bytes, c.st());
+  if (q.stand_in) r = (int)hipMemsetAsync(q.w.zeros.in(workspace), 0, q.w.zeros.bytes, c.st());
   if (r != FM_OK) return r;
-  float* gc = span_ptr<float>(workspace, q.w.gc);
+  float* gc = q.w.gc.in(workspace);
   LossParams lp_e = q.lp;                     // the listed entries leave the negatives - the stand-in does not
   if (q.stand_in) lp_e.wn = 0.f;
   const hipError_t e = with_kind(q.kind, [&](auto kk) {
     hipLaunchKernelGGL((k_closs_entries<decltype(kk)::value>), dim3((q.e.K + 255) / 256), dim3(256), 0, c.st(), feat0, feat1, L, S,
                        C, p.k2, nm_r, sum_r, pitch_r, nm_c, sum_c, pitch_c, q.e.b_ids, q.e.i_ids, q.e.j_ids, q.e.K, lp_e,
-                       span_ptr<float>(workspace, q.w.l_pos), span_ptr<float>(workspace, q.w.l_neg), gc);
+                       q.w.l_pos.in(workspace), q.w.l_neg.in(workspace), gc);
     return hipGetLastError();
   });
   if (e != hipSuccess) return (int)e;
@@ -360,9 +360,9 @@ extern "C" int fm_coarse_loss_backward(const float* feat0, const float* feat1, i
     r = closs_sweep(kGrad, side, c, p, q);
     if (r != FM_OK) return r;
   }
-  float* gcs = span_ptr<float>(workspace, q.w.gcs);
-  hipLaunchKernelGGL(k_closs_scale, dim3((q.e.K + 255) / 256), dim3(256), 0, c.st(), span_ptr<const float>(workspace, q.w.gc),
-                     q.e.K, d_loss, gcs);
+  float* gcs = q.w.gcs.in(workspace);
+  hipLaunchKernelGGL(k_closs_scale, dim3((q.e.K + 255) / 256), dim3(256), 0, c.st(), q.w.gc.in(workspace), q.e.K, d_loss,
+                     gcs);
   q.e.gc = gcs;
   return (int)launch_dsm_entries(p, q.e, d_feat0, d_feat1, c.st());
 }

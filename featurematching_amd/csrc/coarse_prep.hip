@@ -386,7 +386,7 @@ static void fill_prep_args(PrepArgs& a, const void* feat0, const void* feat1, in
   a.exact_step = 0;
   a.l1_0 = w.l1_0.in(base); a.l1_1 = w.l1_1.in(base);
   a.bstat0 = w.bstat0.in(base); a.bstat1 = w.bstat1.in(base);
-  a.zero = span_ptr<uint4>(base, w.prep_zero); a.zero_vec = (int)(w.prep_zero.bytes / 16);
+  a.zero = reinterpret_cast<uint4*>(w.prep_zero.in(base)); a.zero_vec = (int)(w.prep_zero.bytes / 16);
   a.L = w.L; a.S = w.S; a.Lp = w.Lp; a.Sp = w.Sp; a.c_in = c_in;
   a.blocks0 = (int)((long)w.N * w.Lp / 32);
   a.dense_cnt = w.dense_cnt.in(base); a.force = 0; a.f16inv = w.f16inv.in(base);

@@ -649,20 +649,20 @@ constexpr int kMaxLayers = 32;
 
 // Workspace of fm_coarse_transformer, float32, [image]: tiles of 32 tokens per sample; part [N * tiles][kKvFloats]
 // (Seg::part) | kv [N][kKvFloats] (Seg::kv) | diag: TfArgs::diag of a FM_DIAG_CTF build, else empty
-struct CtfWs { int tiles[2]; Span part[2], kv[2], diag; size_t total; };
+struct CtfWs { int tiles[2]; Region<float> part[2], kv[2], diag; size_t total; };
 CtfWs ctf_layout(int N, int L, int S) {
   CtfWs w;
   w.tiles[0] = (L + kTok - 1) / kTok;
   w.tiles[1] = (S + kTok - 1) / kTok;
-  size_t o = 0;
-  auto take = [&](size_t floats) { const Span s{o, floats * 4}; o += s.bytes; return s; };
-  for (int i = 0; i < 2; ++i) w.part[i] = take((size_t)N * w.tiles[i] * kKvFloats);
-  for (int i = 0; i < 2; ++i) w.kv[i] = take((size_t)N * kKvFloats);
-  w.diag = take(0);
+  Carver c;      // (float32 throughout: no padding between the regions)
+  for (int i = 0; i < 2; ++i) c.take(w.part[i], (size_t)N * w.tiles[i] * kKvFloats, sizeof(float));
+  for (int i = 0; i < 2; ++i) c.take(w.kv[i], (size_t)N * kKvFloats, sizeof(float));
+  size_t n_diag = 0;
 #ifdef FM_DIAG_CTF
-  w.diag = take((size_t)N * (w.tiles[0] + w.tiles[1]) * 8 * 16);
+  n_diag = (size_t)N * (w.tiles[0] + w.tiles[1]) * 8 * 16;
 #endif
-  w.total = o;
+  c.take(w.diag, n_diag, sizeof(float));
+  w.total = c.o;
   return w;
 }
 
@@ -741,8 +741,7 @@ extern "C" int fm_coarse_transformer_masked(const float* feat0, const float* fea
       return FM_E_UNSUPPORTED;
   }
   const CtfWs ws = ctf_layout(N, L, S);
-  if (workspace_bytes < ws.total || ((uintptr_t)workspace & 15) || ((uintptr_t)packed & 15))
-    return FM_E_WORKSPACE;
+  if (!workspace_ok(workspace, workspace_bytes, ws.total, 16) || ((uintptr_t)packed & 15)) return FM_E_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   static unsigned long long set_kv = 0, set_layer = 0;
   hipError_t e = ensure_dynamic_lds(&k_ctx_kv, kKvLdsBytes, &set_kv);
@@ -758,8 +757,8 @@ extern "C" int fm_coarse_transformer_masked(const float* feat0, const float* fea
 
   const int* const tl = ws.tiles;
   const int len[2] = {L, S};
-  float* const part[2] = {span_ptr<float>(workspace, ws.part[0]), span_ptr<float>(workspace, ws.part[1])};
-  float* const kv[2] = {span_ptr<float>(workspace, ws.kv[0]), span_ptr<float>(workspace, ws.kv[1])};
+  float* const part[2] = {ws.part[0].in(workspace), ws.part[1].in(workspace)};
+  float* const kv[2] = {ws.kv[0].in(workspace), ws.kv[1].in(workspace)};
   const float* cur[2] = {feat0, feat1};
   float* out[2] = {out0, out1};
   const unsigned char* masks[2] = {mask0, mask1};
@@ -770,7 +769,7 @@ extern "C" int fm_coarse_transformer_masked(const float* feat0, const float* fea
     a.N = N;
     a.w = w;
 #ifdef FM_DIAG_CTF
-    a.diag = span_ptr<float>(workspace, ws.diag);
+    a.diag = ws.diag.in(workspace);
 #endif
     // K / V side: the SOURCE tokens
     int tiles_kv = 0;

@@ -219,20 +219,20 @@ int dsm_status(const DsmCall& c) {
   }
   if (!c.needs_ws) return FM_OK;
   const size_t need = c.is_loss ? closs_layout(c.N, c.L, c.S, c.C, c.e.K).total : dsm_bwd_layout(c.N, c.L, c.S, c.C).total;
-  return c.workspace_bytes < need || ((uintptr_t)c.workspace & 255) ? FM_E_WORKSPACE : FM_OK;
+  return workspace_ok(c.workspace, c.workspace_bytes, need) ? FM_OK : FM_E_WORKSPACE;
 }
 
 DsmProblem dsm_carve(const DsmCall& c) {
   const float inv_ct = inv_ct_of(c.C, c.temperature);
   const DsmBwdWs w = dsm_bwd_layout(c.N, c.L, c.S, c.C);
-  return {c.feat0, c.feat1, c.N, c.L, c.S, c.C, k2_of(inv_ct), inv_ct, span_ptr<float>(c.workspace, w.v),
-          span_ptr<float>(c.workspace, w.u), span_ptr<float>(c.workspace, w.part)};
+  return {c.feat0, c.feat1, c.N, c.L, c.S, c.C, k2_of(inv_ct), inv_ct, w.v.in(c.workspace), w.u.in(c.workspace),
+          w.part.in(c.workspace)};
 }
 
 int dsm_begin(const DsmCall& c, DsmProblem* p) {
   *p = dsm_carve(c);
   const Span sums = dsm_bwd_layout(c.N, c.L, c.S, c.C).sums;
-  return (int)hipMemsetAsync(span_ptr<char>(c.workspace, sums), 0, sums.bytes, c.st());
+  return (int)hipMemsetAsync(sums.in(c.workspace), 0, sums.bytes, c.st());
 }
 
 hipError_t launch_sweep_combine(const DsmSide& o, int Z, const float* d_loss, float* d_out, hipStream_t st) {

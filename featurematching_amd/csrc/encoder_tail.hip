@@ -453,12 +453,13 @@ static int et_groups(int T, int chunk) {
   return c < kEtMaxGroups ? c : kEtMaxGroups;
 }
 // Workspace of either call: the fragments | one slab per workgroup of the backward
-struct EtWs { Span frag, part; size_t total; };
+struct EtWs { Region<float> frag, part; size_t total; };
 static EtWs et_layout(int T) {
   EtWs w;
-  w.frag = {0, align256((size_t)kEtFrag * sizeof(float))};
-  w.part = {w.frag.bytes, (size_t)et_groups(T, kEtBwdChunk) * kEtSlab * sizeof(float)};
-  w.total = align256(w.part.at + w.part.bytes);
+  Carver c;
+  c.take(w.frag, kEtFrag);
+  c.take(w.part, (size_t)et_groups(T, kEtBwdChunk) * kEtSlab);
+  w.total = c.pad();
   return w;
 }
 
@@ -481,7 +482,7 @@ static int et_status(const EtCall& c, bool* wgrad) {
   if (given != 0 && given != 7) return FM_E_NULL;
   if (c.T <= 0 || c.d <= 0) return FM_E_SHAPE;
   if (!et_route(c.T, c.d) || !(c.eps1 > 0.f) || !(c.eps2 > 0.f)) return FM_E_UNSUPPORTED;
-  if (!c.workspace || c.workspace_bytes < et_layout(c.T).total || ((uintptr_t)c.workspace & 255)) return FM_E_WORKSPACE;
+  if (!c.workspace || !workspace_ok(c.workspace, c.workspace_bytes, et_layout(c.T).total)) return FM_E_WORKSPACE;
   *wgrad = given == 7;
   return FM_OK;
 }
@@ -492,7 +493,7 @@ static int et_run(const EtCall& c) {
   if (status != FM_OK) return status;
   hipStream_t st = (hipStream_t)c.stream;
   const EtWs w = et_layout(c.T);
-  float* frag = span_ptr<float>(c.workspace, w.frag);
+  float* frag = w.frag.in(c.workspace);
   const int n_frag = c.backward ? kEtFrag : kEtFwdFrag;
   hipLaunchKernelGGL(k_et_pack, dim3(n_frag / 256), dim3(256), 0, st, c.w_merge, c.w_mlp0, c.w_mlp2, n_frag, frag);
   if (!c.backward) {
@@ -504,7 +505,7 @@ static int et_run(const EtCall& c) {
     return (int)hipGetLastError();
   }
   const int groups = et_groups(c.T, kEtBwdChunk);
-  float* part = span_ptr<float>(c.workspace, w.part);
+  float* part = w.part.in(c.workspace);
   if (wgrad) {
     static unsigned long long lds_bwd = 0;
     const hipError_t e = ensure_dynamic_lds(k_et_bwd<true>, kEtBwdLds, &lds_bwd);

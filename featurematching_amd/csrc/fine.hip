@@ -898,14 +898,15 @@ extern "C" int fm_fine_match(const float* win0, const float* win1, int m_max, co
 
 // Scratch of fm_fine_match_maps for NCHW maps: the channels-last copies k_fine_maps reads.  float32 maps: image 1's
 // only (image 0 is read as it is: map[0] is empty).  Half-precision maps: both images' (2-byte elements), image 0's
-// first, image 1's 256-byte aligned.
-struct FineMapsScratch { Span map[2]; size_t total; };
+// first, image 1's 256-byte aligned.  Byte regions: the element type is the call's (launch_channels_last_copy<T>).
+struct FineMapsScratch { Region<char> map[2]; size_t total; };
 static FineMapsScratch fine_maps_layout(int N, int Cf, int Hf0, int Wf0, int Hf1, int Wf1, int map_dtype) {
   const size_t elem = map_dtype == FM_F32 ? 4 : 2;
   FineMapsScratch s;
-  s.map[0] = {0, map_dtype == FM_F32 ? 0 : (size_t)N * Cf * elem * (size_t)Hf0 * Wf0};
-  s.map[1] = {align256(s.map[0].bytes), (size_t)N * Cf * elem * (size_t)Hf1 * Wf1};
-  s.total = s.map[1].at + s.map[1].bytes;
+  Carver c;
+  c.take(s.map[0], map_dtype == FM_F32 ? 0 : (size_t)N * Cf * elem * (size_t)Hf0 * Wf0);
+  c.take(s.map[1], (size_t)N * Cf * elem * (size_t)Hf1 * Wf1);
+  s.total = c.o;
   return s;
 }
 
@@ -939,16 +940,15 @@ extern "C" int fm_fine_match_maps_dtype(const void* feat_f0, const void* feat_f1
   if (status != FM_OK || m_max == 0) return status;
   const bool prepared = layout == FM_LAYOUT_NCHW_PREPARED, nchw = layout != 1;
   hipStream_t st = (hipStream_t)stream;
-  const float* m0 = (const float*)feat_f0;
-  const float* m1 = (const float*)feat_f1;
+  const void *m0 = feat_f0, *m1 = feat_f1;      // the maps k_fine_maps reads
   int grid_cap = kFineGridCap;
 #ifdef FM_TUNE_ENV
   if (const char* e = getenv("FM_FINE_GRID")) grid_cap = atoi(e) > 0 ? atoi(e) / 8 * 8 : kFineGridCap;
 #endif
   if (nchw) {          // NCHW: channels-last copies (coalesced on both sides), element type kept
     const FineMapsScratch sc = fine_maps_layout(N, Cf, Hf0, Wf0, Hf1, Wf1, map_dtype);
-    float* s0 = span_ptr<float>(scratch, sc.map[0]);
-    float* s1 = span_ptr<float>(scratch, sc.map[1]);
+    void* s0 = sc.map[0].in(scratch);
+    void* s1 = sc.map[1].in(scratch);
     if (map_dtype == FM_F32) {     // image 0 is read as it is; image 1's copy may have been made by the coarse call
       if (!prepared) launch_channels_last_copy<float>(feat_f1, s1, N, Hf1, Wf1, grid_cap, st);
     } else {
@@ -963,8 +963,8 @@ extern "C" int fm_fine_match_maps_dtype(const void* feat_f0, const void* feat_f1
     with_map_dtype(map_dtype, [&](auto dt) {
       auto launch = [&](auto nchw0) {
         hipLaunchKernelGGL((k_fine_maps<decltype(w)::value, decltype(nchw0)::value, decltype(dt)::value>), dim3(blocks),
-                           dim3(256), 0, st, m0, m1, Hf0, Wf0, Hf1, Wf1, stride, pad, w0c, w1c, b_ids, i_ids, j_ids, d_count,
-                           m_max, mix0, mix1, mkpts0_c, mkpts1_c, scale_f, out0, out1);
+                           dim3(256), 0, st, (const float*)m0, (const float*)m1, Hf0, Wf0, Hf1, Wf1, stride, pad, w0c, w1c,
+                           b_ids, i_ids, j_ids, d_count, m_max, mix0, mix1, mkpts0_c, mkpts1_c, scale_f, out0, out1);
       };
       // float32 NCHW: image 0 straight from the map; every other form reads two channels-last maps
       if constexpr (decltype(dt)::value == FM_F32) {

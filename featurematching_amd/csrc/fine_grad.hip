@@ -260,9 +260,18 @@ __global__ __launch_bounds__(256) void k_crop_bwd(const float* __restrict__ d_wi
 
 using namespace fm;
 
+// Workspace of fm_fine_match_backward: every match's share of the 2 (WW + 1) mix-weight gradients (k_fine_mix_reduce sums them)
+struct FineBwdWs { Region<float> part; size_t total; };
+static FineBwdWs fine_bwd_layout(int m_max, int WW) {
+  FineBwdWs w;
+  Carver c;
+  c.take(w.part, (size_t)m_max * 2 * (WW + 1));
+  w.total = c.pad();
+  return w;
+}
+
 extern "C" size_t fm_fine_match_backward_workspace_bytes(int m_max, int WW) {
-  if (m_max < 0 || WW <= 0) return 0;
-  return align256((size_t)m_max * 2 * (WW + 1) * sizeof(float));
+  return m_max >= 0 && WW > 0 ? fine_bwd_layout(m_max, WW).total : 0;
 }
 
 extern "C" int fm_fine_match_backward(const float* win0, const float* win1, int m_max, const int32_t* d_count, int WW,
@@ -274,10 +283,10 @@ extern "C" int fm_fine_match_backward(const float* win0, const float* win1, int 
     return FM_E_NULL;
   if (m_max < 0) return FM_E_SHAPE;
   if (Cf != 64 || (WW != 25 && WW != 49)) return FM_E_UNSUPPORTED;
-  if (workspace_bytes < fm_fine_match_backward_workspace_bytes(m_max, WW) || ((uintptr_t)workspace & 255))
-    return FM_E_WORKSPACE;
+  const FineBwdWs ws = fine_bwd_layout(m_max, WW);
+  if (!workspace_ok(workspace, workspace_bytes, ws.total)) return FM_E_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  float* part = (float*)workspace;
+  float* part = ws.part.in(workspace);
   const int blocks = (m_max + 3) / 4;
   with_window(WW == 25 ? 5 : 7, [&](auto w) {
     hipLaunchKernelGGL(k_fine_bwd<decltype(w)::value>, dim3(blocks), dim3(256), 0, st, win0, win1, m_max, d_count, mix0,
@@ -289,15 +298,16 @@ extern "C" int fm_fine_match_backward(const float* win0, const float* win1, int 
 
 // Workspace of fm_gather_windows_backward, the CSR of matches per cell: starts [N cells + 1] | fill cursors [N cells] |
 // match list [m_max], int32, each 256-byte aligned.  counts: where k_csr_count adds up the cells' counts, zeroed per call.
-struct CropBwdWs { Span start, cursor, list, counts; size_t total; };
+struct CropBwdWs { Region<int> start, cursor, list; Span counts; size_t total; };
 static CropBwdWs crop_bwd_layout(int N, int h_c, int w_c, int m_max) {
   const size_t n = (size_t)N * h_c * w_c;
   CropBwdWs w;
-  w.start = {0, (n + 1) * 4};
-  w.cursor = {align256(w.start.bytes), n * 4};
-  w.list = {w.cursor.at + align256(w.cursor.bytes), (size_t)m_max * 4};
-  w.counts = {0, n * 4};
-  w.total = w.list.at + align256(w.list.bytes);
+  Carver c;
+  c.take(w.start, n + 1);
+  w.counts = Span{w.start.at, w.start.bytes(n)};      // the first n of start
+  c.take(w.cursor, n);
+  c.take(w.list, m_max);
+  w.total = c.pad();
   return w;
 }
 
@@ -315,13 +325,13 @@ extern "C" int fm_gather_windows_backward(const float* d_win, const int64_t* b_i
   if (!generic_window_supported(Cf, W, layout)) return FM_E_UNSUPPORTED;
   if ((long)N * h_c * w_c >= (1L << 31) - 1 || (long)N * Hf >= (1L << 31) / ((Wf + 7) / 8)) return FM_E_UNSUPPORTED;
   const CropBwdWs ws = crop_bwd_layout(N, h_c, w_c, m_max);
-  if (workspace_bytes < ws.total || ((uintptr_t)workspace & 255)) return FM_E_WORKSPACE;
+  if (!workspace_ok(workspace, workspace_bytes, ws.total)) return FM_E_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   const int cells = h_c * w_c, n = N * cells;
-  int* start = span_ptr<int>(workspace, ws.start);
-  int* cursor = span_ptr<int>(workspace, ws.cursor);
-  int* list = span_ptr<int>(workspace, ws.list);
-  hipError_t e = hipMemsetAsync(span_ptr<int>(workspace, ws.counts), 0, ws.counts.bytes, st);
+  int* start = ws.start.in(workspace);
+  int* cursor = ws.cursor.in(workspace);
+  int* list = ws.list.in(workspace);
+  hipError_t e = hipMemsetAsync(ws.counts.in(workspace), 0, ws.counts.bytes, st);
   if (e != hipSuccess) return (int)e;
   const int mb = (m_max + 255) / 256, cb = (n + 255) / 256;
   hipLaunchKernelGGL(k_csr_count, dim3(mb), dim3(256), 0, st, b_ids, ids, d_count, m_max, N, cells, start);

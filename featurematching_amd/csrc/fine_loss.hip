@@ -137,16 +137,19 @@ __global__ __launch_bounds__(256) void k_floss_grad(const float* __restrict__ e0
   d_e1[3 * (size_t)m] = o1x; d_e1[3 * (size_t)m + 1] = o1y; d_e1[3 * (size_t)m + 2] = 0.f;
 }
 
-// Workspace: the record (kFlossRec doubles) | 8 doubles per workgroup of k_floss_partial
-struct FlossWs { Span rec, part; int blocks; size_t total; };
+// Workspace: the record (kFlossRec doubles; record: its 256 bytes, zeroed by a forward call without matches) | 8 doubles
+// per workgroup of k_floss_partial
+struct FlossWs { Region<double> rec, part; Span record; int blocks; size_t total; };
 static FlossWs floss_layout(int m_max) {
   FlossWs w;
   w.blocks = (m_max + 255) / 256;
   if (w.blocks > kFlossMaxBlocks) w.blocks = kFlossMaxBlocks;
   if (w.blocks < 1) w.blocks = 1;
-  w.rec = {0, 256};
-  w.part = {256, align256((size_t)w.blocks * 8 * sizeof(double))};
-  w.total = w.part.at + w.part.bytes;
+  Carver c;
+  c.take(w.rec, kFlossRec);
+  w.record = c.since(w.rec.at, 256);
+  c.take(w.part, (size_t)w.blocks * 8);
+  w.total = c.pad();
   return w;
 }
 static_assert(kFlossRec * sizeof(double) <= 256, "the record's span");
@@ -156,7 +159,7 @@ static int floss_check(const float* e0, const float* e1, int stride, const float
   if (!e0 || !e1 || !gt0 || !gt1 || !workspace) return FM_E_NULL;
   if (m_max < 0 || stride < 3) return FM_E_SHAPE;
   *w = floss_layout(m_max);
-  if (workspace_bytes < w->total || ((uintptr_t)workspace & 255)) return FM_E_WORKSPACE;
+  if (!workspace_ok(workspace, workspace_bytes, w->total)) return FM_E_WORKSPACE;
   return FM_OK;
 }
 
@@ -174,13 +177,13 @@ extern "C" int fm_fine_loss_forward(const float* expec0, const float* expec1, in
   const int r = floss_check(expec0, expec1, row_stride, gt0, gt1, m_max, workspace, workspace_bytes, &w);
   if (r != FM_OK) return r;
   hipStream_t st = (hipStream_t)stream;
-  double* rec = span_ptr<double>(workspace, w.rec);
+  double* rec = w.rec.in(workspace);
   if (m_max == 0) {                                // the reference's `return 0.`: zeros, no launch
     hipError_t e = hipMemsetAsync(loss_out, 0, 3 * sizeof(float), st);
-    if (e == hipSuccess) e = hipMemsetAsync(rec, 0, w.rec.bytes, st);
+    if (e == hipSuccess) e = hipMemsetAsync(w.record.in(workspace), 0, w.record.bytes, st);
     return (int)e;
   }
-  double* part = span_ptr<double>(workspace, w.part);
+  double* part = w.part.in(workspace);
   hipLaunchKernelGGL(k_floss_partial, dim3(w.blocks), dim3(256), 0, st, expec0, expec1, row_stride,
                      reinterpret_cast<const float2*>(gt0), reinterpret_cast<const float2*>(gt1), m_max, d_count, part);
   hipLaunchKernelGGL(k_floss_finish, dim3(1), dim3(64), 0, st, (const double*)part, w.blocks, m_max, d_count, rec, loss_out);
@@ -197,6 +200,6 @@ extern "C" int fm_fine_loss_backward(const float* expec0, const float* expec1, i
   if (m_max == 0) return FM_OK;
   hipLaunchKernelGGL(k_floss_grad, dim3((m_max + 255) / 256), dim3(256), 0, (hipStream_t)stream, expec0, expec1, row_stride,
                      reinterpret_cast<const float2*>(gt0), reinterpret_cast<const float2*>(gt1), m_max,
-                     span_ptr<const double>(workspace, w.rec), d_loss, d_expec0, d_expec1);
+                     w.rec.in(workspace), d_loss, d_expec0, d_expec1);
   return (int)hipGetLastError();
 }

@@ -28,9 +28,11 @@ inline int padded_channels(int c) { return c <= 64 ? 64 : (c <= 128 ? 128 : 256)
 inline bool valid_channels(int c) { return c >= 4 && c <= 256 && c % 4 == 0; }
 inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 
-struct Span { size_t at, bytes; };           // bytes [at, at + bytes) of a workspace
-template <typename T>
-inline T* span_ptr(void* base, const Span& s) { return reinterpret_cast<T*>(static_cast<char*>(base) + s.at); }
+// bytes [at, at + bytes) of a workspace: a range that is set as a whole (hipMemsetAsync), whatever arrays lie in it
+struct Span {
+  size_t at, bytes;
+  char* in(void* base) const { return static_cast<char*>(base) + at; }
+};
 // Where a workspace's array of T starts.  in(base) is its pointer: the element type is stated once, where the region is
 // declared, and a launcher that hands it to a kernel argument of another type does not compile.
 template <typename T>
@@ -39,6 +41,20 @@ struct Region {
   T* in(void* base) const { return reinterpret_cast<T*>(static_cast<char*>(base) + at); }
   static size_t bytes(size_t count) { return count * sizeof(T); }
 };
+// Lays a workspace out front to back; `o` is the bytes taken so far.
+struct Carver {
+  size_t o = 0;
+  size_t pad(size_t align = 256) { return o = (o + align - 1) / align * align; }     // on to the next boundary
+  // r = the next `count` elements of r's type, from an `align`-byte boundary on (sizeof(T): packed behind the last one)
+  template <typename T>
+  void take(Region<T>& r, size_t count, size_t align = 256) { r.at = pad(align); o += r.bytes(count); }
+  // what was taken from `at` on; align: through the padding behind the last region
+  Span since(size_t at, size_t align = 1) { return Span{at, pad(align) - at}; }
+};
+// the caller's workspace holds `need` bytes and is aligned (else FM_E_WORKSPACE)
+inline bool workspace_ok(const void* workspace, size_t have, size_t need, size_t align = 256) {
+  return have >= need && ((uintptr_t)workspace & (align - 1)) == 0;
+}
 // one listing of the candidates, per row or per column: how many each holds, then `slots` entries each - the index on
 // the other side and the exact dot product
 struct CandList { Region<int> count, idx; Region<float> x; };
@@ -268,31 +284,37 @@ struct DsmCall {
 
 // Workspace of the backward entry points: v [N][L] row sums and u [N][S] column sums of g conf, one behind the other
 // (sums: the two, zeroed per call) | part, 256-byte aligned: up to 4 (dsm_zsplit) partial gradients [N][max(L, S)][C]
-struct DsmBwdWs { Span v, u, sums, part; size_t total; };
+struct DsmBwdWs { Region<float> v, u, part; Span sums; size_t total; };
 inline DsmBwdWs dsm_bwd_layout(int N, int L, int S, int C) {
   DsmBwdWs w;
-  w.v = {0, (size_t)N * L * 4};
-  w.u = {w.v.bytes, (size_t)N * S * 4};
-  w.sums = {0, w.v.bytes + w.u.bytes};
-  w.part = {align256(w.sums.bytes), (size_t)4 * N * (size_t)(L > S ? L : S) * C * 4};
-  w.total = w.part.at + w.part.bytes;
+  Carver c;
+  c.take(w.v, (size_t)N * L);
+  c.take(w.u, (size_t)N * S, sizeof(float));
+  w.sums = c.since(w.v.at);                   // v and u
+  c.take(w.part, (size_t)4 * N * (size_t)(L > S ? L : S) * C);
+  w.total = c.o;
   return w;
 }
 // Workspace of the coarse loss: the dual softmax backward's | one loss partial (double) per workgroup of the kSums sweep |
-// the ids (0, 0, 0) of the stand-in entry of an empty supervision | per entry l_pos, l_neg, gc and gc * d_loss
-struct ClossWs { DsmBwdWs dsm; Span loss_part, zero_ids, l_pos, l_neg, gc, gcs; int Ke; size_t total; };
+// the id 0 of the stand-in entry (0, 0, 0) of an empty supervision (zeros: its 256 bytes, zeroed when it stands in) |
+// per entry l_pos, l_neg, gc and gc * d_loss
+struct ClossWs {
+  DsmBwdWs dsm; Region<double> loss_part; Region<int64_t> zero_ids; Span zeros; Region<float> l_pos, l_neg, gc, gcs;
+  int Ke; size_t total;
+};
 inline ClossWs closs_layout(int N, int L, int S, int C, int K) {
   ClossWs w;
   w.dsm = dsm_bwd_layout(N, L, S, C);
   w.Ke = K > 0 ? K : 1;
-  const size_t per = align256((size_t)w.Ke * 4);
-  w.loss_part = {align256(w.dsm.total), align256((size_t)4 * N * ((L + 31) / 32) * 8)};
-  w.zero_ids = {w.loss_part.at + w.loss_part.bytes, 256};
-  w.l_pos = {w.zero_ids.at + w.zero_ids.bytes, per};
-  w.l_neg = {w.l_pos.at + per, per};
-  w.gc = {w.l_neg.at + per, per};
-  w.gcs = {w.gc.at + per, per};
-  w.total = w.gcs.at + per;
+  Carver c{w.dsm.total};
+  c.take(w.loss_part, (size_t)4 * N * ((L + 31) / 32));
+  c.take(w.zero_ids, 1);
+  w.zeros = c.since(w.zero_ids.at, 256);
+  c.take(w.l_pos, w.Ke);
+  c.take(w.l_neg, w.Ke);
+  c.take(w.gc, w.Ke);
+  c.take(w.gcs, w.Ke);
+  w.total = c.pad();
   return w;
 }
 

@@ -407,18 +407,18 @@ static int la_groups(int R) {                    // workgroups per sample of a p
   const int u = (R + kLaUnit - 1) / kLaUnit;
   return u < kLaMaxUnits ? u : kLaMaxUnits;
 }
-// Long-route workspace: the forward's partial slabs [N][la_groups(S)] or, in the backward, [N][la_groups(L)] and behind
-// them the folded dA | dKsum [N]
-struct LaWs { int gs, gl; Span part, dstate; size_t total; };
+// Long-route workspace, carved from its start by either call: the forward's partial slabs [N][la_groups(S)]; the
+// backward's [N][la_groups(L)] and, directly behind them, the folded dA | dKsum [N]
+struct LaWs { int gs, gl; Region<float> part, dstate; size_t total; };
 static LaWs la_layout(int N, int L, int S) {
   LaWs w;
   w.gs = la_groups(S);
   w.gl = la_groups(L);
-  const size_t slab = (size_t)kLaSlab * sizeof(float);
-  w.part = {0, (size_t)N * w.gl * slab};
-  w.dstate = {w.part.bytes, (size_t)N * slab};
-  const size_t fwd = (size_t)N * w.gs * slab, bwd = w.dstate.at + w.dstate.bytes;
-  w.total = align256(fwd > bwd ? fwd : bwd);
+  Carver fwd, bwd;
+  fwd.take(w.part, (size_t)N * w.gs * kLaSlab);
+  bwd.take(w.part, (size_t)N * w.gl * kLaSlab);
+  bwd.take(w.dstate, (size_t)N * kLaSlab, sizeof(float));
+  w.total = align256(fwd.o > bwd.o ? fwd.o : bwd.o);
   return w;
 }
 
@@ -441,7 +441,7 @@ static int la_status(const LaCall& c, LaRoute* route) {
   if (r == kLaNone || !(c.eps > 0.f)) return FM_E_UNSUPPORTED;
   if (r == kLaLong) {
     if (!c.workspace || !(c.backward ? (const void*)c.state : (const void*)c.state_out)) return FM_E_NULL;
-    if (c.workspace_bytes < la_layout(c.N, c.L, c.S).total || ((uintptr_t)c.workspace & 255)) return FM_E_WORKSPACE;
+    if (!workspace_ok(c.workspace, c.workspace_bytes, la_layout(c.N, c.L, c.S).total)) return FM_E_WORKSPACE;
   }
   *route = r;
   return FM_OK;
@@ -469,14 +469,14 @@ static int la_run(const LaCall& c) {
     return (int)hipGetLastError();
   }
   const LaWs w = la_layout(c.N, c.L, c.S);
-  float* part = span_ptr<float>(c.workspace, w.part);
+  float* part = w.part.in(c.workspace);
   const dim3 fold(kLaSlab / 32, c.N);
   if (!c.backward) {
     hipLaunchKernelGGL(k_la_kv_part, dim3(w.gs, c.N), dim3(256), 0, st, c.k, c.v, c.kv_mask, c.S, part);
     hipLaunchKernelGGL(k_la_fold, fold, dim3(256), 0, st, (const float*)part, w.gs, c.state_out);
     hipLaunchKernelGGL(k_la_out, dim3(w.gl, c.N), dim3(256), 0, st, c.q, c.q_mask, (const float*)c.state_out, c.L, c.eps, c.out);
   } else {
-    float* dstate = span_ptr<float>(c.workspace, w.dstate);
+    float* dstate = w.dstate.in(c.workspace);
     hipLaunchKernelGGL(k_la_bwd_q, dim3(w.gl, c.N), dim3(256), 0, st, c.q, c.q_mask, c.d_out, c.state, c.L, c.eps, c.d_q, part);
     hipLaunchKernelGGL(k_la_fold, fold, dim3(256), 0, st, (const float*)part, w.gl, dstate);
     hipLaunchKernelGGL(k_la_bwd_kv, dim3(w.gs, c.N), dim3(256), 0, st, c.k, c.v, c.kv_mask, (const float*)dstate, c.S, c.d_k, c.d_v);

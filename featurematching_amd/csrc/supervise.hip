@@ -153,17 +153,18 @@ __global__ __launch_bounds__(256) void k_spv_table0(const int32_t* __restrict__ 
   if (last[i] == t) o.fine_mtx_0[i] = o.fine_kp0[t];
 }
 
-// Workspace: first [S] (unsigned, 0xffffffff = empty) | last [L] (int, -1 = empty) - one region, set to 0xff bytes per call |
-// block_cnt [ceil(S / 1024)]
-struct SpvWs { Span first, last, tables, block_cnt; int nb; size_t total; };
+// Workspace: first [S] (0xffffffff = empty) | last [L] (-1 = empty) - tables: the two and their padding, set to 0xff bytes
+// per call | block_cnt [ceil(S / 1024)]
+struct SpvWs { Region<unsigned> first; Region<int> last, block_cnt; Span tables; int nb; size_t total; };
 static SpvWs spv_layout(int L, int S) {
   SpvWs w;
-  w.first = {0, align256((size_t)S * 4)};
-  w.last = {w.first.bytes, align256((size_t)L * 4)};
-  w.tables = {0, w.first.bytes + w.last.bytes};
+  Carver c;
+  c.take(w.first, S);
+  c.take(w.last, L);
+  w.tables = c.since(w.first.at, 256);
   w.nb = (S + kSpvScanBlock - 1) / kSpvScanBlock;
-  w.block_cnt = {w.tables.bytes, align256((size_t)w.nb * 4)};
-  w.total = w.block_cnt.at + w.block_cnt.bytes;
+  c.take(w.block_cnt, w.nb);
+  w.total = c.pad();
   return w;
 }
 
@@ -192,12 +193,12 @@ extern "C" int fm_supervise_matches(const float* kp0, const float* kp1, int K, i
   const int L = h0c * w0c, S = h1c * w1c;
   if (cap < (K < S ? K : S)) return FM_E_SHAPE;            // every survivor must have a row
   const SpvWs w = spv_layout(L, S);
-  if (workspace_bytes < w.total || ((uintptr_t)workspace & 255)) return FM_E_WORKSPACE;
+  if (!workspace_ok(workspace, workspace_bytes, w.total)) return FM_E_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  unsigned* first = span_ptr<unsigned>(workspace, w.first);
-  int* last = span_ptr<int>(workspace, w.last);
-  int* block_cnt = span_ptr<int>(workspace, w.block_cnt);
-  hipError_t e = hipMemsetAsync(span_ptr<char>(workspace, w.tables), 0xff, w.tables.bytes, st);
+  unsigned* first = w.first.in(workspace);
+  int* last = w.last.in(workspace);
+  int* block_cnt = w.block_cnt.in(workspace);
+  hipError_t e = hipMemsetAsync(w.tables.in(workspace), 0xff, w.tables.bytes, st);
   if (e == hipSuccess) e = hipMemsetAsync(d_count, 0, 2 * sizeof(int32_t), st);
   if (e == hipSuccess) e = hipMemsetAsync(fine_mtx_0, 0, (size_t)L * 8, st);
   if (e == hipSuccess) e = hipMemsetAsync(fine_mtx_1, 0, (size_t)S * 8, st);

@@ -245,6 +245,86 @@ def test_layout_query_is_consistent():
     assert offs[-1] == n.value
 
 
+def _coarse_bytes_mode(lib, *args):
+    n = C.c_size_t(0)
+    assert lib.fm_coarse_workspace_bytes_mode(*args, C.byref(n)) == 0
+    return n.value
+
+
+def _coarse_tf_bytes(lib, *args):
+    n = C.c_size_t(0)
+    assert lib.fm_coarse_tf_workspace_bytes(*args, C.byref(n)) == 0
+    return n.value
+
+
+# (query, arguments, bytes): every workspace's byte query where its layout arithmetic can go wrong - either side of a
+# 256-byte boundary and of each workgroup cap.  A query that refuses its arguments answers 0.
+WORKSPACE_BYTES = [
+    ("fm_dual_softmax_backward_workspace_bytes", (1, 1, 1, 64), 1280),
+    ("fm_dual_softmax_backward_workspace_bytes", (1, 63, 65, 64), 67072),
+    ("fm_dual_softmax_backward_workspace_bytes", (1, 64, 64, 64), 66048),
+    ("fm_dual_softmax_backward_workspace_bytes", (1, 65, 63, 64), 67072),
+    ("fm_coarse_loss_workspace_bytes", (1, 33, 31, 4, 0), 4096),
+    ("fm_coarse_loss_workspace_bytes", (1, 33, 31, 4, 1), 4096),
+    ("fm_coarse_loss_workspace_bytes", (1, 33, 31, 4, 64), 4096),
+    ("fm_coarse_loss_workspace_bytes", (1, 33, 31, 4, 65), 5120),
+    ("fm_supervise_workspace_bytes", (1, 1, 1, 1), 768),
+    ("fm_supervise_workspace_bytes", (1, 1, 32, 32), 4608),
+    ("fm_supervise_workspace_bytes", (1, 1, 1, 1025), 4864),
+    ("fm_supervise_workspace_bytes", (1, 1, 4096, 4096), 67174656),
+    ("fm_supervise_workspace_bytes", (1, 1, 4096, 4097), 0),
+    ("fm_fine_loss_workspace_bytes", (-1,), 0),
+    ("fm_fine_loss_workspace_bytes", (0,), 512),
+    ("fm_fine_loss_workspace_bytes", (1,), 512),
+    ("fm_fine_loss_workspace_bytes", (256,), 512),
+    ("fm_fine_loss_workspace_bytes", (257,), 512),
+    ("fm_fine_loss_workspace_bytes", (65536,), 16640),
+    ("fm_fine_loss_workspace_bytes", (65537,), 16640),
+    ("fm_fine_match_backward_workspace_bytes", (0, 25), 0),
+    ("fm_fine_match_backward_workspace_bytes", (1, 25), 256),
+    ("fm_fine_match_backward_workspace_bytes", (1, 49), 512),
+    ("fm_fine_match_backward_workspace_bytes", (3, 49), 1280),
+    ("fm_gather_windows_backward_workspace_bytes", (1, 1, 1, 0), 512),
+    ("fm_gather_windows_backward_workspace_bytes", (1, 1, 1, 1), 768),
+    ("fm_gather_windows_backward_workspace_bytes", (2, 7, 9, 65), 1536),
+    ("fm_gather_windows_backward_workspace_bytes", (1, 8, 8, 64), 1024),
+    ("fm_linear_attention_state_bytes", (1, 1, 1, 8, 32), 33792),
+    ("fm_linear_attention_workspace_bytes", (1, 1, 1, 8, 32), 67584),
+    ("fm_linear_attention_state_bytes", (2, 33, 8193, 8, 32), 67584),
+    ("fm_linear_attention_workspace_bytes", (2, 33, 8193, 8, 32), 17301504),
+    ("fm_linear_attention_state_bytes", (2, 8193, 33, 8, 32), 67584),
+    ("fm_linear_attention_workspace_bytes", (2, 8193, 33, 8, 32), 17369088),
+    ("fm_linear_attention_state_bytes", (3, 49, 49, 8, 8), 0),
+    ("fm_linear_attention_workspace_bytes", (3, 49, 49, 8, 8), 0),
+    ("fm_encoder_tail_workspace_bytes", (0, 64), 0),
+    ("fm_encoder_tail_workspace_bytes", (1, 64), 345088),
+    ("fm_encoder_tail_workspace_bytes", (128, 64), 345088),
+    ("fm_encoder_tail_workspace_bytes", (129, 64), 460800),
+    ("fm_encoder_tail_workspace_bytes", (32768, 64), 29851648),
+    ("fm_encoder_tail_workspace_bytes", (32769, 64), 29851648),
+    *[("fm_encoder_tail_state_bytes", (t, 64), 0) for t in (0, 1, 128, 129, 32768, 32769)],
+    (_coarse_tf_bytes, (1, 1, 1), 135168),
+    (_coarse_tf_bytes, (2, 32, 33), 337920),
+    (_coarse_tf_bytes, (1, 4800, 4800), 10205184),
+    ("fm_fine_maps_scratch_bytes_dtype", (1, 64, 3, 5, 7, 9, 0, _lib.FM_F32), 16128),
+    ("fm_fine_maps_scratch_bytes_dtype", (1, 64, 3, 5, 7, 9, 0, _lib.FM_F16), 10112),
+    ("fm_fine_maps_scratch_bytes_dtype", (1, 64, 3, 5, 7, 9, 0, _lib.FM_BF16), 10112),
+    ("fm_fine_maps_scratch_bytes_dtype", (1, 64, 3, 5, 7, 9, 1, _lib.FM_F32), 0),
+    (_coarse_bytes_mode, (1, 1, 1, 64, 8, 0, 0), 61952),
+    (_coarse_bytes_mode, (1, 257, 65, 64, 8, 0, 0), 111872),
+    (_coarse_bytes_mode, (1, 257, 65, 64, 8, _lib.FM_MODE_DENSE, 0), 325120),
+    (_coarse_bytes_mode, (1, 257, 65, 64, 8, _lib.FM_MODE_STATS, 1), 325120),
+]
+
+
+@pytest.mark.parametrize("query,args,expected", WORKSPACE_BYTES,
+                         ids=[f"{getattr(q, '__name__', q).lstrip('_')}{a}".replace(" ", "") for q, a, _ in WORKSPACE_BYTES])
+def test_workspace_byte_queries_are_pinned(query, args, expected):
+    lib = _lib.load()
+    got = query(lib, *args) if callable(query) else getattr(lib, query)(*args)
+    assert got == expected
+
+
 def test_ops_refuse_cpu_tensors():
     import torch
     from featurematching_amd import ops

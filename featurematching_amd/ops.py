@@ -1098,6 +1098,90 @@ def encoder_tail(x: torch.Tensor, a: torch.Tensor, merge_w: torch.Tensor, ln1_w:
     return _EncoderTail.apply(x, a, eps1, eps2, *params)
 
 
+def qkv_projection_supported(x: torch.Tensor, source: torch.Tensor) -> bool:
+    """Whether qkv_projection serves x, source: float32 GPU tensors [T, 64] (Tx, Ts independent) or [N, L, 64], [N, S, 64]
+    with the same leading batch dimension, at least one token each (and at most 2^24) - qp_route of csrc/qkv_proj.hip."""
+    for t in (x, source):
+        if not (t.is_cuda and t.dtype == torch.float32 and t.dim() >= 2 and t.shape[-1] == 64):
+            return False
+        if not 1 <= t.numel() // 64 <= 1 << 24:
+            return False
+    return x.dim() == source.dim() and (x.dim() == 2 or x.shape[0] == source.shape[0])
+
+
+def _same_memory(x: torch.Tensor, source: torch.Tensor) -> bool:
+    """source is x, or a view of the same storage with x's offset, shape and strides"""
+    return source is x or (source.untyped_storage().data_ptr() == x.untyped_storage().data_ptr()
+                           and source.storage_offset() == x.storage_offset() and source.shape == x.shape
+                           and source.stride() == x.stride())
+
+
+class _QkvProjection(torch.autograd.Function):
+    """fm_qkv_projection_forward / fm_qkv_projection_backward: x, source (self mode: x alone) and the three weights stay on
+    ctx; each call has a workspace of its own."""
+
+    @staticmethod
+    def forward(ctx, x, source, wq, wk, wv):
+        lib = _lib.load()
+        self_mode = source is None
+        xc = x.reshape(-1, 64).contiguous()
+        sc = xc if self_mode else source.reshape(-1, 64).contiguous()
+        wc = [_f32c(w.detach(), "weight") for w in (wq, wk, wv)]
+        tx, ts, dev = xc.shape[0], sc.shape[0], xc.device
+        need = int(lib.fm_qkv_projection_workspace_bytes(tx, ts, 64))
+        ws, wsp = _aligned_workspace(need, dev)
+        q, k, v = torch.empty_like(xc), torch.empty_like(sc), torch.empty_like(sc)
+        _lib.check(lib.fm_qkv_projection_forward(_ptr(xc), _ptr(sc), *[_ptr(w) for w in wc], tx, ts, 64, wsp, need, _ptr(q),
+                                                 _ptr(k), _ptr(v), _stream(dev)), "fm_qkv_projection_forward")
+        if self_mode:
+            ctx.save_for_backward(xc, *wc)
+        else:
+            ctx.save_for_backward(xc, sc, *wc)
+        s_shape = x.shape if self_mode else source.shape
+        ctx.call = (self_mode, need, x.shape, s_shape)
+        return q.view(x.shape), k.view(s_shape), v.view(s_shape)
+
+    @staticmethod
+    def backward(ctx, gq, gk, gv):
+        lib = _lib.load()
+        self_mode, need, x_shape, s_shape = ctx.call
+        if self_mode:
+            xc, *wc = ctx.saved_tensors
+            sc = xc
+        else:
+            xc, sc, *wc = ctx.saved_tensors
+        tx, ts, dev = xc.shape[0], sc.shape[0], xc.device
+        g = [_f32c(t, "grad").reshape(-1, 64).contiguous() for t in (gq, gk, gv)]
+        ws, wsp = _aligned_workspace(need, dev)
+        d_x = torch.empty_like(xc)
+        d_src = None if self_mode else torch.empty_like(sc)
+        # weight gradients: all three or none (the kernels then skip that work)
+        d_w = [torch.empty_like(w) for w in wc] if any(ctx.needs_input_grad[2:]) else [None] * 3
+        _lib.check(lib.fm_qkv_projection_backward(_ptr(xc), _ptr(sc), *[_ptr(w) for w in wc], *[_ptr(t) for t in g], tx, ts,
+                                                  64, wsp, need, _ptr(d_x), _ptr(d_src), *[_ptr(w) for w in d_w],
+                                                  _stream(dev)), "fm_qkv_projection_backward")
+        d_w = [d if want else None for d, want in zip(d_w, ctx.needs_input_grad[2:])]
+        return (d_x.view(x_shape), None if self_mode else d_src.view(s_shape), *d_w)
+
+
+def qkv_projection(x: torch.Tensor, source: torch.Tensor, wq: torch.Tensor, wk: torch.Tensor, wv: torch.Tensor):
+    """The three projections at the top of transformer.EncoderLayer.forward as one differentiable HIP op (float32 on the
+    exact-float32 matrix instructions, forward and backward, both deterministic):
+        q = x wq^T,  k = source wk^T,  v = source wv^T
+    x, source [T, 64] or [N, L, 64], [N, S, 64] -> (q shaped as x, k and v shaped as source).  Self mode - `source` is x, or the
+    same storage, offset, shape and strides - reads x once per pass, and the whole gradient comes back in x's slot (None in
+    source's).  Only x, source and the weights are kept for the backward.  Inputs that qkv_projection_supported refuses
+    raise; so do CPU tensors."""
+    _on_gpu(x, "x"), _on_gpu(source, "source")
+    if not qkv_projection_supported(x, source):
+        raise ValueError(f"qkv_projection serves float32 x, source [..., 64] of one batch size with at least one token each, "
+                         f"got {tuple(x.shape)} {x.dtype}, {tuple(source.shape)} {source.dtype}")
+    for w in (wq, wk, wv):
+        if tuple(w.shape) != (64, 64) or w.dtype != torch.float32 or not w.is_cuda:
+            raise ValueError(f"qkv_projection weights are float32 GPU tensors [64, 64], got {tuple(w.shape)} {w.dtype}")
+    return _QkvProjection.apply(x, None if _same_memory(x, source) else source, wq, wk, wv)
+
+
 def fine_match_maps(feat_f0: torch.Tensor, feat_f1: torch.Tensor, b_ids, i_ids, j_ids, w: int, stride: int, w0c: int,
                     w1c: int, mix0: torch.Tensor, mix1: torch.Tensor, mkpts0_c: torch.Tensor, mkpts1_c: torch.Tensor,
                     scale_f: float, pad: int = 2, count: Optional[torch.Tensor] = None,

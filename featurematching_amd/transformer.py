@@ -60,12 +60,16 @@ class EncoderLayer(nn.Module):
     function above; every other call is the torch function, as with hip_attention=False.  hip_tail=True likewise sends
     the three lines behind the attention (merge, norm1, mlp, norm2, the residual) through ops.encoder_tail - one fused HIP
     kernel forward, one backward that recomputes the chain - wherever ops.encoder_tail_supported accepts (float32 GPU
-    tensors, d_model 64; masked calls too: the tail is token-wise); every other call takes the torch lines as they are."""
+    tensors, d_model 64; masked calls too: the tail is token-wise); every other call takes the torch lines as they are.
+    hip_proj=True likewise sends the three projections in front of the attention through ops.qkv_projection - one HIP
+    kernel forward, one backward - wherever ops.qkv_projection_supported accepts (x, source); every other call takes the
+    three nn.Linear lines as they are."""
 
     def __init__(self, d_model: int, nhead: int, attention: str = 'linear', hip_attention: bool = False,
-                 hip_tail: bool = False):
+                 hip_tail: bool = False, hip_proj: bool = False):
         super().__init__()
         self.attention, self.hip_attention, self.hip_tail = attention, hip_attention, hip_tail
+        self.hip_proj = hip_proj
         self.nhead, self.dim = nhead, d_model // nhead
         self.q_proj = nn.Linear(d_model, d_model, bias=False)
         self.k_proj = nn.Linear(d_model, d_model, bias=False)
@@ -80,7 +84,14 @@ class EncoderLayer(nn.Module):
         n, l, _ = x.shape
         heads = lambda t: t.view(n, -1, self.nhead, self.dim)
         attn = linear_attention if self.attention == 'linear' else full_attention
-        q, k, v = heads(self.q_proj(x)), heads(self.k_proj(source)), heads(self.v_proj(source))
+        qkv = None
+        if self.hip_proj:
+            from . import ops
+            if ops.qkv_projection_supported(x, source):
+                qkv = ops.qkv_projection(x, source, self.q_proj.weight, self.k_proj.weight, self.v_proj.weight)
+        if qkv is None:
+            qkv = self.q_proj(x), self.k_proj(source), self.v_proj(source)
+        q, k, v = heads(qkv[0]), heads(qkv[1]), heads(qkv[2])
         if self.hip_attention and self.attention == 'linear':
             from . import ops
             if ops.linear_attention_supported(q, k):
@@ -113,15 +124,17 @@ class LocalFeatureTransformer(nn.Module):
     the torch layers, as a fine-tuning run that freezes batch norm with .eval() needs.
     hip_attention=True (default False) gives the torch layers - training mode, inputs that require grad, masks at the
     fine level - the HIP attention core with its HIP backward (EncoderLayer); the eval-mode kernels are not affected.
-    hip_tail=True (default False) gives them the fused HIP tail with its HIP backward (EncoderLayer; d_model 64 only)."""
+    hip_tail=True (default False) gives them the fused HIP tail with its HIP backward (EncoderLayer; d_model 64 only).
+    hip_proj=True (default False) gives them the fused q / k / v projections with their HIP backward (EncoderLayer;
+    d_model 64 only): with all three switches a training-mode fine layer is three HIP ops each way."""
 
     _warned_detached = False
 
     def __init__(self, config, use_hip: bool = True, check_range: bool = True, inference_only: bool = True,
-                 hip_attention: bool = False, hip_tail: bool = False):
+                 hip_attention: bool = False, hip_tail: bool = False, hip_proj: bool = False):
         super().__init__()
         self.use_hip, self.check_range, self.inference_only = use_hip, check_range, inference_only
-        self.hip_attention, self.hip_tail = hip_attention, hip_tail
+        self.hip_attention, self.hip_tail, self.hip_proj = hip_attention, hip_tail, hip_proj
         self.range_fallbacks = 0
         self.last_status = None
         self.attention = config.get('attention', 'linear')
@@ -129,7 +142,7 @@ class LocalFeatureTransformer(nn.Module):
             raise ValueError(f"attention must be 'linear' or 'full' (transformer.py:22), got {self.attention!r}")
         self.d_model, self.layer_names = config['d_model'], list(config['layer_names'])
         self.layers = nn.ModuleList(EncoderLayer(config['d_model'], config['nhead'], self.attention, hip_attention,
-                                                 hip_tail)
+                                                 hip_tail, hip_proj)
                                     for _ in self.layer_names)
         for p in self.parameters():
             if p.dim() > 1:

@@ -744,6 +744,42 @@ int fm_encoder_tail_backward(const float* x, const float* a, const float* w_merg
                              float* d_ln1_b, float* d_w_mlp0, float* d_w_mlp2, float* d_ln2_w, float* d_ln2_b,
                              void* stream);
 
+/*
+ * The q / k / v projections of an encoder layer of the context transformer (the three bias-free linear maps in front of
+ * the attention) and their gradient, fused: the fine level's training path, d = 64.  x [dev] float32 [Tx, d] (the layer's
+ * input), src [dev] float32 [Ts, d] (the tokens it attends to), wq, wk, wv [d, d] (nn.Linear weights, [out, in]).  All
+ * pointers 16-byte aligned.
+ *     q = x wq^T        k = src wk^T        v = src wv^T
+ * float32 on the exact-float32 matrix instructions: one rounding per product, no reduced precision.
+ * Self mode is src == x (the same address; then Ts must equal Tx): x is read once per pass.  Any other src is cross mode,
+ * Tx and Ts independent.  Outputs must not overlap inputs or each other: that is the caller's duty and is not checked.
+ *   fm_qkv_projection_forward  : q [Tx, d], k, v [Ts, d].  Two launches.
+ *   fm_qkv_projection_backward : from gq [Tx, d], gk, gv [Ts, d] (the gradients of q, k, v):
+ *                                  cross mode  d_x [Tx, d] = gq wq,  d_src [Ts, d] = gk wk + gv wv;
+ *                                  self mode   d_x [Tx, d] = gq wq + gk wk + gv wv, one sum in registers; d_src is not
+ *                                              written and may be NULL;
+ *                                  d_wq = sum_t gq^T x,  d_wk = sum_t gk^T src,  d_wv = sum_t gv^T src, each [d, d].
+ *                                Every element is written.  d_wq, d_wk, d_wv are all given or all NULL; all NULL = the
+ *                                data gradients only, and no weight-gradient work is done.  Three launches (two without).
+ * workspace: fm_qkv_projection_workspace_bytes(Tx, Ts, d) bytes [dev], 256-byte aligned, at most 13 MiB whatever the
+ * token counts are (the weights in the kernels' operand order and one slab of partial weight gradients per workgroup, at
+ * most 256); the same size serves both calls and both modes, and nothing is kept in it between calls.  Supported: d = 64,
+ * 1 <= Tx, Ts <= 2^24 = 16 777 216.  The query answers 0 for arguments that the calls refuse.  No atomics, grids that
+ * depend on Tx, Ts and the mode alone: every output is the same bits on every run.  No host synchronisation and no
+ * allocation.
+ * Statuses, checked in this order before anything is launched: FM_E_NULL (a required pointer; some but not all of d_wq,
+ * d_wk, d_wv; d_src in cross mode), FM_E_SHAPE (Tx, Ts or d <= 0; src == x with Ts != Tx), FM_E_UNSUPPORTED (d != 64, a
+ * token count above 2^24), FM_E_WORKSPACE (NULL, too small or misaligned); then a hipError_t.
+ */
+size_t fm_qkv_projection_workspace_bytes(int Tx, int Ts, int d);
+int fm_qkv_projection_forward(const float* x, const float* src, const float* wq, const float* wk, const float* wv, int Tx,
+                              int Ts, int d, void* workspace, size_t workspace_bytes, float* q, float* k, float* v,
+                              void* stream);
+int fm_qkv_projection_backward(const float* x, const float* src, const float* wq, const float* wk, const float* wv,
+                               const float* gq, const float* gk, const float* gv, int Tx, int Ts, int d, void* workspace,
+                               size_t workspace_bytes, float* d_x, float* d_src, float* d_wq, float* d_wk, float* d_wv,
+                               void* stream);
+
 #ifdef __cplusplus
 }
 #endif

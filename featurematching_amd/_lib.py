@@ -94,6 +94,9 @@ SIGNATURES = {
     "fm_qkv_projection_workspace_bytes": (C.c_size_t, [_i, _i, _i]),
     "fm_qkv_projection_forward": (_i, [_p] * 5 + [_i, _i, _i, _p, C.c_size_t] + [_p] * 3 + [_p]),
     "fm_qkv_projection_backward": (_i, [_p] * 8 + [_i, _i, _i, _p, C.c_size_t] + [_p] * 5 + [_p]),
+    "fm_window_merge_workspace_bytes": (C.c_size_t, [_i] * 5),
+    "fm_window_merge_forward": (_i, [_p] + [_i] * 10 + [_p] * 4 + [_i, _p, C.c_size_t, _p, _p]),
+    "fm_window_merge_backward": (_i, [_p] + [_i] * 10 + [_p] * 4 + [_i, _p, _p, C.c_size_t] + [_p] * 3 + [_p]),
     "fm_gather_windows": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p, _p]),
     "fm_gather_windows_dtype": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p, _p]),
     "fm_coarse_cell_maps": (_i, [_p, _i, _i, _i, _i, _i, C.POINTER(_p), C.POINTER(_i), C.POINTER(_p),

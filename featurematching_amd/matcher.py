@@ -64,17 +64,38 @@ class Matcher(nn.Module):
     FineMatching with the reference's `data` dict protocol and sub-module names (network/net.py:24-32,51-92), so
     that a reference state dict addresses the same parameters."""
 
-    def __init__(self, config=None, backbone: nn.Module = None):
+    def __init__(self, config=None, backbone: nn.Module = None, hip_train: bool = True, train_coarse: str = 'stats'):
         super().__init__()
+        if train_coarse not in ('stats', 'matrix'):
+            raise ValueError(f"train_coarse must be 'stats' or 'matrix', got {train_coarse!r}")
         cfg = dict(DEFAULT_CONFIG)
         cfg.update(config or {})
         self.config = cfg
+        self.hip_train, self.train_coarse = hip_train, train_coarse
         self.backbone = backbone or SmallFPN(3, cfg['coarse']['d_model'], cfg['fine']['d_model'])
         self.coarse = LocalFeatureTransformer(cfg['coarse'])
         self.coarse_matching = CoarseMatching(cfg['match_coarse'])
         self.fine_preprocess = FinePreprocess(cfg)
         self.fine = LocalFeatureTransformer(cfg['fine'])
         self.fine_matching = FineMatching(cfg['fine'], window=cfg['fine_window_size'])
+        self.train(self.training)
+
+    def train(self, mode: bool = True):
+        """Training mode switches on what only a training step uses, eval mode switches it off again - an eval-mode call
+        is the same launches whatever `hip_train` is: the HIP training ops of the context layers (hip_attention, hip_tail,
+        hip_proj; d_model 256 keeps the torch tail and projections by itself) and of FinePreprocess (hip_merge) with
+        hip_train, and the coarse stage's training output (loss_stats for train_coarse='stats', conf_matrix for
+        'matrix')."""
+        super().train(mode)
+        on = bool(mode) and self.hip_train
+        for tf in (self.coarse, self.fine):
+            tf.hip_attention = tf.hip_tail = tf.hip_proj = on
+            for layer in tf.layers:
+                layer.hip_attention = layer.hip_tail = layer.hip_proj = on
+        self.fine_preprocess.hip_merge = on
+        self.coarse_matching.loss_stats = bool(mode) and self.train_coarse == 'stats'
+        self.coarse_matching.conf_matrix = bool(mode) and self.train_coarse == 'matrix'
+        return self
 
     def load_state_dict(self, state_dict, *args, **kwargs):
         """network/net.py:94-102: checkpoints of the reference's Lightning module carry a `matcher.` prefix (and older
@@ -91,22 +112,56 @@ class Matcher(nn.Module):
             sd[k] = v
         return super().load_state_dict(sd, *args, **kwargs)
 
-    @torch.no_grad()
     def forward(self, data):
         """network/net.py:40-92; results are written into `data` (returned as well, for convenience: the reference
-        returns None)"""
-        data.update({'bs': data['image0'].size(0),
-                     'hw0_i': data['image0'].shape[2:], 'hw1_i': data['image1'].shape[2:]})
-        feats_c, feats_f = self.backbone(torch.cat([data['image0'], data['image1']], dim=0))
-        (feat_c0, feat_c1), (feat_f0, feat_f1) = feats_c.split(data['bs']), feats_f.split(data['bs'])
-        data.update({'hw0_c': feat_c0.shape[2:], 'hw1_c': feat_c1.shape[2:],
-                     'hw0_f': feat_f0.shape[2:], 'hw1_f': feat_f1.shape[2:]})
-        return self.forward_features(feat_c0, feat_c1, feat_f0, feat_f1, data)
+        returns None).  Eval mode runs under no_grad; training mode runs with grad mode as the caller set it and needs
+        the supervision ids in `data` (forward_features)."""
+        with torch.set_grad_enabled(self.training and torch.is_grad_enabled()):
+            data.update({'bs': data['image0'].size(0),
+                         'hw0_i': data['image0'].shape[2:], 'hw1_i': data['image1'].shape[2:]})
+            if self.training:
+                self._require_supervision(data)
+            feats_c, feats_f = self.backbone(torch.cat([data['image0'], data['image1']], dim=0))
+            (feat_c0, feat_c1), (feat_f0, feat_f1) = feats_c.split(data['bs']), feats_f.split(data['bs'])
+            data.update({'hw0_c': feat_c0.shape[2:], 'hw1_c': feat_c1.shape[2:],
+                         'hw0_f': feat_f0.shape[2:], 'hw1_f': feat_f1.shape[2:]})
+            return self.forward_features(feat_c0, feat_c1, feat_f0, feat_f1, data)
 
-    @torch.no_grad()
+    @staticmethod
+    def _require_supervision(data):
+        missing = [k for k in ('spv_b_ids', 'spv_i_ids', 'spv_j_ids') if k not in data]
+        if missing:
+            raise RuntimeError(f"a training-mode Matcher selects the fine windows by the supervision ids: data lacks {missing} - "
+                               "run supervision.data_preprocess and supervision.compute_supervision_coarse first "
+                               "(Matcher.training_step does)")
+
     def forward_features(self, feat_c0, feat_c1, feat_f0, feat_f1, data):
         """network/net.py:66-92 on the backbone's maps feat_c* [N,C,hc,wc], feat_f* [N,Cf,Hf,Wf]; `data` holds
-        bs, hw0_i, hw1_i."""
+        bs, hw0_i, hw1_i - and in training mode spv_b_ids, spv_i_ids, spv_j_ids (compute_supervision_coarse): the ids
+        that select the fine windows (coarse_matching_new.py:113-116)."""
+        if self.training:
+            self._require_supervision(data)
+            return self._train_features(feat_c0, feat_c1, feat_f0, feat_f1, data)
+        with torch.no_grad():
+            return self._eval_features(feat_c0, feat_c1, feat_f0, feat_f1, data)
+
+    def _train_features(self, feat_c0, feat_c1, feat_f0, feat_f1, data):
+        """the same steps without what only eval mode has: no context tables ahead of the match count, no fused fine
+        kernel and so no range report to read back"""
+        data.update({'hw0_c': feat_c0.shape[2:], 'hw1_c': feat_c1.shape[2:],
+                     'hw0_f': feat_f0.shape[2:], 'hw1_f': feat_f1.shape[2:]})
+        feat_c0 = feat_c0.flatten(2).transpose(1, 2).contiguous()       # n c h w -> n (h w) c
+        feat_c1 = feat_c1.flatten(2).transpose(1, 2).contiguous()
+        feat_c0, feat_c1 = self.coarse(feat_c0, feat_c1)                # :74
+        self.coarse_matching(feat_c0, feat_c1, data)                    # :75
+        win0, win1 = self.fine_preprocess(feat_f0, feat_f1, feat_c0, feat_c1, data)     # :78
+        if win0.size(0) != 0:
+            win0, win1 = self.fine(win0, win1)                          # :79-80
+        self.fine_matching(win0, win1, data)                            # :83
+        data.update({'feat_c0': feat_c0, 'feat_c1': feat_c1, 'feat_f0': feat_f0, 'feat_f1': feat_f1})
+        return data
+
+    def _eval_features(self, feat_c0, feat_c1, feat_f0, feat_f1, data):
         data.update({'hw0_c': feat_c0.shape[2:], 'hw1_c': feat_c1.shape[2:],
                      'hw0_f': feat_f0.shape[2:], 'hw1_f': feat_f1.shape[2:]})
         feat_c0 = feat_c0.flatten(2).transpose(1, 2).contiguous()       # n c h w -> n (h w) c
@@ -127,6 +182,21 @@ class Matcher(nn.Module):
             self.fine_matching(redo[0], redo[1], data)
         data.update({'feat_c0': feat_c0, 'feat_c1': feat_c1, 'feat_f0': feat_f0, 'feat_f1': feat_f1})
         return data
+
+    def training_step(self, data, loss) -> torch.Tensor:
+        """The reference's training step (lightning_new.py:216-230) on one pair: data_preprocess,
+        compute_supervision_coarse, the matcher, compute_supervision_fine and `loss` (modules.Loss), in that order.
+        `data` holds image0, image1 and the correspondences origin_kp0 / origin_kp1 [1, K, 2]; returns data['loss'], ready
+        for backward().  One pair per call, as the supervision."""
+        from . import supervision
+        if not self.training:
+            raise RuntimeError("Matcher.training_step needs training mode: call .train() first")
+        supervision.data_preprocess(data)
+        supervision.compute_supervision_coarse(data, dense_gt=self.train_coarse == 'matrix')
+        self(data)
+        supervision.compute_supervision_fine(data)
+        loss(data)
+        return data['loss']
 
     def match(self, img0: torch.Tensor, img1: torch.Tensor):
         """img0, img1: [N,C,H,W] (or [C,H,W]) float tensors on the GPU, H and W multiples of 8.

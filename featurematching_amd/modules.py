@@ -240,12 +240,15 @@ class Loss(nn.Module):
 
 class FinePreprocess(nn.Module):
     """fused_merge=False keeps crop and context merge apart in eval mode too, cell_ordered=False takes the list-ordered
-    crop kernel (tools that time one variant against the other; both default to the fast path)."""
+    crop kernel (tools that time one variant against the other; both default to the fast path).
+    hip_merge=True: a call that wants a gradient runs crop + context merge as ops.window_merge (HIP forward and backward,
+    once per image; the windows and the [.., 128] concatenation never reach memory) where ops.window_merge_supported
+    holds - float32 GPU maps of 64 channels, W in (5, 7).  Every other call runs the torch lines."""
 
-    def __init__(self, config, fused_merge: bool = True, cell_ordered: bool = True):
+    def __init__(self, config, fused_merge: bool = True, cell_ordered: bool = True, hip_merge: bool = False):
         super().__init__()
         self.config = config
-        self.fused_merge, self.cell_ordered = fused_merge, cell_ordered
+        self.fused_merge, self.cell_ordered, self.hip_merge = fused_merge, cell_ordered, hip_merge
         self.cat_c_feat = config['fine_concat_coarse_feat']
         self.W = config['fine_window_size']
         d_model_c = config['coarse']['d_model']
@@ -270,6 +273,17 @@ class FinePreprocess(nn.Module):
         nchw = feat_f0.is_contiguous() and feat_f1.is_contiguous()
         return self.fused_merge and not self.training and not wants_grad and self.d_model_f == 64 and W in (5, 7) \
             and feat_f0.shape[1] == 64 and (nchw or ops.maps_read_in_place(feat_f0, feat_f1))
+
+    def _hip_merge_ok(self, feat_f0, feat_f1, feat_c0, feat_c1, W) -> bool:
+        """hip_merge serves the calls that want a gradient (the eval-mode fused kernel keeps the rest): float32
+        everywhere, both maps as ops.window_merge_supported asks"""
+        if not (self.hip_merge and self.cat_c_feat and self.d_model_f == 64):
+            return False
+        params = (self.down_proj.weight, self.down_proj.bias, self.merge_feat.weight, self.merge_feat.bias)
+        if not _wants_grad(feat_f0, feat_f1, feat_c0, feat_c1, *params):
+            return False
+        return all(t.is_cuda and t.dtype == torch.float32 for t in (feat_c0, feat_c1) + params) \
+            and ops.window_merge_supported(feat_f0, W) and ops.window_merge_supported(feat_f1, W)
 
     def _merge_constants(self):
         """(packed W_w fragments, E = W_c . down_proj.weight [64, C], e = W_c . down_proj.bias + merge bias),
@@ -339,6 +353,15 @@ class FinePreprocess(nn.Module):
                 else:
                     win0 = ops.gather_merge_windows(feat_f0, packed, ctx0, b_ids, i_ids, W, stride, hw0_c[0], hw0_c[1])
                     win1 = ops.gather_merge_windows(feat_f1, packed, ctx1, b_ids, j_ids, W, stride, hw1_c[0], hw1_c[1])
+            return win0, win1
+        if self._hip_merge_ok(feat_f0, feat_f1, feat_c0, feat_c1, W):
+            half = self.d_model_f
+            w_win = self.merge_feat.weight[:, :half]
+            rows = []
+            for feat_c, ids in ((feat_c0, i_ids), (feat_c1, j_ids)):     # the position-independent half, a row per match
+                rows.append(F.linear(self.down_proj(feat_c[b_ids, ids]), self.merge_feat.weight[:, half:], self.merge_feat.bias))
+            win0 = ops.window_merge(feat_f0, w_win, rows[0], b_ids, i_ids, W, stride, hw0_c[0], hw0_c[1])
+            win1 = ops.window_merge(feat_f1, w_win, rows[1], b_ids, j_ids, W, stride, hw1_c[0], hw1_c[1])
             return win0, win1
         if _wants_grad(feat_f0, feat_f1, training=self.training):
             # the crop with its HIP backward (fm_gather_windows_backward): the fine loss reaches the fine maps

@@ -1182,6 +1182,80 @@ def qkv_projection(x: torch.Tensor, source: torch.Tensor, wq: torch.Tensor, wk: 
     return _QkvProjection.apply(x, None if _same_memory(x, source) else source, wq, wk, wv)
 
 
+def window_merge_supported(feat_f: torch.Tensor, w: int) -> bool:
+    """Whether window_merge serves the fine map feat_f at window size w: a float32 GPU map [N, 64, Hf, Wf] stored
+    NCHW-contiguous or channels-last, w in (5, 7) - wm_status of csrc/window_merge.hip."""
+    return feat_f.is_cuda and feat_f.dtype == torch.float32 and feat_f.dim() == 4 and feat_f.shape[1] == 64 \
+        and w in (5, 7) and _stored_layout(feat_f) is not None
+
+
+class _WindowMerge(torch.autograd.Function):
+    """fm_window_merge_forward / fm_window_merge_backward: the map, the ids, w_win and ctx_rows stay on ctx (no window,
+    no concatenation); each call has a workspace of its own."""
+
+    @staticmethod
+    def forward(ctx, feat_f, w_win, ctx_rows, b_ids, ids, w, stride, h_c, w_c, pad):
+        lib = _lib.load()
+        layout = _stored_layout(feat_f)
+        n, _, hf, wf = feat_f.shape
+        dev, m_max = feat_f.device, int(b_ids.shape[0])
+        wc, cc = _f32c(w_win.detach(), "w_win"), _f32c(ctx_rows.detach(), "ctx_rows")
+        bb, ii = _i64c(b_ids), _i64c(ids)
+        geom = (n, 64, hf, wf, layout, w, stride, pad, int(h_c), int(w_c))
+        need = int(lib.fm_window_merge_workspace_bytes(n, int(h_c), int(w_c), m_max, w))
+        ws, wsp = _aligned_workspace(need, dev)
+        out = torch.empty(m_max, w * w, 64, dtype=torch.float32, device=dev)
+        _lib.check(lib.fm_window_merge_forward(_ptr(feat_f), *geom, _ptr(wc), _ptr(cc), _ptr(bb), _ptr(ii), m_max, wsp, need,
+                                               _ptr(out), _stream(dev)), "fm_window_merge_forward")
+        ctx.save_for_backward(feat_f, wc, cc, bb, ii)
+        ctx.call = (geom, need, m_max)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad):
+        lib = _lib.load()
+        feat_f, wc, cc, bb, ii = ctx.saved_tensors
+        geom, need, m_max = ctx.call
+        dev = feat_f.device
+        g = _f32c(grad, "grad")
+        ws, wsp = _aligned_workspace(need, dev)
+        d_feat = torch.empty_like(feat_f) if ctx.needs_input_grad[0] else None     # (preserve_format: the map's own layout)
+        d_w = torch.empty_like(wc) if ctx.needs_input_grad[1] else None
+        d_ctx = torch.empty_like(cc)
+        if m_max == 0:
+            d_feat = None if d_feat is None else d_feat.zero_()
+            d_w = None if d_w is None else d_w.zero_()
+        _lib.check(lib.fm_window_merge_backward(_ptr(feat_f), *geom, _ptr(wc), _ptr(cc), _ptr(bb), _ptr(ii), m_max, _ptr(g),
+                                                wsp, need, _ptr(d_feat), _ptr(d_w), _ptr(d_ctx), _stream(dev)),
+                   "fm_window_merge_backward")
+        return (d_feat, d_w, d_ctx if ctx.needs_input_grad[2] else None,
+                None, None, None, None, None, None, None)
+
+
+def window_merge(feat_f: torch.Tensor, w_win: torch.Tensor, ctx_rows: torch.Tensor, b_ids: torch.Tensor, ids: torch.Tensor,
+                 w: int, stride: int, h_c: int, w_c: int, pad: int = 2) -> torch.Tensor:
+    """Window crop + context merge of one image as one differentiable HIP op (float32 on the exact-float32 matrix
+    instructions, forward and backward, both deterministic):
+        out[m, r, :] = w_win win[m, r, :] + ctx_rows[m, :]          [M, w w, 64]
+    win = the w x w window of feat_f [N, 64, Hf, Wf] at cell ids[m] of sample b_ids[m] on the h_c x w_c grid (gather_windows'
+    crop: zero padding), w_win [64, 64] = the window half of merge_feat.weight, ctx_rows [M, 64] = its other half applied to
+    the projected coarse descriptors, plus the bias.  The windows are never written to memory.  The map's gradient comes
+    back in the map's layout; the map's and w_win's are computed only where they are asked for.  Inputs that window_merge_supported refuses
+    raise; so do CPU tensors."""
+    _on_gpu(feat_f, "feat_f")
+    if not window_merge_supported(feat_f, w):
+        raise ValueError(f"window_merge serves float32 maps [N, 64, Hf, Wf] (NCHW-contiguous or channels-last) at w in (5, 7), "
+                         f"got {tuple(feat_f.shape)} {feat_f.dtype}, w = {w}")
+    m = int(b_ids.shape[0])
+    if tuple(w_win.shape) != (64, 64) or w_win.dtype != torch.float32 or not w_win.is_cuda:
+        raise ValueError(f"window_merge: w_win is a float32 GPU tensor [64, 64], got {tuple(w_win.shape)} {w_win.dtype}")
+    if tuple(ctx_rows.shape) != (m, 64) or ctx_rows.dtype != torch.float32 or not ctx_rows.is_cuda:
+        raise ValueError(f"window_merge: ctx_rows is a float32 GPU tensor [{m}, 64], got {tuple(ctx_rows.shape)} {ctx_rows.dtype}")
+    if int(ids.shape[0]) != m:
+        raise ValueError("window_merge: b_ids and ids differ in length")
+    return _WindowMerge.apply(feat_f, w_win, ctx_rows, b_ids, ids, int(w), int(stride), int(h_c), int(w_c), int(pad))
+
+
 def fine_match_maps(feat_f0: torch.Tensor, feat_f1: torch.Tensor, b_ids, i_ids, j_ids, w: int, stride: int, w0c: int,
                     w1c: int, mix0: torch.Tensor, mix1: torch.Tensor, mkpts0_c: torch.Tensor, mkpts1_c: torch.Tensor,
                     scale_f: float, pad: int = 2, count: Optional[torch.Tensor] = None,

@@ -780,6 +780,47 @@ int fm_qkv_projection_backward(const float* x, const float* src, const float* wq
                                size_t workspace_bytes, float* d_x, float* d_src, float* d_wq, float* d_wk, float* d_wv,
                                void* stream);
 
+/*
+ * Window crop + context merge of the fine preprocessing (the crop, then the merge layer over [window | context]) and its
+ * gradient, fused, per image: the fine level's training path.  feat_f [dev] float32 [N, Cf, Hf, Wf] in `layout` 0 (NCHW)
+ * or 1 (channels-last); b_ids, ids [dev] int64 [m_max], (y, x) = divmod(ids[m], w_c) on the h_c x w_c coarse grid; w_win
+ * [64, 64] float32 row-major ([out, in]: the merge weight's columns of the window half, contiguous); ctx [m_max, 64]
+ * float32, the position-independent half of the merge, one row per match.  All pointers 16-byte aligned.
+ *     win[m, r, c] = feat_f[b_m, c, stride y - pad + r / W, stride x - pad + r % W]     (0 outside the map)
+ *     out[m, r, :] = w_win win[m, r, :] + ctx[m, :]                                     out [m_max, W W, 64]
+ * float32 on the exact-float32 matrix instructions: one rounding per product, no reduced precision.  The windows and the
+ * concatenation are never written to memory, in either direction.  The rows must be valid, as for fm_gather_windows: a
+ * row whose sample or cell lies outside the batch or the grid reads a window of zeros (out = ctx[m]) and gives the map
+ * no gradient, but nothing checks that a valid cell is the intended one.
+ *   fm_window_merge_forward  : out.  Two launches.
+ *   fm_window_merge_backward : from g [m_max, W W, 64] (the gradient of out):
+ *                                d_ctx [m_max, 64]    = sum_r g[m, r, :];
+ *                                d_w_win [64, 64]     = sum_{m, r} g[m, r, :]^T win[m, r, :] (the windows cropped again);
+ *                                                       may be NULL: no weight-gradient work is done then;
+ *                                d_feat [N, Cf, Hf, Wf] in `layout` = the crop's adjoint of g w_win, as
+ *                                                       fm_gather_windows_backward defines it (every element written,
+ *                                                       exact +0 where no window reads); may be NULL (a frozen
+ *                                                       backbone): g w_win is not computed then.
+ * workspace: fm_window_merge_workspace_bytes(N, h_c, w_c, m_max, W) bytes [dev], 256-byte aligned: the weight in the
+ * kernels' operand order, one slab of partial weight gradients per workgroup (at most 256), g w_win [m_max, W W, 64] and
+ * the crop backward's lists; the same size serves both calls, and nothing is kept in it between calls.  Supported: Cf =
+ * 64, W in {5, 7}, stride >= 1, pad >= 0, m_max W W <= 2^24, fewer than 2^31 - 1 cells in the batch.  The query answers 0
+ * for arguments that the calls refuse.  No float atomics, grids that depend on the arguments alone: every output is the
+ * same bits on every run.  No host synchronisation and no allocation.
+ * m_max = 0 returns FM_OK at once, nothing looked at or written.  Statuses, checked in this order before anything is
+ * launched: FM_E_NULL (a required pointer; d_feat and d_w_win may be NULL), FM_E_SHAPE (a non-positive size or stride, m_max < 0),
+ * FM_E_UNSUPPORTED (anything outside the list above, a layout that is neither 0 nor 1), FM_E_WORKSPACE (NULL, too small
+ * or misaligned); then a hipError_t.
+ */
+size_t fm_window_merge_workspace_bytes(int N, int h_c, int w_c, int m_max, int W);
+int fm_window_merge_forward(const float* feat_f, int N, int Cf, int Hf, int Wf, int layout, int W, int stride, int pad,
+                            int h_c, int w_c, const float* w_win, const float* ctx, const int64_t* b_ids,
+                            const int64_t* ids, int m_max, void* workspace, size_t workspace_bytes, float* out, void* stream);
+int fm_window_merge_backward(const float* feat_f, int N, int Cf, int Hf, int Wf, int layout, int W, int stride, int pad,
+                             int h_c, int w_c, const float* w_win, const float* ctx, const int64_t* b_ids,
+                             const int64_t* ids, int m_max, const float* g, void* workspace, size_t workspace_bytes,
+                             float* d_feat, float* d_w_win, float* d_ctx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

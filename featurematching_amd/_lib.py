@@ -64,6 +64,7 @@ SIGNATURES = {
     "fm_debug_defer_exact_layout": (_i, [_i, _i, _i, _i, _i, C.POINTER(C.c_int64), _i]),
     "fm_read_count": (_i, [_p, _i, C.POINTER(C.c_int32), _p]),
     "fm_read_count_info": (_i, [_p, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _p]),
+    "fm_debug_pose_solve": (_i, [_p, _p, _i, _p, _p, _p]),
     "fm_debug_launch_flat": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _f, _f, _i, _p]),
     "fm_coarse_softmax_stats": (_i, [_p, _i, _i, _i, _i, _i, C.POINTER(_p), C.POINTER(_p), C.POINTER(_i), C.POINTER(_p),
                                      C.POINTER(_p), C.POINTER(_i)]),
@@ -119,6 +120,8 @@ SIGNATURES = {
     "fm_fine_transformer_status": (_i, [_p, _p, _i, _p, _i, _i, _p, _p, _p, _p, _p]),
     "fm_fine_transformer_start": (_i, [_p, _p, _i, _p, _i, _i, _p, _p, _p, _p, _i, _p, _p]),
     "fm_epipolar_errors": (_i, [_p, _p, _i, _p, _p, _i, _i, _p, _p, _p, _f, _p, _p, _p, _p]),
+    "fm_pose_workspace_bytes": (C.c_size_t, [_i, _i, _i]),
+    "fm_estimate_pose": (_i, [_p, _p, _i, _p, _p, _i, _i, _p, _p, _f, _i, C.c_uint64, _p, C.c_size_t, _p, _p, _p, _p, _p, _p]),
     "fm_fine_match": (_i, [_p, _p, _i, _p, _i, _i, _p, _p, _p, _p, _f, _p, _p, _p]),
     "fm_fine_match_backward_workspace_bytes": (C.c_size_t, [_i, _i]),
     "fm_fine_match_backward": (_i, [_p, _p, _i, _p, _i, _i, _p, _p, _f, _p, _p, _p, C.c_size_t, _p, _p, _p, _p, _p]),

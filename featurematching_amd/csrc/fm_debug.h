@@ -57,6 +57,10 @@ int fm_debug_defer_exact(int mode);
 /* Byte offset in the coarse workspace of the counter of deferred entries (int32, zeroed per call), the tag bit of a list
  * index, and whether a common-path call of this shape defers under the present switch (3 values). */
 int fm_debug_defer_exact_layout(int N, int L, int S, int C, int cand_slots, int64_t* out, int n_out);
+/* The five-point solver of fm_estimate_pose (k_pose_solve) alone, on the caller's samples: q0, q1 [dev] float64 [S, 5, 2]
+ * normalised coordinates -> E_out [dev] float64 [S, 10, 9] (the first count_out[s] of a sample's ten slots are written:
+ * unit Frobenius norm, ascending z) and count_out [dev] int32 [S].  FM_E_NULL, FM_E_SHAPE (S <= 0), a hipError_t. */
+int fm_debug_pose_solve(const double* q0, const double* q1, int S, double* E_out, int32_t* count_out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -821,6 +821,38 @@ int fm_window_merge_backward(const float* feat_f, int N, int Cf, int Hf, int Wf,
                              const int64_t* ids, int m_max, const float* g, void* workspace, size_t workspace_bytes,
                              float* d_feat, float* d_w_win, float* d_ctx, void* stream);
 
+/*
+ * Relative pose of every pair from its matches (utils/metrics.py:79-109 estimate_pose, there OpenCV on the host, one pair
+ * at a time): five-point RANSAC over `samples` hypotheses per pair, float64 arithmetic, four launches, no host
+ * synchronisation.  Inputs as fm_epipolar_errors takes them: mkpts0 / mkpts1 [dev] float32 [m_max, kpt_stride], m_bids
+ * [dev] int64 [m_max], the number of matches min(*d_count, m_max) when d_count != NULL, K0 / K1 [dev] float32 [N, 3, 3].
+ *   m_bids must be NON-DECREASING (CoarseMatching writes it so): pair b owns a contiguous range of rows; a row whose id lies
+ *   outside [0, N) belongs to no pair and its inlier flag is 0.
+ *   Normalisation: q = ((x - cx) / fx, (y - cy) / fy), each image by its own K; a match is an inlier of E where its
+ *   squared Sampson distance (q1^T E q0)^2 / ((E q0)_x^2 + (E q0)_y^2 + (E^T q1)_x^2 + (E^T q1)_y^2) is below
+ *   (pixel_thr / f)^2, f = (fx0 + fy0 + fx1 + fy1) / 4.
+ *   Sampling: draw k = 0..7 of hypothesis h of pair b is splitmix64((8 h + k) * 0x9E3779B97F4A7C15 + key) mod M_b with key
+ *   = synth._stream_key(seed, b); the sample is the first five distinct draws (fewer, or M_b < 5: no hypothesis).
+ *   Each sample yields up to ten essential matrices (Nister's five-point method); the pair's winner has the most inliers,
+ *   then the lowest hypothesis, then the lowest candidate slot (ascending z).  Of its four decompositions (R, +-t) the one
+ *   with the most inliers in front of both cameras wins, the first of equals.  The same inputs give the same bits.
+ * Outputs [dev]: R_out float64 [N, 9] (row-major rotation), t_out float64 [N, 3] (unit length), E_out float64 [N, 9] (the
+ * winning essential matrix, unit Frobenius norm), inlier uint8 [m_max] (the winner's inliers; every row is written),
+ * per_pair int32 [N, 4] = {matches, inliers, inliers in front of both cameras, ok}.  ok = 1 only where the pair has at
+ * least 5 matches, a candidate existed and some inlier lies in front of both cameras; else R = I, t = 0.
+ * workspace: fm_pose_workspace_bytes(N, m_max, samples) bytes [dev], 256-byte aligned (the query returns 0 for what the
+ * call refuses and does not decrease in any argument).
+ * Statuses, checked in this order before anything is launched: FM_E_NULL (a required pointer; d_count may be NULL),
+ * FM_E_SHAPE (N <= 0, m_max < 0, kpt_stride < 2, samples <= 0), FM_E_UNSUPPORTED (pixel_thr <= 0 or not finite, samples >
+ * 65536, m_max >= 2^31 / 8), FM_E_WORKSPACE (NULL, too small or misaligned); then m_max = 0 returns FM_OK at once, nothing
+ * written; then a hipError_t.
+ */
+size_t fm_pose_workspace_bytes(int N, int m_max, int samples);
+int fm_estimate_pose(const float* mkpts0, const float* mkpts1, int kpt_stride, const int64_t* m_bids, const int32_t* d_count,
+                     int m_max, int N, const float* K0, const float* K1, float pixel_thr, int samples, uint64_t seed,
+                     void* workspace, size_t workspace_bytes, double* R_out, double* t_out, double* E_out,
+                     unsigned char* inlier, int32_t* per_pair, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -31,9 +31,20 @@ struct PrepArgs {
   float* diag;                        // diagnostic build: stamp buffer
 };
 
-__device__ __forceinline__ bool bad_value(float4 v) {   // NaN fails the comparison too
-  return !(fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))) < 32768.f) ||
-         v.x != v.x || v.y != v.y || v.z != v.z || v.w != v.w;
+// Four codes clamp(rint(x * inv_sigma), +-127), element 0 in the lowest byte.  Three instructions per element and three
+// per word instead of eight and six (rint, max, min, convert; and / shift / or):
+//   v_med3_f32 clamps BEFORE the rounding - the bounds are integers and rint is monotone, so the order does not matter;
+//     a NaN product (the multiplication has quieted it) leaves it as min3 = -127, which is what fmax / fmin made of it
+//   + 1.5 * 2^23 rounds to nearest-even at an ulp of one, which is rintf's rounding, and leaves the code in two's
+//     complement in the float's lowest byte (|code| <= 127: the sum stays in [2^23, 2^24))
+//   v_perm_b32 gathers the four lowest bytes (selector bytes 0-3: second operand, 4-7: first, 0x0c: zero)
+__device__ __forceinline__ int quant4(float x0, float x1, float x2, float x3, float inv_sigma) {
+  constexpr float kRound = 12582912.f;
+  const unsigned u0 = __float_as_uint(__builtin_amdgcn_fmed3f(x0 * inv_sigma, -127.f, 127.f) + kRound);
+  const unsigned u1 = __float_as_uint(__builtin_amdgcn_fmed3f(x1 * inv_sigma, -127.f, 127.f) + kRound);
+  const unsigned u2 = __float_as_uint(__builtin_amdgcn_fmed3f(x2 * inv_sigma, -127.f, 127.f) + kRound);
+  const unsigned u3 = __float_as_uint(__builtin_amdgcn_fmed3f(x3 * inv_sigma, -127.f, 127.f) + kRound);
+  return (int)(__builtin_amdgcn_perm(u1, u0, 0x0c0c0400u) | __builtin_amdgcn_perm(u3, u2, 0x04000c0cu));
 }
 
 // One dispatch prepares both images and clears the per-call counters.
@@ -117,8 +128,8 @@ __global__ __launch_bounds__(256) void k_prep_split(PrepArgs a) {
   }
 
   // ---- the image's step: largest |x| over kPrepSampleRows rows spread evenly over the image (the same rows in every
-  // workgroup of the image: max is order independent, so all of them arrive at the same step).  <= 8 loads per
-  // thread, all in flight together and ahead of the block's own rows ----
+  // workgroup of the image: max is order independent, so all of them arrive at the same step).  8 loads per
+  // thread, all in flight together behind the block's own rows ----
   float amax_s = 0.f;
   const bool exact_step = a.exact_step != 0;         // (uniform)
   if (exact_step) {
@@ -135,22 +146,39 @@ __global__ __launch_bounds__(256) void k_prep_split(PrepArgs a) {
     const int ns = min(kPrepSampleRows, rows);
     const int vpr = a.c_in >> 2;                       // 4-channel vectors per row (c_in % 4 == 0)
     const int total = ns * vpr;                        // <= 32 * 64
-    float4 sv[8];
     // (every workgroup starts at another row of the sample: 300 workgroups asking for the same lines at the same
     // moment queue up on a few L2 channels)
     const int rot = (int)((blockIdx.x * 5u) % (unsigned)ns) * vpr;
+    // All eight requests leave back to back: no load sits behind a branch (a vector past the sample's end asks for the
+    // sample's last one again - a maximum does not change under repetition), the input type is decided once around the
+    // loads and not inside each, and the two divisions of every address are multiplications by reciprocals the whole
+    // workgroup shares.  (With a predicate and the type switch around every load the compiler waited for each request -
+    // and, at the first, for the block's own rows - before it formed the next one's address, ~170 instructions of 64-bit
+    // division: eight L2 round trips in a row, 4.3 us from the workgroup's start until everything had landed; now 2.8.)
+    //   idx / vpr         = idx * ceil(2^17 / vpr) >> 17    exact for idx < 2048, vpr <= 64
+    //   t * rows / ns     = t * (rows / ns) + (t * (rows % ns)) / ns,  the last by ceil(2^16 / ns) >> 16: exact below 2048
+    const unsigned vinv = (131072u + (unsigned)vpr - 1u) / (unsigned)vpr;
+    const int rq = rows / ns, rr = rows - rq * ns;
+    const unsigned ninv = (65536u + (unsigned)ns - 1u) / (unsigned)ns;
+    long e[8];
 #pragma unroll
     for (int p = 0; p < 8; ++p) {
-      int idx = p * 256 + tid;
-      sv[p] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (idx < total) {
-        idx += rot;
-        if (idx >= total) idx -= total;
-        const int t = idx / vpr, v = idx - t * vpr;
-        const long e = ((long)b * rows + (long)t * rows / ns) * a.c_in + v * 4;
-        if (a.in_dtype == FM_F32) sv[p] = *reinterpret_cast<const float4*>((const float*)src + e);
-        else sv[p] = half4_to_float4(*reinterpret_cast<const uint2*>((const unsigned short*)src + e), a.in_dtype);
-      }
+      int idx = min(p * 256 + tid, total - 1) + rot;
+      if (idx >= total) idx -= total;
+      const int t = (int)(((unsigned)idx * vinv) >> 17), v = idx - t * vpr;
+      const int srow = t * rq + (int)(((unsigned)(t * rr) * ninv) >> 16);      // = t * rows / ns
+      e[p] = ((long)b * rows + srow) * a.c_in + v * 4;
+    }
+    float4 sv[8];
+    if (a.in_dtype == FM_F32) {
+#pragma unroll
+      for (int p = 0; p < 8; ++p) sv[p] = *reinterpret_cast<const float4*>((const float*)src + e[p]);
+    } else {
+      uint2 hv[8];
+#pragma unroll
+      for (int p = 0; p < 8; ++p) hv[p] = *reinterpret_cast<const uint2*>((const unsigned short*)src + e[p]);
+#pragma unroll
+      for (int p = 0; p < 8; ++p) sv[p] = half4_to_float4(hv[p], a.in_dtype);
     }
 #pragma unroll
     for (int p = 0; p < 8; ++p)
@@ -181,74 +209,93 @@ __global__ __launch_bounds__(256) void k_prep_split(PrepArgs a) {
   _Float16* const lo = img1 ? a.lo1 : a.lo0;
 
   float s1 = 0.f, amax = 0.f, clip = 0.f;
-  bool bad = false;
   constexpr int NCH16 = (C / 16 + 7) / 8;     // 16-channel chunks per thread (one 16-byte store of codes each)
+  // The source of the rows is decided ONCE, around the chunk loop (a generic lambda, instantiated per source): the
+  // staged loop then holds no global load, so nothing in it waits on the memory counter - with the three sources inside
+  // one loop body the compiler put a wait for ALL outstanding memory operations ahead of every chunk, and the second
+  // chunk's LDS reads stood behind the first chunk's code store being acknowledged.
+  const auto chunks = [&](auto source) {
+    constexpr int SRC = decltype(source)::value;      // 0: the staged tile, 1: float32 rows, 2: half-precision rows
 #pragma unroll
-  for (int n = 0; n < NCH16; ++n) {           // C/16 chunks of 16 channels, 8 per pass
-    const int q16 = n * 8 + (tid >> 5);
-    if (q16 >= C / 16) break;                  // (C = 64: four chunks, half of the threads have none)
-    float4 v[4];
+    for (int n = 0; n < NCH16; ++n) {           // C/16 chunks of 16 channels, 8 per pass
+      const int q16 = n * 8 + (tid >> 5);
+      if (q16 >= C / 16) break;                  // (C = 64: four chunks, half of the threads have none)
+      float4 v[4];
 #pragma unroll
-    for (int p = 0; p < 4; ++p) v[p] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (staged) {
+      for (int p = 0; p < 4; ++p) v[p] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if constexpr (SRC == 0) {
 #pragma unroll
-      for (int p = 0; p < 4; ++p) v[p] = *reinterpret_cast<const float4*>(&tile[r * PITCH + q16 * 16 + 4 * p]);
-    } else if (local < rows) {
-      if (a.in_dtype == FM_F32) {
-        const float* row = (const float*)src + row_off;
+        for (int p = 0; p < 4; ++p) v[p] = *reinterpret_cast<const float4*>(&tile[r * PITCH + q16 * 16 + 4 * p]);
+      } else if (local < rows) {
+        if constexpr (SRC == 1) {
+          const float* row = (const float*)src + row_off;
 #pragma unroll
-        for (int p = 0; p < 4; ++p)
-          if (q16 * 16 + 4 * p < a.c_in) v[p] = *reinterpret_cast<const float4*>(row + q16 * 16 + 4 * p);
-      } else {
-        // half-precision rows (what a ROCm backbone under autocast hands over): 4 values per 8-byte load; every
-        // float16 / bfloat16 value is exact in float32, so everything downstream sees the caller's numbers
-        const unsigned short* row = (const unsigned short*)src + row_off;
+          for (int p = 0; p < 4; ++p)
+            if (q16 * 16 + 4 * p < a.c_in) v[p] = *reinterpret_cast<const float4*>(row + q16 * 16 + 4 * p);
+        } else {
+          // half-precision rows (what a ROCm backbone under autocast hands over): 4 values per 8-byte load; every
+          // float16 / bfloat16 value is exact in float32, so everything downstream sees the caller's numbers
+          const unsigned short* row = (const unsigned short*)src + row_off;
+          uint2 hv[4];
 #pragma unroll
-        for (int p = 0; p < 4; ++p) {
-          uint2 hv = make_uint2(0u, 0u);
-          if (q16 * 16 + 4 * p < a.c_in) hv = *reinterpret_cast<const uint2*>(row + q16 * 16 + 4 * p);
-          v[p] = half4_to_float4(hv, a.in_dtype);
+          for (int p = 0; p < 4; ++p) {
+            hv[p] = make_uint2(0u, 0u);
+            if (q16 * 16 + 4 * p < a.c_in) hv[p] = *reinterpret_cast<const uint2*>(row + q16 * 16 + 4 * p);
+          }
+#pragma unroll
+          for (int p = 0; p < 4; ++p) v[p] = half4_to_float4(hv[p], a.in_dtype);
+        }
+      }
+      const float x[16] = {v[0].x, v[0].y, v[0].z, v[0].w, v[1].x, v[1].y, v[1].z, v[1].w,
+                           v[2].x, v[2].y, v[2].z, v[2].w, v[3].x, v[3].y, v[3].z, v[3].w};
+      // L1 sum in element order (its rounding is part of the result); the maximum in any order (NaN never wins it)
+      float m16 = 0.f;
+#pragma unroll
+      for (int e = 0; e < 16; e += 2) {
+        s1 += fabsf(x[e]);
+        s1 += fabsf(x[e + 1]);
+        m16 = fmaxf(fmaxf(m16, fabsf(x[e])), fabsf(x[e + 1]));      // (one v_max3_f32 with |.| source modifiers)
+      }
+      amax = fmaxf(amax, m16);
+      // The clipped mass is +0 term by term unless an element lies beyond 127 sigma, which kPrepHeadroom makes rare: the
+      // sixteen sub / max / add run only in a wave one of whose lanes holds such an element in this chunk (and then in
+      // all of its lanes, in element order: the same sum, since clip + (+0) = clip).
+      if (__any(m16 > clip_at)) {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) clip += fmaxf(fabsf(x[e]) - clip_at, 0.f);
+      }
+      int wq[4];
+#pragma unroll
+      for (int p = 0; p < 4; ++p) wq[p] = quant4(x[4 * p], x[4 * p + 1], x[4 * p + 2], x[4 * p + 3], inv_sigma);
+      const int h = q16 / KS8, ks = q16 - h * KS8;
+      const long off = (((rb * KS8 + ks) * 2 + h) * 32 + r) * 16;
+      *reinterpret_cast<int4*>(qp + off) = make_int4(wq[0], wq[1], wq[2], wq[3]);
+      if (PLANES) {      // the two 8-channel chunks of this 16-channel chunk, in k_prep_f16's layout and arithmetic
+        constexpr int KSTEPS = C / 16;
+#pragma unroll
+        for (int c8 = 0; c8 < 2; ++c8) {
+          const float x[8] = {v[2 * c8].x, v[2 * c8].y, v[2 * c8].z, v[2 * c8].w,
+                              v[2 * c8 + 1].x, v[2 * c8 + 1].y, v[2 * c8 + 1].z, v[2 * c8 + 1].w};
+          half8 hh, ll;
+#pragma unroll
+          for (int e = 0; e < 8; ++e) split_f16(x[e] * sc16, hh, ll, e);
+          const int q8 = 2 * q16 + c8;
+          const int h2 = q8 / KSTEPS, ks2 = q8 - h2 * KSTEPS;
+          const long off2 = (((rb * KSTEPS + ks2) * 2 + h2) * 32 + r) * 8;
+          *reinterpret_cast<half8*>(hi + off2) = hh;
+          *reinterpret_cast<half8*>(lo + off2) = ll;
         }
       }
     }
-    int wq[4];
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      bad = bad || bad_value(v[p]);
-      const float x[4] = {v[p].x, v[p].y, v[p].z, v[p].w};
-      int wd = 0;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float ax = fabsf(x[e]);
-        s1 += ax;
-        amax = fmaxf(amax, ax);
-        clip += fmaxf(ax - clip_at, 0.f);
-        const int c = (int)fminf(fmaxf(rintf(x[e] * inv_sigma), -127.f), 127.f);
-        wd |= (c & 0xff) << (8 * e);
-      }
-      wq[p] = wd;
-    }
-    const int h = q16 / KS8, ks = q16 - h * KS8;
-    const long off = (((rb * KS8 + ks) * 2 + h) * 32 + r) * 16;
-    *reinterpret_cast<int4*>(qp + off) = make_int4(wq[0], wq[1], wq[2], wq[3]);
-    if (PLANES) {      // the two 8-channel chunks of this 16-channel chunk, in k_prep_f16's layout and arithmetic
-      constexpr int KSTEPS = C / 16;
-#pragma unroll
-      for (int c8 = 0; c8 < 2; ++c8) {
-        const float x[8] = {v[2 * c8].x, v[2 * c8].y, v[2 * c8].z, v[2 * c8].w,
-                            v[2 * c8 + 1].x, v[2 * c8 + 1].y, v[2 * c8 + 1].z, v[2 * c8 + 1].w};
-        half8 hh, ll;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) split_f16(x[e] * sc16, hh, ll, e);
-        const int q8 = 2 * q16 + c8;
-        const int h2 = q8 / KSTEPS, ks2 = q8 - h2 * KSTEPS;
-        const long off2 = (((rb * KSTEPS + ks2) * 2 + h2) * 32 + r) * 8;
-        *reinterpret_cast<half8*>(hi + off2) = hh;
-        *reinterpret_cast<half8*>(lo + off2) = ll;
-      }
-    }
-  }
+  };
+  if (staged) chunks(std::integral_constant<int, 0>{});
+  else if (a.in_dtype == FM_F32) chunks(std::integral_constant<int, 1>{});
+  else chunks(std::integral_constant<int, 2>{});
   PREP_STAMP(3)
+  // A bad value (NaN, Inf, |x| >= 32768) shows in what the thread has folded anyway: Inf and the range in its maximum,
+  // NaN in its L1 sum (at most 32 terms below 2^15 each: finite unless an element is not) - one test per thread, not
+  // one per element.
+  const bool bad = !(amax < 32768.f) || !(s1 < INFINITY);
   // per-row L1 norm and clipped mass (a row's channels sit in 8 threads); block maxima
   sm[tid >> 5][r] = s1;
   sm2[tid >> 5][r] = clip;

@@ -17,10 +17,11 @@ __global__ __launch_bounds__(256) void k_epipolar(const float* __restrict__ k0, 
                                                   const float* __restrict__ K1, float thr, float* __restrict__ epi,
                                                   unsigned char* __restrict__ inlier, int32_t* __restrict__ per_pair) {
   const int m = blockIdx.x * 256 + threadIdx.x;
-  const int M = d_count ? min(d_count[0], m_max) : m_max;
+  const int M = d_count ? max(0, min(d_count[0], m_max)) : m_max;
   if (m >= M) return;
-  const int b = (int)m_bids[m];
-  if (b < 0 || b >= N) { epi[m] = __builtin_nanf(""); if (inlier) inlier[m] = 0; return; }
+  const int64_t id = m_bids[m];                // range-tested in 64 bits, as k_pose_prep does: 2^32 + 1 is no pair
+  if (id < 0 || id >= N) { epi[m] = __builtin_nanf(""); if (inlier) inlier[m] = 0; return; }
+  const int b = (int)id;
   const float* t4 = T + (long)b * 16;          // row-major [4,4]
   const float tx = t4[3], ty = t4[7], tz = t4[11];
   // E = [t]x R   (numeric.cross_product_matrix(t) @ R)

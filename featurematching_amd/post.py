@@ -29,7 +29,10 @@ VERSION = 1
 
 def epipolar_errors(mkpts0: torch.Tensor, mkpts1: torch.Tensor, m_bids: torch.Tensor, T_0to1: torch.Tensor,
                     K0: torch.Tensor, K1: torch.Tensor, inlier_thr: float = 1e-4, count: Optional[torch.Tensor] = None):
-    """-> (epi_errs float32 [M], inlier bool [M], per_pair int32 [N,2] = matches / inliers per pair)."""
+    """-> (epi_errs float32 [M], inlier bool [M], per_pair int32 [N,2] = matches / inliers per pair).
+    `count`: a tensor holding the number of rows, on any device and of any integer type (converted as estimate_poses
+    converts it; a negative count is none).  A row behind the count, like a row whose id lies outside [0, N) - tested in
+    64 bits, as estimate_poses tests it - reads NaN and not-inlier and is counted in no pair."""
     lib = _lib.load()
     if not mkpts0.is_cuda:
         raise RuntimeError("mkpts0 must live on the GPU: the HIP path has no CPU fallback")
@@ -39,7 +42,9 @@ def epipolar_errors(mkpts0: torch.Tensor, mkpts1: torch.Tensor, m_bids: torch.Te
     n = T_0to1.shape[0]
     f = lambda t: t.to(dev).float().contiguous()
     T, a0, a1 = f(T_0to1), f(K0), f(K1)
-    epi = torch.empty(m, dtype=torch.float32, device=dev)
+    if count is not None:                                 # the C call reads one int32 on the device
+        count = count.to(dev, torch.int32).reshape(-1)[:1].contiguous()
+    epi = torch.full((m,), float("nan"), dtype=torch.float32, device=dev)   # the kernel writes the rows that exist
     inl = torch.zeros(m, dtype=torch.uint8, device=dev)
     per = torch.zeros(n, 2, dtype=torch.int32, device=dev)
     if m:

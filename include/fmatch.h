@@ -534,11 +534,17 @@ int fm_fine_transformer_start(const float* win0, const float* win1, int m_max, c
  * of every match against a relative pose, and a RANSAC-free inlier score per pair.
  *   mkpts0/mkpts1 [dev] float32 [m_max, kpt_stride] (x, y in pixels first; kpt_stride = 3 for the fine
  *   keypoints [M,3], 2 for plain [M,2]); m_bids [dev] int64 [m_max] (data['m_bids']); the number of matches is
- *   min(*d_count, m_max) when d_count != NULL.  T_0to1 [dev] float32 [N,4,4], K0/K1 [dev] float32 [N,3,3],
+ *   max(0, min(*d_count, m_max)) when d_count != NULL (d_count [dev]: a device address, as in fm_estimate_pose).
+ *   T_0to1 [dev] float32 [N,4,4], K0/K1 [dev] float32 [N,3,3],
  *   row-major.  E = [t]x R (:65-66), points normalised by their intrinsics (:41-42),
  *   d = (p1.E p0)^2 (1/((E p0)_x^2 + (E p0)_y^2) + 1/((E^T p1)_x^2 + (E^T p1)_y^2))   (:47-56).
  * Outputs: epi_errs float32 [m_max] (data['epi_errs']); optional inlier uint8 [m_max] (d < inlier_thr) and
  * per_pair int32 [N,2] = {matches, inliers} per pair, which the caller zeroes beforehand (the kernel adds).
+ * A row whose id lies outside [0, N) - compared as int64, as fm_estimate_pose compares it, so 2^32 + 1 is no pair -
+ * gets epi_errs = NaN and inlier = 0 and is counted in no pair.  Rows behind the count are not written at all: a caller
+ * who wants them to read as foreign rows fills epi_errs with NaN and inlier with 0 beforehand (post.epipolar_errors does).
+ * Status: FM_OK at once for m_max == 0; then FM_E_NULL for a missing mkpts0, mkpts1, m_bids, T_0to1, K0, K1 or epi_errs;
+ * then FM_E_SHAPE for m_max < 0, N <= 0 or kpt_stride < 2.
  */
 int fm_epipolar_errors(const float* mkpts0, const float* mkpts1, int kpt_stride, const int64_t* m_bids,
                        const int32_t* d_count, int m_max, int N, const float* T_0to1, const float* K0,

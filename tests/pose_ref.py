@@ -3,7 +3,9 @@
 The yardstick of tests/test_pose_ref.py and tests/test_gpu_pose.py: sampling, Nister's five-point solver, Sampson
 scoring, the tie rules and the decomposition, vectorised over hypotheses.  The solver's root finder is np.roots by
 default - the kernel uses Durand-Kerner, so it is measured against an independent one; roots="dk" restates the kernel's
-own for experiments.  Nothing here is imported by the package.
+own for experiments.  At the end: the float64 formula of the squared symmetric epipolar distance (csrc/post.hip), its
+plain float32 transcription and the residual measure tests/test_gpu_post_edges.py compares them in, and the checks of
+a pose result that both GPU test files share.  Nothing here is imported by the package.
 """
 from __future__ import annotations
 
@@ -53,24 +55,37 @@ def rodrigues(w):
     return np.eye(3) + np.sin(th) * k + (1 - np.cos(th)) * (k @ k)
 
 
-def scene(seed: int, n: int, noise: float = 0.0, outliers: float = 0.0, back: bool = False):
+def intrinsics(fx, fy, cx, cy):
+    """-> K float32 [3, 3]"""
+    return np.array([[fx, 0, cx], [0, fy, cy], [0, 0, 1]], np.float32)
+
+
+def scene(seed: int, n: int, noise: float = 0.0, outliers: float = 0.0, back: bool = False, intr0=None, intr1=None,
+          baseline: float = 0.3, plane=None):
     """n matches of a seeded two-view scene: depth 2-6, a rotation of about 0.1 rad, baseline 0.3, f = 500, principal
     point (320, 240); `noise` px of Gaussian noise on both images, a share `outliers` redrawn uniformly in image 1;
     `back`: the baseline points towards -x (the decomposition's own t has a positive largest component: such a scene's
-    pose is one of the -t decompositions).
-    -> dict: k0, k1 float32 [n, 2]; K float32 [3, 3]; T float64 [4, 4]; R, t, E (unit Frobenius norm); outlier bool [n];
+    pose is one of the -t decompositions).  `intr0`, `intr1`: (fx, fy, cx, cy) of image 0 / image 1 in place of f = 500
+    and (320, 240), taken at their float32 values, as the kernels read them.  `baseline`: the length of t (0: a pure
+    rotation, E = 0).  `plane`: a [3]; every point lies on the plane a . X = 1 of camera 0 in place of the seeded depths.
+    -> dict: k0, k1 float32 [n, 2]; K float32 [3, 3] (f = 500, whatever intr0 / intr1 say); K0, K1 float32 [3, 3]: the
+    intrinsics of image 0 / image 1; T float64 [4, 4]; R, t, E (unit Frobenius norm; zero where t is); outlier bool [n];
     q0, q1 float64 [n, 2]: the exact normalised coordinates before noise, outliers and the rounding to float32"""
+    K0 = K.copy() if intr0 is None else intrinsics(*intr0)
+    K1 = K.copy() if intr1 is None else intrinsics(*intr1)
+    (fx0, fy0, cx0, cy0), (fx1, fy1, cx1, cy1) = ((float(k[0, 0]), float(k[1, 1]), float(k[0, 2]), float(k[1, 2])) for k in (K0, K1))
     u = synth.uniform(seed, 40, 8)
     axis = 2 * u[:3] - 1
     R = rodrigues(axis / np.linalg.norm(axis) * (0.08 + 0.04 * u[3]))
     d = np.array([-1.0 if back else 1.0, 2 * u[4] - 1, 0.6 * (2 * u[5] - 1)])
-    t = 0.3 * d / np.linalg.norm(d)
+    t = baseline * d / np.linalg.norm(d)
     px = synth.uniform(seed, 41, 3 * n).reshape(3, n)
     x0 = np.stack([px[0] * WIDTH, px[1] * HEIGHT], 1)
-    depth = 2 + 4 * px[2]
-    X = np.stack([(x0[:, 0] - CX) / F, (x0[:, 1] - CY) / F, np.ones(n)], 1) * depth[:, None]
+    ray = np.stack([(x0[:, 0] - cx0) / fx0, (x0[:, 1] - cy0) / fy0, np.ones(n)], 1)
+    depth = 2 + 4 * px[2] if plane is None else 1.0 / (ray @ np.asarray(plane, np.float64))
+    X = ray * depth[:, None]
     Y = X @ R.T + t
-    x1 = np.stack([F * Y[:, 0] / Y[:, 2] + CX, F * Y[:, 1] / Y[:, 2] + CY], 1)
+    x1 = np.stack([fx1 * Y[:, 0] / Y[:, 2] + cx1, fy1 * Y[:, 1] / Y[:, 2] + cy1], 1)
     exact = dict(q0=X[:, :2] / X[:, 2:], q1=Y[:, :2] / Y[:, 2:])
     if noise:
         g = synth.normal(seed, 21, (4, n)).astype(np.float64) * noise
@@ -82,8 +97,31 @@ def scene(seed: int, n: int, noise: float = 0.0, outliers: float = 0.0, back: bo
     E = skew(t) @ R
     T = np.eye(4)
     T[:3, :3], T[:3, 3] = R, t
-    return dict(k0=x0.astype(np.float32), k1=x1.astype(np.float32), K=K.copy(), T=T, R=R, t=t,
-                E=E / np.linalg.norm(E), outlier=out, **exact)
+    return dict(k0=x0.astype(np.float32), k1=x1.astype(np.float32), K=K.copy(), K0=K0, K1=K1, T=T, R=R, t=t,
+                E=E / np.linalg.norm(E) if baseline else E, outlier=out, **exact)
+
+
+# ---- degenerate geometry: what drives the solver's "no candidate" exits -------------------------------------------------
+PLANE = (0.03, -0.02, 0.25)       # a . X = 1: depths of about 3.5 to 4.7 over the image at f = 400 to 900
+
+
+def pure_rotation(seed: int, n: int, **kw):
+    """t = 0: every E = [t]x R is zero, no essential matrix is defined; the matches are a homography's"""
+    return scene(seed, n, baseline=0.0, **kw)
+
+
+def planar(seed: int, n: int, **kw):
+    """all points on the plane PLANE . X = 1 of camera 0: the pose is well defined (the five-point solver, unlike the
+    eight-point one, has no planar degeneracy), the linear system of a sample is merely worse conditioned"""
+    return scene(seed, n, plane=PLANE, **kw)
+
+
+def repeated(seed: int, n: int, distinct: int = 8, **kw):
+    """the first `distinct` matches of scene(seed, distinct), each repeated in turn to fill n rows: a sample of five rows
+    mostly holds the same match twice (distinct = 1: every row is the same match)"""
+    sc = scene(seed, distinct, **kw)
+    rows = np.arange(n) % distinct
+    return dict(sc, **{k: sc[k][rows] for k in ("k0", "k1", "outlier", "q0", "q1")})
 
 
 def exact_samples(seed: int, count: int):
@@ -104,8 +142,45 @@ def batch(scenes):
     k0 = np.concatenate([s["k0"] for s in scenes]).astype(np.float32).reshape(-1, 2)
     k1 = np.concatenate([s["k1"] for s in scenes]).astype(np.float32).reshape(-1, 2)
     bids = np.concatenate([np.full(len(s["k0"]), b, np.int64) for b, s in enumerate(scenes)])
-    Ks = np.stack([s["K"] for s in scenes]).astype(np.float32)
-    return k0, k1, bids, Ks, Ks.copy(), np.stack([s["T"] for s in scenes])
+    K0 = np.stack([s.get("K0", s["K"]) for s in scenes]).astype(np.float32)
+    K1 = np.stack([s.get("K1", s["K"]) for s in scenes]).astype(np.float32)
+    return k0, k1, bids, K0, K1, np.stack([s["T"] for s in scenes])
+
+
+def pair_intrinsics(b: int):
+    """(fx, fy, cx, cy) of image 0 and of image 1 of pair `b`, every pair and image its own: one image's fx lies in 440 to
+    520, the other's in 700 to 790 (which is which varies), fy is 10 to 13 % larger or smaller than fx, so the focal
+    lengths span about 400 to 900 and the mean of either image alone is at least 8 % off the mean of both; principal
+    points 15 to 45 px off (320, 240) on a side that varies -> (intr0, intr1) for scene(intr0=, intr1=)"""
+    u = synth.uniform(b, 45, 17)
+    out = []
+    for v, wide in zip(u[:16].reshape(2, 8), (u[16] < 0.5, u[16] >= 0.5)):
+        fx = 700 + 90 * v[0] if wide else 440 + 80 * v[0]
+        ratio = 1.1 + 0.03 * v[1]
+        fy = fx * ratio if v[2] < 0.5 else fx / ratio
+        off = lambda a, s: (15 + 30 * a) * (1 if s < 0.5 else -1)
+        out.append((fx, fy, CX + off(v[3], v[4]), CY + off(v[5], v[6])))
+    return tuple(out)
+
+
+def with_near_line_matches(sc, rows, distances_px):
+    """scene `sc` with k1 of `rows` replaced by the exact projection moved off its epipolar line until the match's Sampson
+    distance to the true E is `distances_px` (a negative one: to the other side), in the pose estimate's pixels - those of
+    the mean of the four focal lengths: matches that a threshold below the distance drops and one above it keeps"""
+    E = sc["E"].reshape(3, 3)
+    K0, K1 = sc["K0"].astype(np.float64), sc["K1"].astype(np.float64)
+    f = (K0[0, 0] + K0[1, 1] + K1[0, 0] + K1[1, 1]) / 4
+    k1 = sc["k1"].copy()
+    for row, want in zip(rows, distances_px):
+        q0 = sc["q0"][row:row + 1]
+        line = E @ np.append(q0[0], 1.0)
+        step = want / f * line[:2] / np.linalg.norm(line[:2])
+        scale = 1.4                                      # the distance is close to linear in the offset: a few rescalings
+        for _ in range(6):
+            q = sc["q1"][row] + scale * step
+            scale *= abs(want) / f / np.sqrt(sampson(E.ravel(), q0, q[None])[0])
+        k1[row] = (K1[0, 0] * q[0] + K1[0, 2], K1[1, 1] * q[1] + K1[1, 2])
+    return dict(sc, k1=k1.astype(np.float32))
 
 
 def in_band(E, q0, q1, thr2, width=1e-9):
@@ -139,6 +214,43 @@ SCENES = {
     "back30": dict(seed=60, n=300, outliers=0.3, back=True), "back30b": dict(seed=71, n=300, outliers=0.3, back=True),
     "noisy64": dict(seed=24, n=64, noise=0.5, outliers=0.3), "noisy300": dict(seed=25, n=300, noise=0.5, outliers=0.3),
 }
+
+
+# the scenes of tests/test_gpu_post_edges.py, chosen like clean30 (tests/test_pose_ref.py checks each): noise-free, 30 %
+# redrawn, image 0 and image 1 with intrinsics of their own.  "intr0/1/2" are the pairs 0, 1, 2 of one batch (each is
+# estimated under its own stream index), "planar" has every point on PLANE, "thr" is estimated at 0.5, 1 and 3 px.  The
+# first redrawn matches of each are put at 0.95 and 1.05 of a threshold instead (NEAR_LINE): a threshold formed from
+# one image's focal lengths alone, 8 % off at least, or one that is not the caller's, keeps or drops one of them.
+# "planar" has none: coplanar points fit a second essential matrix, the true one's twin about 4 degrees away, as well
+# as the true one, and which of the two collects more of the redrawn matches decides the winner - in about one seed in
+# forty it is the true one, and a match 5 % inside the threshold tips that balance
+EDGE_SCENES = {
+    "intr0": dict(seed=101, n=300, outliers=0.3, pair=0), "intr1": dict(seed=140, n=150, outliers=0.3, pair=1),
+    "intr2": dict(seed=181, n=70, outliers=0.3, pair=2), "planar": dict(seed=436, n=200, outliers=0.3, pair=3, plane=PLANE),
+    "thr": dict(seed=402, n=200, outliers=0.3, pair=4),
+}
+PIXEL_THRS = (0.5, 1.0, 3.0)
+NEAR_LINE = {"thr": (0.475, -0.525, 0.95, -1.05, 2.85, -3.15), "planar": ()}
+
+
+def edge_scene(name: str):
+    kw = dict(EDGE_SCENES[name])
+    intr0, intr1 = pair_intrinsics(kw.pop("pair"))
+    sc = scene(intr0=intr0, intr1=intr1, **kw)
+    near = NEAR_LINE.get(name, (0.95, -1.05))
+    return with_near_line_matches(sc, np.flatnonzero(sc["outlier"])[:len(near)], near)
+
+
+def sparse_batch(pairs: int, live, per_pair: int = 20):
+    """a batch of `pairs` pairs, each with intrinsics of its own, whose matches all lie in the pairs `live` (40 in a single
+    live pair, `per_pair` in each of several): more pairs than matches -> batch()'s tuple"""
+    n = per_pair if len(live) > 1 else 2 * per_pair
+    scenes = []
+    for b in range(pairs):
+        intr0, intr1 = pair_intrinsics(b)
+        sc = scene(200 + b, n if b in live else 1, outliers=0.2, intr0=intr0, intr1=intr1)
+        scenes.append(sc if b in live else dict(sc, k0=sc["k0"][:0], k1=sc["k1"][:0]))
+    return batch(scenes)
 
 
 NOISE_FREE = ("clean", "clean30", "clean60", "back30", "back30b")
@@ -430,9 +542,167 @@ def estimate(k0, k1, K0, K1, seed=0, b=0, samples=2048, pixel_thr=1.0, roots="nu
     return dict(ok=True, E=E, R=best[0], t=best[1], mask=mask, inliers=int(mask.sum()), votes=votes, hyp=int(hyp), slot=int(slot))
 
 
+def same_bits(a, b):
+    return all(np.array_equal(a[k], b[k], equal_nan=True) for k in a) and a.keys() == b.keys()
+
+
+def check_bookkeeping(out, k0, k1, bids, K0, K1, pixel_thr=1.0, any_outcome=False):
+    """`out`: the fields of post.estimate_poses as NumPy arrays.  What holds for any scene: counts and masks are NumPy's
+    for the returned E, R is a rotation, t a unit vector, E is [t]x R up to scale, votes are the inliers in front of both
+    cameras, ok follows the rule.  any_outcome (degenerate geometry, where the winner is rounding luck): every output is
+    finite, matches within in_band of the threshold are left out of the mask comparison instead of being ruled out, and
+    what needs a well-conditioned E - [t]x R against E, the votes against NumPy's - is not asked"""
+    n = K0.shape[0]
+    bids = np.asarray(bids)
+    assert not out["inliers"][(bids < 0) | (bids >= n)].any()
+    if any_outcome:
+        assert all(np.isfinite(out[k]).all() for k in ("R", "t", "E"))
+    for b in range(n):
+        rows = bids == b
+        m = int(rows.sum())
+        matches, inliers, votes, ok = (int(v) for v in out["per_pair"][b])
+        assert matches == m and bool(ok) == bool(out["ok"][b])
+        q0, q1 = normalise(k0[rows][:, :2], K0[b]), normalise(k1[rows][:, :2], K1[b])
+        thr2 = threshold2(K0[b], K1[b], pixel_thr)
+        E, R, t = out["E"][b], out["R"][b], out["t"][b]
+        assert inliers == int(out["inliers"][rows].sum())
+        if m < 5:
+            assert not ok and inliers == 0 and votes == 0
+        if not np.any(E):                                   # no candidate
+            assert not ok and inliers == 0 and not out["inliers"][rows].any()
+        else:
+            assert abs(np.linalg.norm(E) - 1) <= 1e-12
+            band = in_band(E, q0, q1, thr2)
+            assert any_outcome or not band.any()            # a condition of the comparison below, not a tolerance
+            with np.errstate(invalid="ignore"):
+                mask = sampson(E.ravel(), q0, q1) < thr2
+            assert np.array_equal(out["inliers"][rows][~band], mask[~band])
+            assert any_outcome or inliers == int(mask.sum())
+        if ok:
+            assert votes > 0 and inliers >= votes
+            assert np.linalg.norm(R.T @ R - np.eye(3)) <= 1e-12 and abs(np.linalg.det(R) - 1) <= 1e-12
+            assert abs(np.linalg.norm(t) - 1) <= 1e-12
+            if any_outcome:
+                continue
+            # E meets its cubic constraint to 1e-10 (the solver's gate), and so is an essential matrix to about that;
+            # [t]x R of its closed-form decomposition then agrees to the same order: 1e-8 leaves two decimal places
+            G = skew(t) @ R
+            G /= np.linalg.norm(G)
+            assert min(np.linalg.norm(G - E), np.linalg.norm(G + E)) <= 1e-8
+            assert votes == int((in_front(R, t, q0, q1) & mask).sum())
+            assert votes == max(int((in_front(Rd, td, q0, q1) & mask).sum()) for Rd, td in decompose(E))
+        else:
+            assert np.array_equal(R, np.eye(3)) and not t.any() and votes == 0
+
+
 def rotation_angle_deg(Ra, Rb):
     return float(np.rad2deg(np.arccos(np.clip((np.trace(Ra.T @ Rb) - 1) / 2, -1, 1))))
 
 
 def vector_angle_deg(a, b):
     return float(np.rad2deg(np.arccos(np.clip(a @ b / (np.linalg.norm(a) * np.linalg.norm(b)), -1, 1))))
+
+
+# ---- the squared symmetric epipolar distance (csrc/post.hip) ------------------------------------------------------------
+EPS32 = float(np.finfo(np.float32).eps)
+
+
+def symmetric_epipolar(k0, k1, T, K0, K1, parts=False):
+    """The formula at the head of csrc/post.hip for one pair, in float64 on inputs taken at their float32 values, as the
+    kernel reads them: k0, k1 [M, >= 2] pixels, T [4, 4], K0, K1 [3, 3] -> d float64 [M], d = r^2 w with r = p1 . E p0 and
+    w = 1 / ((E p0)_x^2 + (E p0)_y^2) + 1 / ((E^T p1)_x^2 + (E^T p1)_y^2).
+    parts=True -> (d, S, w): S [M] is the sum of the absolute values of every product that r is the signed sum of -
+    |p1_i| |t_k R_lj| |p0_j| over the two products of each of the nine E_ij - the scale of r's rounding error."""
+    w64 = lambda x: np.asarray(x, np.float32).astype(np.float64)
+    k0, k1, T, K0, K1 = w64(k0), w64(k1), w64(T), w64(K0), w64(K1)
+    R, t = T[:3, :3], T[:3, 3]
+    E = skew(t) @ R
+    p0 = np.stack([(k0[:, 0] - K0[0, 2]) / K0[0, 0], (k0[:, 1] - K0[1, 2]) / K0[1, 1], np.ones(len(k0))], 1)
+    p1 = np.stack([(k1[:, 0] - K1[0, 2]) / K1[0, 0], (k1[:, 1] - K1[1, 2]) / K1[1, 1], np.ones(len(k1))], 1)
+    Ep0, Etp1 = p0 @ E.T, p1 @ E
+    r = (p1 * Ep0).sum(1)
+    with np.errstate(all="ignore"):
+        w = 1.0 / (Ep0[:, 0] ** 2 + Ep0[:, 1] ** 2) + 1.0 / (Etp1[:, 0] ** 2 + Etp1[:, 1] ** 2)
+        d = r * r * w
+    if not parts:
+        return d
+    S = ((np.abs(p1) @ (np.abs(skew(t)) @ np.abs(R))) * np.abs(p0)).sum(1)
+    return d, S, w
+
+
+def symmetric_epipolar_f32(k0, k1, T, K0, K1):
+    """the same formula written out in float32 NumPy, one rounding per operation and the sums from left to right: what
+    plain float32 arithmetic makes of it (the reference computes it in float32 torch) -> d float32 [M]"""
+    f = np.float32
+    k0, k1, T, K0, K1 = (np.asarray(x, f) for x in (k0, k1, T, K0, K1))
+    R, (tx, ty, tz) = T[:3, :3], T[:3, 3]
+    E = [[-tz * R[1, c] + ty * R[2, c] for c in range(3)], [tz * R[0, c] - tx * R[2, c] for c in range(3)],
+         [-ty * R[0, c] + tx * R[1, c] for c in range(3)]]
+    p0x, p0y = (k0[:, 0] - K0[0, 2]) / K0[0, 0], (k0[:, 1] - K0[1, 2]) / K0[1, 1]
+    p1x, p1y = (k1[:, 0] - K1[0, 2]) / K1[0, 0], (k1[:, 1] - K1[1, 2]) / K1[1, 1]
+    e = [E[i][0] * p0x + E[i][1] * p0y + E[i][2] for i in range(3)]
+    g = [p1x * E[0][j] + p1y * E[1][j] + E[2][j] for j in range(2)]
+    r = p1x * e[0] + p1y * e[1] + e[2]
+    with np.errstate(all="ignore"):
+        d = r * r * (f(1) / (e[0] * e[0] + e[1] * e[1]) + f(1) / (g[0] * g[0] + g[1] * g[1]))
+    assert d.dtype == np.float32
+    return d
+
+
+def epipolar_case(name: str):
+    """the inputs of tests/test_gpu_post_edges.py's epipolar tests, every pair and image with its own intrinsics
+    (pair_intrinsics) -> (k0, k1 float32 [M, 2], m_bids int64 [M], T float32 [N, 4, 4], K0, K1 float32 [N, 3, 3]).
+    "noisy": 3 pairs of 260 + 300 + 140 = 700 matches (three workgroups of 256), half a pixel of noise, 30 % redrawn;
+    "exact": 3 pairs of 100 matches projected in float64 and rounded to float32; "rotation": one pair of 64 with t = 0"""
+    sizes, kw = {"noisy": ((260, 300, 140), dict(noise=0.5, outliers=0.3)), "exact": ((100, 100, 100), {}),
+                 "rotation": ((64,), dict(baseline=0.0))}[name]
+    scenes = []
+    for b, n in enumerate(sizes):
+        intr0, intr1 = pair_intrinsics(b)
+        scenes.append(scene(80 + b, n, intr0=intr0, intr1=intr1, **kw))
+    k0, k1, bids, K0, K1, T = batch(scenes)
+    return k0, k1, bids, T.astype(np.float32), K0, K1
+
+
+def epipolar_rows(fn, k0, k1, bids, T, K0, K1):
+    """fn = symmetric_epipolar / symmetric_epipolar_f32 over a batch: its result(s) per row, NaN where the id is no pair"""
+    bids = np.asarray(bids)
+    out = None
+    for b in range(len(T)):
+        rows = bids == b
+        res = fn(k0[rows], k1[rows], T[b], K0[b], K1[b])
+        res = res if isinstance(res, tuple) else (res,)
+        if out is None:
+            out = tuple(np.full(len(bids), np.nan, r.dtype) for r in res)
+        for o, r in zip(out, res):
+            o[rows] = r
+    return out if len(out) > 1 else out[0]
+
+
+def epipolar_reference(name: str):
+    """-> (d64, S, w64) per row of epipolar_case(name)"""
+    return epipolar_rows(lambda *a: symmetric_epipolar(*a, parts=True), *epipolar_case(name))
+
+
+def transcription_measure():
+    """the largest residual_measure of the float32 transcription against float64 over the cases of
+    tests/test_gpu_post_edges.py in which d is a number: plain float32's own error in units of eps32 S sqrt(w)"""
+    worst = 0.0
+    for name in ("noisy", "exact"):
+        d64, S, w = epipolar_reference(name)
+        worst = max(worst, float(residual_measure(epipolar_rows(symmetric_epipolar_f32, *epipolar_case(name)), d64, S, w).max()))
+    return worst
+
+
+def residual_bound(S, w, c):
+    """what |sqrt(d) - sqrt(d64)| may be in float32: c eps32 S sqrt(w).  sqrt(d) = |r| sqrt(w) is the residual in units of
+    distance; r is a signed sum of products whose absolute values add up to S, each rounded a few times, so its error
+    scales with eps32 S whatever r itself comes to - measured in d, a match on its epipolar line would allow nothing"""
+    with np.errstate(all="ignore"):
+        return c * EPS32 * S * np.sqrt(w)
+
+
+def residual_measure(d, d64, S, w):
+    """|sqrt(d) - sqrt(d64)| in units of eps32 S sqrt(w64): the c that residual_bound would need for this d"""
+    with np.errstate(all="ignore"):
+        return np.abs(np.sqrt(np.asarray(d, np.float64)) - np.sqrt(d64)) / (EPS32 * S * np.sqrt(w))

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import pose_ref as pr
+from pose_ref import check_bookkeeping, same_bits
 from featurematching_amd import _lib, post
 
 pytestmark = pytest.mark.gpu
@@ -21,49 +22,6 @@ def dev(x):
 def call(k0, k1, bids, K0, K1, **kw):
     out = post.estimate_poses(dev(k0), dev(k1), dev(bids), dev(K0), dev(K1), **kw)
     return {k: getattr(out, k).cpu().numpy() for k in out._fields}
-
-
-def same_bits(a, b):
-    return all(np.array_equal(a[k], b[k], equal_nan=True) for k in a) and a.keys() == b.keys()
-
-
-def check_bookkeeping(out, k0, k1, bids, K0, K1):
-    """what holds for any scene: counts and masks are NumPy's for the returned E, R is a rotation, t a unit vector, E is
-    [t]x R up to scale, votes are the inliers in front of both cameras, ok follows the rule"""
-    n = K0.shape[0]
-    bids = np.asarray(bids)
-    assert not out["inliers"][(bids < 0) | (bids >= n)].any()
-    for b in range(n):
-        rows = bids == b
-        m = int(rows.sum())
-        matches, inliers, votes, ok = (int(v) for v in out["per_pair"][b])
-        assert matches == m and bool(ok) == bool(out["ok"][b])
-        q0, q1 = pr.normalise(k0[rows][:, :2], K0[b]), pr.normalise(k1[rows][:, :2], K1[b])
-        thr2 = pr.threshold2(K0[b], K1[b])
-        E, R, t = out["E"][b], out["R"][b], out["t"][b]
-        if m < 5:
-            assert not ok and inliers == 0 and votes == 0
-        if not np.any(E):                                   # no candidate
-            assert not ok and inliers == 0 and not out["inliers"][rows].any()
-        else:
-            assert abs(np.linalg.norm(E) - 1) <= 1e-12
-            assert not pr.in_band(E, q0, q1, thr2).any()    # a condition of the comparison below, not a tolerance
-            with np.errstate(invalid="ignore"):
-                mask = pr.sampson(E.ravel(), q0, q1) < thr2
-            assert np.array_equal(out["inliers"][rows], mask) and inliers == int(mask.sum())
-        if ok:
-            assert votes > 0 and inliers >= votes
-            assert np.linalg.norm(R.T @ R - np.eye(3)) <= 1e-12 and abs(np.linalg.det(R) - 1) <= 1e-12
-            assert abs(np.linalg.norm(t) - 1) <= 1e-12
-            # E meets its cubic constraint to 1e-10 (the solver's gate), and so is an essential matrix to about that;
-            # [t]x R of its closed-form decomposition then agrees to the same order: 1e-8 leaves two decimal places
-            G = pr.skew(t) @ R
-            G /= np.linalg.norm(G)
-            assert min(np.linalg.norm(G - E), np.linalg.norm(G + E)) <= 1e-8
-            assert votes == int((pr.in_front(R, t, q0, q1) & mask).sum())
-            assert votes == max(int((pr.in_front(Rd, td, q0, q1) & mask).sum()) for Rd, td in pr.decompose(E))
-        else:
-            assert np.array_equal(R, np.eye(3)) and not t.any() and votes == 0
 
 
 @functools.lru_cache(maxsize=None)

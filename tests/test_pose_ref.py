@@ -131,6 +131,117 @@ def test_restatement_finds_the_ground_truth_inliers_of_the_noise_free_scenes(nam
             assert np.array_equal(R, est["R"]) and np.array_equal(t, est["t"])
 
 
+# ---- the scenes and yardsticks of tests/test_gpu_post_edges.py ------------------------------------------------------------
+def test_intrinsics_are_optional_and_existing_scenes_keep_theirs():
+    for name, kw in pr.SCENES.items():
+        sc = pr.scene(**kw)
+        assert np.array_equal(sc["K"], pr.K) and np.array_equal(sc["K0"], pr.K) and np.array_equal(sc["K1"], pr.K), name
+    k0, k1, bids, K0, K1, T = pr.batch([pr.scene(**pr.SCENES["noisy64"]), pr.edge_scene("intr2")])
+    assert np.array_equal(K0[0], pr.K) and np.array_equal(K1[0], pr.K) and K0.dtype == K1.dtype == np.float32
+    sc = pr.edge_scene("intr2")
+    assert np.array_equal(K0[1], sc["K0"]) and np.array_equal(K1[1], sc["K1"]) and not np.array_equal(sc["K0"], sc["K1"])
+    assert bids.tolist() == [0] * 64 + [1] * 70 and T.shape == (2, 4, 4)
+    # the exact normalised coordinates are the float32 keypoints' under the scene's own intrinsics, to float32's rounding
+    assert np.abs(pr.normalise(sc["k0"], sc["K0"]) - sc["q0"]).max() < 1e-6
+    inl = ~sc["outlier"]
+    assert np.abs(pr.normalise(sc["k1"], sc["K1"]) - sc["q1"])[inl].max() < 1e-6
+    seen = set()
+    for b in range(300):
+        for fx, fy, cx, cy in pr.pair_intrinsics(b):
+            assert 390 <= min(fx, fy) and max(fx, fy) <= 920 and max(fx, fy) / min(fx, fy) >= 1.1
+            assert 15 <= abs(cx - pr.CX) <= 45 and 15 <= abs(cy - pr.CY) <= 45
+            seen.add((fx, fy, cx, cy))
+    assert len(seen) == 600
+
+
+@pytest.mark.parametrize("name", ["intr0", "intr1", "intr2", "planar"])
+def test_restatement_finds_the_ground_truth_inliers_of_the_edge_scenes(name):
+    """chosen like clean30: the restatement's winner has exactly the ground truth's inliers, under the stream index the
+    GPU test estimates the scene at, and no match lies on the threshold"""
+    sc = pr.edge_scene(name)
+    b = pr.EDGE_SCENES[name]["pair"] if name.startswith("intr") else 0
+    q0, q1 = pr.normalise(sc["k0"], sc["K0"]), pr.normalise(sc["k1"], sc["K1"])
+    thr2 = pr.threshold2(sc["K0"], sc["K1"])
+    truth = pr.sampson(sc["E"].ravel(), q0, q1) < thr2
+    assert not pr.in_band(sc["E"], q0, q1, thr2).any()
+    assert truth.sum() >= (~sc["outlier"]).sum() and 0.25 < sc["outlier"].mean() < 0.4
+    # the two near-line matches: a threshold formed from either image's focal lengths alone decides one of them otherwise
+    for Ka in (sc["K0"], sc["K1"]) if name != "planar" else ():
+        assert not np.array_equal(pr.sampson(sc["E"].ravel(), q0, q1) < pr.threshold2(Ka, Ka), truth)
+    for roots in ("numpy", "dk"):
+        est = pr.estimate(sc["k0"], sc["k1"], sc["K0"], sc["K1"], seed=0, b=b, samples=256, roots=roots)
+        assert est["ok"] and np.array_equal(est["mask"], truth), roots
+        assert not pr.in_band(est["E"], q0, q1, thr2).any()
+        assert pr.rotation_angle_deg(est["R"], sc["R"]) < 0.01 and pr.vector_angle_deg(est["t"], sc["t"]) < 0.1
+    if name == "planar":
+        X = np.concatenate([sc["q0"], np.ones((len(q0), 1))], 1)
+        assert np.linalg.matrix_rank(np.concatenate([X / (X @ np.array(pr.PLANE))[:, None], np.ones((len(q0), 1))], 1), tol=1e-9) == 3
+
+
+def test_threshold_scene_tells_the_thresholds_apart():
+    sc = pr.edge_scene("thr")
+    q0, q1 = pr.normalise(sc["k0"], sc["K0"]), pr.normalise(sc["k1"], sc["K1"])
+    counts = []
+    for thr in pr.PIXEL_THRS:
+        thr2 = pr.threshold2(sc["K0"], sc["K1"], thr)
+        ests = [pr.estimate(sc["k0"], sc["k1"], sc["K0"], sc["K1"], seed=0, samples=256, pixel_thr=thr, roots=r) for r in ("numpy", "dk")]
+        for est in ests:
+            assert est["ok"] and not pr.in_band(est["E"], q0, q1, thr2).any()
+        assert np.array_equal(ests[0]["mask"], ests[1]["mask"])
+        counts.append(ests[0]["inliers"])
+    # of the six near-line matches one lies below 0.5 px, two more below 1 px, two more below 3 px
+    assert counts[1] - counts[0] == 2 and counts[2] - counts[1] == 2, counts
+
+
+@pytest.mark.parametrize("live", [(7, 298), (0,), (299,)])
+def test_sparse_batches_have_a_pose_in_every_live_pair(live):
+    k0, k1, bids, K0, K1, _ = pr.sparse_batch(300, live)
+    assert len(k0) == 40 and K0.shape == (300, 3, 3)
+    for b in live:
+        rows = bids == b
+        q0, q1 = pr.normalise(k0[rows], K0[b]), pr.normalise(k1[rows], K1[b])
+        ests = [pr.estimate(k0[rows], k1[rows], K0[b], K1[b], seed=4, b=b, samples=64, roots=r) for r in ("numpy", "dk")]
+        for est in ests:
+            assert est["ok"] and est["inliers"] >= 0.7 * rows.sum()
+            assert not pr.in_band(est["E"], q0, q1, pr.threshold2(K0[b], K1[b])).any()
+        assert np.array_equal(ests[0]["mask"], ests[1]["mask"])
+
+
+def test_degenerate_generators():
+    rot = pr.pure_rotation(90, 64)
+    assert not rot["t"].any() and not rot["E"].any() and not rot["T"][:3, 3].any()
+    h0 = np.concatenate([rot["q0"], np.ones((64, 1))], 1) @ rot["R"].T                 # q1 is the rotated ray, nothing else
+    assert np.abs(h0[:, :2] / h0[:, 2:] - rot["q1"]).max() < 1e-14
+    rep = pr.repeated(91, 64)
+    assert len(np.unique(rep["k0"], axis=0)) == 8 and np.array_equal(rep["k0"][:8], rep["k0"][8:16]) and len(rep["k1"]) == 64
+    one = pr.repeated(91, 64, distinct=1)
+    assert len(np.unique(np.hstack([one["k0"], one["k1"]]), axis=0)) == 1
+    assert not pr.estimate(one["k0"], one["k1"], one["K0"], one["K1"], samples=64)["ok"]
+
+
+def test_epipolar_yardsticks():
+    """the float64 formula and its float32 transcription against the oracle's float32 torch restatement (which
+    tests/test_oracle.py pins to the reference's fixture), in the measure the GPU tests use; the transcription's own error,
+    from which their c is taken; the exact case's float64 distances, small against the bound"""
+    from oracle import matcher_ref as orc
+    measured = pr.transcription_measure()
+    assert abs(measured - 0.6999) < 5e-4, measured           # the figure in the header of tests/test_gpu_post_edges.py
+    c = 4 * measured
+    for name in ("noisy", "exact"):
+        case = pr.epipolar_case(name)
+        d64, S, w = pr.epipolar_reference(name)
+        torch32 = orc.symmetric_epipolar_errors(*(torch.as_tensor(a) for a in case)).numpy()
+        assert pr.residual_measure(torch32, d64, S, w).max() <= c
+        plain = pr.epipolar_rows(pr.symmetric_epipolar, *case)
+        assert np.array_equal(plain, d64)
+    k0, k1, bids, T, K0, K1 = pr.epipolar_case("noisy")
+    assert np.bincount(bids).tolist() == [260, 300, 140] and len({K.tobytes() for K in list(K0) + list(K1)}) == 6
+    d64, S, w = pr.epipolar_reference("exact")
+    assert (np.sqrt(d64) <= 0.6 * pr.residual_bound(S, w, c)).all()
+    assert np.isnan(pr.epipolar_reference("rotation")[0]).all()
+    assert np.isnan(pr.epipolar_rows(pr.symmetric_epipolar_f32, *pr.epipolar_case("rotation"))).all()
+
+
 def test_estimate_pose_needs_five_matches():
     k = np.zeros((4, 2), np.float32)
     assert post.estimate_pose(k, k, np.eye(3), np.eye(3), 0.5, conf=0.99999) is None

@@ -388,7 +388,11 @@ int fm_fine_match(const float* win0, const float* win1, int m_max, const int32_t
  *                              d_mix0[r] = sum_m dq . win0[r,:],  d_mix0[WW] = sum_m sum_c dq
  *                            Outputs d_win0 / d_win1 [m_max, WW, Cf], d_mix0 / d_mix1 [WW+1] (weights, then bias), all
  *                            float32 [dev].  Rows at or beyond min(*d_count, m_max) (d_count may be NULL) get zero
- *                            gradients.  d_mix is reduced from per-match partials in a fixed order.  workspace:
+ *                            gradients and are never read (win0, win1, d_out0, d_out1 may hold anything there); a
+ *                            negative *d_count counts as 0.  With a count of 0 (or below) every d_win row is zero and
+ *                            d_mix0 / d_mix1 are all zero.  A *d_count above m_max counts as m_max.  What the counted
+ *                            rows get, and d_mix, are bit for bit what the call on those rows alone gives.
+ *                            d_mix is reduced from per-match partials in a fixed order.  workspace:
  *                            fm_fine_match_backward_workspace_bytes(m_max, WW) bytes [dev], 256-byte aligned.
  *                            Cf = 64, WW in {25, 49} (else FM_E_UNSUPPORTED); m_max = 0: returns at once, nothing written.
  *   fm_gather_windows_backward : the adjoint of fm_gather_windows.  d_win [dev] float32 [m_max, W*W, Cf]; b_ids / ids as

@@ -1,6 +1,6 @@
 """float64 restatements of the fine stage (fine_matching_new.py:50-79) and of the backward formula the HIP kernels
-implement (include/fmatch.h, fm_fine_match_backward): the yardsticks of tests/test_fine_grad_abi.py and
-tests/test_gpu_fine_grad.py."""
+implement (include/fmatch.h, fm_fine_match_backward): the yardsticks of tests/test_fine_grad_abi.py,
+tests/test_gpu_fine_grad.py and tests/test_gpu_fine_backward.py."""
 import math
 
 import torch
@@ -109,14 +109,15 @@ FINE_TIED = 300         # the first rows have win1 = 3 * win0 (the recipe of tes
 FINE_SCALE = 2.0
 
 
-def regime_inputs(w: int, gain: float, m: int = FINE_M):
-    """(win0, win1, mix0, mix1) float32 on the CPU, seeded by (W, gain): windows gain * N(0, 1), the first FINE_TIED
-    rows with win1 = 3 * win0, mix = [WW + 1] uniform in +-1/sqrt(WW) (torch's init range of Linear(WW, 1))"""
+def regime_inputs(w: int, gain: float, m: int = FINE_M, tied: int = FINE_TIED):
+    """(win0, win1, mix0, mix1) float32 on the CPU, seeded by (W, gain): windows gain * N(0, 1), the first `tied`
+    rows with win1 = 3 * win0, mix = [WW + 1] uniform in +-1/sqrt(WW) (torch's init range of Linear(WW, 1)).
+    tests/test_fine_ref.py holds the bits of the default call to a digest"""
     ww = w * w
     g = torch.Generator().manual_seed(1000 * w + int(round(gain * 100)))
     win0 = gain * torch.randn(m, ww, 64, generator=g)
     win1 = gain * torch.randn(m, ww, 64, generator=g)
-    win1[:FINE_TIED] = 3 * win0[:FINE_TIED]
+    win1[:tied] = 3 * win0[:tied]
     mix0, mix1 = ((2 * torch.rand(ww + 1, generator=g) - 1) / math.sqrt(ww) for _ in range(2))
     return win0, win1, mix0, mix1
 
@@ -186,6 +187,95 @@ def fine_backward(win0, win1, mix0, mix1, scale, d_out0, d_out1):
         d_mix[d][:ww] += torch.einsum('mc,mrc->r', dq, wa)
         d_mix[d][ww] += dq.sum()
     return d_win[0], d_win[1], d_mix[0], d_mix[1]
+
+
+# ---- the cases of the fine backward's accuracy test (tests/test_gpu_fine_backward.py runs them on the device,
+# tests/test_fine_ref.py asserts from the CPU what that file assumes about them).  A case is (W, gain, target, M):
+# regime_inputs(W, gain, m=M, tied=M // 2), so a small M holds tied and free rows, and a d_out seeded by (W, M).
+BWD_TARGETS = ("xy", "std", "all")      # d_out with std column 0 / with x, y columns 0 / all three columns non-zero
+BWD_GAINS = (0.02, 0.3, 1.0)
+BWD_M = 600
+# scale_f per (W, gain): each of 1, 2, 4 meets every target, as the targets are crossed with (W, gain)
+BWD_SCALE = {(5, 0.02): 1.0, (5, 0.3): 2.0, (5, 1.0): 4.0, (7, 0.02): 2.0, (7, 0.3): 4.0, (7, 1.0): 1.0}
+BWD_REGULAR = [(w, gain, target, BWD_M) for w in (5, 7) for gain in BWD_GAINS for target in BWD_TARGETS]
+# either side of the four matches of a workgroup of k_fine_bwd, of a wave and of the 256-match stride of
+# k_fine_mix_reduce, two and four strides
+BWD_EDGE_M = (1, 2, 3, 4, 5, 7, 8, 9, 63, 64, 65, 255, 256, 257, 513, 1025)
+BWD_EDGES = [(w, 0.3, "all", m) for w in (5, 7) for m in BWD_EDGE_M]
+BWD_NAMES = ("d_win0", "d_win1", "d_mix0", "d_mix1")
+# twice the largest e32_m / top_m of torch's float32 autograd over BWD_REGULAR (4.90e-6: W = 5, gain 1.0, std, d_win1),
+# measured on the CPU by tests/test_fine_ref.py: profiles/fine_backward_accuracy.txt
+BWD_FLOOR = 2 * 4.90e-6
+
+
+def backward_d_out(w: int, m: int, target: str):
+    """(d_out0, d_out1) float32 [M, 3] = N(0, 1), seeded by (W, M); the columns the target leaves out are zero"""
+    g = torch.Generator().manual_seed(77 * w + m)
+    d = [torch.randn(m, 3, generator=g), torch.randn(m, 3, generator=g)]
+    for t in d:
+        if target == "xy":
+            t[:, 2] = 0
+        elif target == "std":
+            t[:, :2] = 0
+        else:
+            assert target == "all" and (t != 0).all()
+    return d[0], d[1]
+
+
+def backward_inputs(w: int, gain: float, target: str, m: int):
+    """(win0, win1, mix0, mix1, d_out0, d_out1, scale_f) of a case, float32 on the CPU"""
+    return (*regime_inputs(w, gain, m=m, tied=m // 2), *backward_d_out(w, m, target), BWD_SCALE.get((w, gain), FINE_SCALE))
+
+
+def backward_autograd(win0, win1, mix0, mix1, d_out0, d_out1, scale, dtype, fn=fine_forward, device="cpu"):
+    """[d_win0, d_win1, d_mix0, d_mix1] of fn (fine_forward, or a drop-in for it) under autograd in `dtype` on
+    `device`, mkpts_c = 0, in the leaves' dtype"""
+    leaves = [t.detach().to(device, dtype).clone().requires_grad_(True) for t in (win0, win1, mix0, mix1)]
+    z = torch.zeros(win0.shape[0], 2, device=device, dtype=dtype)
+    outs = fn(*leaves, z, z, scale)
+    return list(torch.autograd.grad(outs, leaves, [d_out0.to(device, dtype), d_out1.to(device, dtype)]))
+
+
+def backward_yardstick(w: int, gain: float, target: str, m: int):
+    """(g64, g32, var64 [M, 4], var_bar) of a case: the gradients of fine_forward under float64 and under float32
+    autograd on the CPU (both as float64 tensors), the float64 variances and the variance bar of fine_bars (mult * d0
+    + 4 ulp, d0 = the float32 forward's own largest variance error on this case) that tests/test_gpu_fine_forward.py
+    holds the kernel's variances within - 0 for target xy, whose gradient does not pass through a variance.  Nothing
+    here comes from a kernel"""
+    inp = backward_inputs(w, gain, target, m)
+    g64 = backward_autograd(*inp, torch.float64)
+    g32 = [t.double() for t in backward_autograd(*inp, torch.float32)]
+    _, var64, e32, d0 = fine_yardstick(*inp[:4], scale=inp[6])
+    return g64, g32, var64, (0.0 if target == "xy" else fine_bars(w, e32, d0, scale=inp[6])[1])
+
+
+def backward_bars(g64, g32, var64, var_bar, floor=BWD_FLOOR, mult=FINE_MULT):
+    """(bar, top, e32) [M] per match of a window gradient [M, WW, C]:
+        bar_m = mult * e32_m + (floor + COND_m) * top_m,  top_m = max |g64[m]|,  e32_m = max |g32[m] - g64[m]|
+    COND_m = var_bar / (2 vmin_m), vmin_m = the smallest of match m's four float64 variances: the kernel's variances
+    are within var_bar of float64 and d sqrt(var) = g / (2 sqrt(var)) inherits half their relative error.  var_bar = 0
+    (target xy: no std gradient) leaves COND out"""
+    top = g64.abs().flatten(1).amax(1)
+    e32 = (g32 - g64).abs().flatten(1).amax(1)
+    cond = var_bar / (2 * var64.amin(1))
+    return mult * e32 + (floor + cond) * top, top, e32
+
+
+def backward_mix_bars(g64, g32, var64, var_bar, floor=BWD_FLOOR, mult=FINE_MULT):
+    """(bar, top, e32) per entry of a mix gradient [WW + 1]: the same form with top = max |g64| over the tensor (a
+    scalar), e32 per entry and COND at the smallest variance of the case"""
+    top = g64.abs().max()
+    e32 = (g32 - g64).abs()
+    cond = var_bar / (2 * var64.min())
+    return mult * e32 + (floor + cond) * top, top, e32
+
+
+def backward_excess(name, got, g64, g32, var64, var_bar):
+    """(|got - g64| per match or per entry, its bar, e32) of tensor `name` of BWD_NAMES; got as float64 on the CPU"""
+    bars = backward_bars if name.startswith("d_win") else backward_mix_bars
+    bar, _, e32 = bars(g64, g32, var64, var_bar)
+    err = (got - g64).abs()
+    return (err.flatten(1).amax(1) if name.startswith("d_win") else err), bar, e32
 
 
 # (Cf, W, stride, pad) of the general crop tests (tests/test_crop_ref.py pins the yardsticks at these,

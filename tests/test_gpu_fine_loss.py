@@ -21,7 +21,9 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 FLOOR = 2 * 1.15e-7        # profiles/fine_loss_accuracy.txt: the largest e_ref / |loss64| over the inputs of tests/test_gpu_fine_loss.py
 GTOL = 4 * 1.85e-7         # profiles/fine_loss_accuracy.txt: the largest float32 autograd error / max|g64| over the same inputs
-SIZES = (1, 2, 63, 64, 65, 257, 4097)          # below / at / above a wave and a workgroup, several workgroups
+# below / at / above a wave and a workgroup, several workgroups; 70001: k_floss_partial caps its grid at 256 workgroups,
+# so above 65 536 rows its grid-stride loop takes a second trip (in the first 4465 threads only)
+SIZES = (1, 2, 63, 64, 65, 257, 4097, 70001)
 CASES = [f"m{m}" for m in SIZES] + ["clamp"]
 
 
@@ -83,7 +85,9 @@ def _assert_close(case, got, ref64, ref32, scale=1.0):
         top = r.abs().max().item()
         assert top > 0 and (g.double() / scale - r).abs().max().item() <= GTOL * top, case
         assert g.dtype == torch.float32 and g[:, 2].abs().max().item() == 0          # the weights are detached
-        assert (g[r[:, 0] == 0][:, :2] == 0).all()                                     # rows left out: exactly zero
+        # rows left out: exactly zero.  They are the rows whose reference gradient is zero in x AND y; x alone does not
+        # tell (m70001, row 4802 of image 0: expec x == gt x in float32, the row takes part and has a y gradient)
+        assert (g[(r[:, :2] == 0).all(1)][:, :2] == 0).all()
 
 
 @pytest.mark.parametrize("case", CASES)

@@ -576,6 +576,19 @@ int fm_epipolar_errors(const float* mkpts0, const float* mkpts1, int kpt_stride,
  *                               fm_dual_softmax_backward_workspace_bytes bytes [dev], 256-byte aligned.  feat0 / feat1
  *                               float32.  Entries sharing a row or a column are added with float atomics (the order of
  *                               their additions is the only non-deterministic part).
+ * What tests/test_gpu_dsm_grad.py establishes about these calls and the coarse loss below, with statistics made by the caller:
+ *   - pitch_r >= L and pitch_c >= S may be any such value, the two independently; positions L .. pitch_r - 1 and S ..
+ *     pitch_c - 1 of a row of the statistics are never read (they may hold NaN).  A smaller pitch is FM_E_SHAPE.
+ *   - the statistics need not come from fm_coarse_match: any (nm, sum) with exp2(-nm) sum the softmax denominator serves,
+ *     and a relative error delta of the denominators reaches the gradients as at most ~4 delta of the summed terms'
+ *     magnitude (not of the gradient: on saturated problems the gradient is the small residue of those terms).
+ *   - fm_dual_softmax_backward adds a triple once per time it is listed (three times the same (b, i, j, gc) = once with
+ *     3 gc); entries with distinct rows and columns give the same bits on every call.  The coarse loss wants DISTINCT triples.
+ *   - K = 0: fm_dual_softmax_conf_at returns FM_OK and writes nothing; fm_dual_softmax_backward writes exact zeros to all
+ *     of d_feat0 / d_feat1 and does not look at the id and gc pointers.  A sample of the batch without an entry gets
+ *     exact zeros; so does every call of fm_dual_softmax_backward_dense with G = 0.
+ *   - nothing outside the buffers, the outputs and the stated workspace bytes is read or written; the workspace may hold
+ *     anything on entry.
  */
 int fm_coarse_softmax_stats(void* workspace, int N, int L, int S, int C, int cand_slots, const float** nm_r,
                             const float** sum_r, int* pitch_r, const float** nm_c, const float** sum_c, int* pitch_c);

@@ -27,7 +27,7 @@
 //     A slab is [8][33][32] floats per sample: rows 0..31 of a head the matrix, row 32 the vector.
 // No atomics: every sum has one owner and a fixed order, so every output is the same bits on every run.
 #include "fm_internal.h"
-#include "fm_wave_device.h"
+#include "fm_tile_device.h"
 
 namespace fm {
 
@@ -242,20 +242,12 @@ __global__ __launch_bounds__(256) void k_la_kv_part(const float* __restrict__ k,
   o[32 * 32] = ks;
 }
 
-// dst[n] = sum over the n_part slabs of part[n], in a fixed order: 32 entries per workgroup, slice j = tid >> 5 of its 8
-// adds slabs j, j + 8, ... in index order (8 short chains of loads in place of one long one), then the 8 slices in index
-// order
+// dst[n] = sum over the n_part slabs of part[n] (fold_slabs' order, fm_tile_device.h)
 __global__ __launch_bounds__(256) void k_la_fold(const float* __restrict__ part, int n_part, float* __restrict__ dst) {
   __shared__ float red[8][32];
-  const int x = threadIdx.x & 31, j = threadIdx.x >> 5, i = blockIdx.x * 32 + x, n = blockIdx.y;
-  const float* p = part + (size_t)n * n_part * kLaSlab + i;
-  float s = 0.f;
-#pragma unroll 4
-  for (int c = j; c < n_part; c += 8) s += p[(size_t)c * kLaSlab];
-  red[j][x] = s;
-  __syncthreads();
-  if (j == 0)
-    dst[(size_t)n * kLaSlab + i] = ((((((red[0][x] + red[1][x]) + red[2][x]) + red[3][x]) + red[4][x]) + red[5][x]) + red[6][x]) + red[7][x];
+  const int x = threadIdx.x & 31, i = blockIdx.x * 32 + x, n = blockIdx.y;
+  float v;
+  if (fold_slabs(part + (size_t)n * n_part * kLaSlab + i, n_part, kLaSlab, red, &v)) dst[(size_t)n * kLaSlab + i] = v;
 }
 
 // out: thread (h, x) holds column x of A and Ksum[x]; the denominator is the one 32-lane sum per token and head

@@ -8,116 +8,38 @@
 //     d_feat       = crop adjoint of (g Ww)
 // Every product runs on v_mfma_f32_32x32x2_f32: exact float32, one rounding per product, a k-ordered fmaf chain.
 //
-// Tiling: qkv_proj.hip's.  A token is one (m, r) pair, T = m_max W W of them; a wave owns 32 consecutive tokens, the
-// token on the lane (lane & 31), a token's 64 channels in 32 registers of the lanes `lane` and `lane ^ 32` ("layout L":
-// register R of lane half h <-> channel 8 (R >> 2) + 4 h + (R & 3)).  The products are computed transposed,
-// out^T [channel][token] = M [out][in] in^T; k_wm_pack writes M = Ww (forward) or Ww^T (backward) as A-operand
-// fragments [out tile][R >> 2][lane][R & 3] once per call.
+// Tiling: fm_tile_device.h's (layout L, fragments, the exchange image).  A token is one (m, r) pair, T = m_max W W of
+// them; a wave owns 32 consecutive tokens.  k_wm_pack writes M = Ww (forward) or Ww^T (backward) as fragments once per call.
 // The loader (wm_crop) is the crop: a lane's token gives (b, y0 + r / W, x0 + r % W); NCHW reads one float per register
 // and lane - the 32 lanes of a register's load walk runs of W consecutive pixels of one channel plane - channels-last
-// reads the token's 256-byte record as 16-byte pieces, as qp_load does.  A pixel outside the map, a row whose sample or
+// reads the token's 256-byte record as 16-byte pieces, as tile_load does.  A pixel outside the map, a row whose sample or
 // cell lies outside the batch or the grid (the crop's adjoint leaves such a row out as well) and a token past T read 0.
 //   k_wm_fwd  : 8 waves; the fragments (16 KB) in LDS; writes out alone.
 //   k_wm_bwd  : 4 waves; fragments from L2.  g Ww goes to the workspace as [m_max, WW, 64]: the map's gradient is
 //     fm_gather_windows_backward (fine_grad.hip: CSR of matches per cell, one wave per pixel, a fixed order) on it.  The
-//     weight gradient sums over TOKENS, which sit on lanes: each wave writes g and the cropped window transposed into an
-//     LDS image [channel][token] (128 rows of 33 floats per wave) and, between two barriers, every wave multiplies ITS
-//     tile (wave >> 1, wave & 1) of d_Ww over all four images.  Per workgroup one slab of partial sums; k_wm_fold adds
-//     the slabs in a fixed order.  WGRAD = false: no crop, no exchange, no barriers, no LDS.  DATA = false (d_feat ==
-//     NULL): no product, no g Ww, no crop backward.
+//     weight gradient: each wave writes g and the cropped window into its image (128 rows per wave) and every wave
+//     multiplies ITS tile (wave >> 1, wave & 1) of d_Ww over all four images; k_wm_fold adds the workgroups' slabs.
+//     WGRAD = false: no crop, no exchange, no barriers, no LDS.  DATA = false (d_feat == NULL): no product, no g Ww, no
+//     crop backward.
 //   k_wm_dctx : one wave per match at a time, lane = channel, r ascending: one owner per row.
 // No float atomics, grids that depend on the arguments alone (at most 256 workgroups, a grid stride over the chunks),
 // fixed summation orders: the same inputs give the same bits.
 #include "fm_internal.h"
-#include "fm_wave_device.h"
+#include "fm_tile_device.h"
 
 namespace fm {
 
-constexpr int kWmTile = 32;                      // tokens of a wave's tile (the N of the MFMA)
-constexpr int kWmFwdWaves = 8, kWmFwdChunk = kWmFwdWaves * kWmTile;     // 256 tokens per workgroup and round
-constexpr int kWmBwdWaves = 4, kWmBwdChunk = kWmBwdWaves * kWmTile;     // 128
-constexpr int kWmMaxGroups = 256;                // workgroups of either kernel (one per CU; the rest by grid stride)
-constexpr int kWmMaxT = 1 << 24;                 // tokens of one call (fmatch.h)
 constexpr int kWmMat = 4096;                     // floats of the 64 x 64 matrix: its fragments, a slab of partial sums
-constexpr int kWmPitch = 33, kWmImage = 128 * kWmPitch;      // floats of an exchange row / of a wave's image
+constexpr int kWmImage = 128 * kTilePitch;       // floats of a wave's image
 constexpr int kWmFwdLds = kWmMat * 4;
-constexpr int kWmBwdLds = kWmBwdWaves * kWmImage * 4;
+constexpr int kWmBwdLds = kTileBwdWaves * kWmImage * 4;
 static_assert(kWmMat % 32 == 0, "k_wm_fold's grid covers a slab exactly");
 static_assert(kWmBwdLds <= 160 * 1024 && kWmFwdLds <= 160 * 1024, "one workgroup per CU");
 
-// frag[idx], [ot][q][lane][e] = M[32 ot + (lane & 31)][8 q + 4 (lane >> 5) + e], M = Ww (tr = 0) or Ww^T (tr = 1)
+// the fragments of M = Ww (tr = 0) or Ww^T (tr = 1)
 __global__ __launch_bounds__(256) void k_wm_pack(const float* __restrict__ w, int tr, float* __restrict__ frag) {
   const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= kWmMat) return;
-  const int e = i & 3, lane = (i >> 2) & 63, rest = i >> 8;
-  const int row = 32 * (rest >> 3) + (lane & 31), col = 8 * (rest & 7) + 4 * (lane >> 5) + e;
-  frag[i] = tr ? w[col * 64 + row] : w[row * 64 + col];
-}
-
-// 0, but not to the compiler: added to the base of the fragments once per round of the token loop, it keeps their loads -
-// the same addresses in every round - from being hoisted out of the loop and spilled (encoder_tail.hip's note)
-__device__ __forceinline__ int wm_opaque_zero() {
-  int z = 0;
-  asm volatile("" : "+s"(z));
-  return z;
-}
-
-// acc[ot] = rows 32 ot .. of M in^T for the wave's 32 tokens; in[R] in layout L.  The fragments of group q + 2 are
-// requested before the products of group q and nothing crosses a group's end (sched_barrier), so that loads from L2
-// stay two groups ahead of their use.
-__device__ __forceinline__ void wm_mm(const float4* __restrict__ F, const float (&in)[32], f32x16 (&acc)[2], int lane) {
-#pragma unroll
-  for (int ot = 0; ot < 2; ++ot)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[ot][r] = 0.f;
-  constexpr int NQ = 8, AHEAD = 2;
-  float4 w[AHEAD + 1][2];
-#pragma unroll
-  for (int q = 0; q < AHEAD; ++q)
-#pragma unroll
-    for (int ot = 0; ot < 2; ++ot) w[q][ot] = F[(ot * NQ + q) * 64 + lane];
-#pragma unroll
-  for (int q = 0; q < NQ; ++q) {
-    if (q + AHEAD < NQ) {
-#pragma unroll
-      for (int ot = 0; ot < 2; ++ot) w[(q + AHEAD) % (AHEAD + 1)][ot] = F[(ot * NQ + q + AHEAD) * 64 + lane];
-    }
-#pragma unroll
-    for (int ot = 0; ot < 2; ++ot) {
-      const float4 f = w[q % (AHEAD + 1)][ot];
-      acc[ot] = __builtin_amdgcn_mfma_f32_32x32x2f32(f.x, in[4 * q], acc[ot], 0, 0, 0);
-      acc[ot] = __builtin_amdgcn_mfma_f32_32x32x2f32(f.y, in[4 * q + 1], acc[ot], 0, 0, 0);
-      acc[ot] = __builtin_amdgcn_mfma_f32_32x32x2f32(f.z, in[4 * q + 2], acc[ot], 0, 0, 0);
-      acc[ot] = __builtin_amdgcn_mfma_f32_32x32x2f32(f.w, in[4 * q + 3], acc[ot], 0, 0, 0);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-  }
-}
-
-// rows t0 .. t0 + 31 of a [T, 64] tensor <-> layout L; rows past T read as 0 and are not written
-__device__ __forceinline__ void wm_load(const float* __restrict__ p, size_t t0, int T, int lane, float* __restrict__ v) {
-  const size_t tok = t0 + (lane & 31);
-  const bool live = tok < (size_t)T;
-  const float4* s = reinterpret_cast<const float4*>(p + tok * 64 + 4 * (lane >> 5));
-#pragma unroll
-  for (int q = 0; q < 8; ++q) {
-    const float4 r = live ? s[2 * q] : make_float4(0.f, 0.f, 0.f, 0.f);
-    v[4 * q] = r.x; v[4 * q + 1] = r.y; v[4 * q + 2] = r.z; v[4 * q + 3] = r.w;
-  }
-}
-// the two tiles of an accumulator (+ the 64 floats at `bias`, if given: the lane's pieces of them) -> row tok of [T, 64]
-__device__ __forceinline__ void wm_store(float* __restrict__ p, size_t tok, bool live, int lane, const float* __restrict__ bias,
-                                         const f32x16& a, const f32x16& b) {
-  if (!live) return;
-  float4* s = reinterpret_cast<float4*>(p + tok * 64 + 4 * (lane >> 5));
-  const float4* c = reinterpret_cast<const float4*>(bias ? bias + 4 * (lane >> 5) : nullptr);
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const float4 lo = bias ? c[2 * q] : make_float4(0.f, 0.f, 0.f, 0.f);
-    const float4 hi = bias ? c[2 * q + 8] : make_float4(0.f, 0.f, 0.f, 0.f);
-    s[2 * q] = make_float4(a[4 * q] + lo.x, a[4 * q + 1] + lo.y, a[4 * q + 2] + lo.z, a[4 * q + 3] + lo.w);
-    s[2 * q + 8] = make_float4(b[4 * q] + hi.x, b[4 * q + 1] + hi.y, b[4 * q + 2] + hi.z, b[4 * q + 3] + hi.w);
-  }
+  if (i < kWmMat) frag[i] = frag_value(w, 64, 64, tr != 0, i);
 }
 
 // the map and the grid of one call
@@ -159,106 +81,76 @@ __device__ __forceinline__ void wm_crop(const WmMap& g, size_t tok, bool live, i
 }
 
 template <int W>
-__global__ __launch_bounds__(kWmFwdWaves * 64) void k_wm_fwd(WmMap g, const float* __restrict__ frag,
-                                                             const float* __restrict__ ctx, int T, float* __restrict__ out) {
+__global__ __launch_bounds__(kTileFwdWaves * 64) void k_wm_fwd(WmMap g, const float* __restrict__ frag,
+                                                               const float* __restrict__ ctx, int T, float* __restrict__ out) {
   extern __shared__ __attribute__((aligned(16))) float wm_lds[];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  for (int i = tid; i < kWmMat / 4; i += kWmFwdWaves * 64)
+  for (int i = tid; i < kWmMat / 4; i += kTileFwdWaves * 64)     // (written out: a helper moves the loop in the kernel)
     reinterpret_cast<float4*>(wm_lds)[i] = reinterpret_cast<const float4*>(frag)[i];
   __syncthreads();
   const float4* F0 = reinterpret_cast<const float4*>(wm_lds);
-  const int chunks = (T + kWmFwdChunk - 1) / kWmFwdChunk;
+  const int chunks = (T + kTileFwdChunk - 1) / kTileFwdChunk;
   for (int ch = blockIdx.x; ch < chunks; ch += gridDim.x) {
-    const size_t t0 = (size_t)ch * kWmFwdChunk + wave * kWmTile;
+    const size_t t0 = (size_t)ch * kTileFwdChunk + wave * kTile;
     if (t0 >= (size_t)T) continue;
     const size_t tok = t0 + (lane & 31);
     const bool live = tok < (size_t)T;
-    const float4* F = F0 + wm_opaque_zero();
+    const float4* F = F0 + opaque_zero();
     float in[32];
     wm_crop<W>(g, tok, live, lane, in);
     f32x16 acc[2];
-    wm_mm(F, in, acc, lane);
-    wm_store(out, tok, live, lane, live ? ctx + (tok / (W * W)) * 64 : nullptr, acc[0], acc[1]);
+    tile_mm<2, 32>(F, in, acc, lane);
+    tile_store(out, tok, live, lane, live ? ctx + (tok / (W * W)) * 64 : nullptr, acc[0], acc[1]);
   }
-}
-
-// the wave's image: row (row0 + channel) <- v (32 registers in layout L), column = token
-__device__ __forceinline__ void wm_put(float* __restrict__ E, int row0, int lane, const float* __restrict__ v) {
-  float* e = E + (row0 + 4 * (lane >> 5)) * kWmPitch + (lane & 31);
-#pragma unroll
-  for (int R = 0; R < 32; ++R) e[(8 * (R >> 2) + (R & 3)) * kWmPitch] = v[R];
-}
-// acc[out][in] += sum over the chunk's 128 tokens of rows rowA.. (out) times rows rowB.. (in): the waves' images in index
-// order, the tokens of each in order
-__device__ __forceinline__ void wm_wgrad(const float* __restrict__ E, int rowA, int rowB, int lane, f32x16& acc) {
-  const int at = (lane & 31) * kWmPitch + (lane >> 5);
-  for (int w = 0; w < kWmBwdWaves; ++w) {
-    const float* pa = E + w * kWmImage + rowA * kWmPitch + at;
-    const float* pb = E + w * kWmImage + rowB * kWmPitch + at;
-#pragma unroll 4
-    for (int s = 0; s < kWmTile / 2; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(pa[2 * s], pb[2 * s], acc, 0, 0, 0);
-  }
-}
-// tile -> slab: D[i][j] at col j = lane & 31, row i = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
-__device__ __forceinline__ void wm_tile_out(float* __restrict__ dst, int lane, const f32x16& acc) {
-#pragma unroll
-  for (int r = 0; r < 16; ++r) dst[((r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * 64 + (lane & 31)] = acc[r];
 }
 
 // WGRAD = false: g Ww only - no crop, no exchange, no barriers, no LDS, `part` unused.  DATA = false (the map wants no
 // gradient): no product, `frag` and `gw` unused.
 template <int W, bool WGRAD, bool DATA>
-__global__ __launch_bounds__(kWmBwdWaves * 64) void k_wm_bwd(WmMap g, const float* __restrict__ frag,
-                                                             const float* __restrict__ grad, int T, float* __restrict__ gw,
-                                                             float* __restrict__ part) {
-  extern __shared__ __attribute__((aligned(16))) float wm_lds[];     // [wave][128 rows][kWmPitch]
+__global__ __launch_bounds__(kTileBwdWaves * 64) void k_wm_bwd(WmMap g, const float* __restrict__ frag,
+                                                               const float* __restrict__ grad, int T, float* __restrict__ gw,
+                                                               float* __restrict__ part) {
+  extern __shared__ __attribute__((aligned(16))) float wm_lds[];     // [wave][128 rows][kTilePitch]
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const float4* F0 = reinterpret_cast<const float4*>(frag);
-  f32x16 wacc;                                                       // this wave's tile of d_Ww
+  f32x16 wacc[1];                                                    // this wave's tile of d_Ww
 #pragma unroll
-  for (int r = 0; r < 16; ++r) wacc[r] = 0.f;
-  const int chunks = (T + kWmBwdChunk - 1) / kWmBwdChunk;
+  for (int r = 0; r < 16; ++r) wacc[0][r] = 0.f;
+  const int chunks = (T + kTileBwdChunk - 1) / kTileBwdChunk;
   for (int ch = blockIdx.x; ch < chunks; ch += gridDim.x) {
-    const size_t t0 = (size_t)ch * kWmBwdChunk + wave * kWmTile;     // past T in the last chunk: a tile of zeros
+    const size_t t0 = (size_t)ch * kTileBwdChunk + wave * kTile;     // past T in the last chunk: a tile of zeros
     const size_t tok = t0 + (lane & 31);
     const bool live = tok < (size_t)T;
-    const float4* F = F0 + wm_opaque_zero();
+    const float4* F = F0 + opaque_zero();
     float gv[32];
-    wm_load(grad, t0, T, lane, gv);
+    tile_load(grad, t0, T, lane, gv);
     if (WGRAD) {
       float vin[32];
       wm_crop<W>(g, tok, live, lane, vin);
       float* Ew = wm_lds + wave * kWmImage;
-      wm_put(Ew, 0, lane, gv);
-      wm_put(Ew, 64, lane, vin);
+      tile_put<32>(Ew, 0, lane, gv);
+      tile_put<32>(Ew, 64, lane, vin);
     }
     if (DATA) {
       f32x16 acc[2];
-      wm_mm(F, gv, acc, lane);
-      wm_store(gw, tok, live, lane, nullptr, acc[0], acc[1]);
+      tile_mm<2, 32>(F, gv, acc, lane);
+      tile_store(gw, tok, live, lane, nullptr, acc[0], acc[1]);      // (+ 0 as it was: -0 is stored as +0)
     }
     if (WGRAD) {
       __syncthreads();
-      wm_wgrad(wm_lds, 32 * (wave >> 1), 64 + 32 * (wave & 1), lane, wacc);
+      tile_wgrad<1, kTileBwdWaves, kWmImage>(wm_lds, 32 * (wave >> 1), 64 + 32 * (wave & 1), lane, wacc);
       __syncthreads();
     }
   }
-  if (WGRAD) wm_tile_out(part + (size_t)blockIdx.x * kWmMat + 32 * (wave >> 1) * 64 + 32 * (wave & 1), lane, wacc);
+  if (WGRAD) tile_out(part + (size_t)blockIdx.x * kWmMat + 32 * (wave >> 1) * 64 + 32 * (wave & 1), 64, lane, wacc[0]);
 }
 
-// d_Ww = the sum of the n_part slabs, in a fixed order (k_qp_fold's: 8 slices of every 8th slab, then the slices in
-// index order)
+// d_Ww = the sum of the n_part slabs (fold_slabs' order)
 __global__ __launch_bounds__(256) void k_wm_fold(const float* __restrict__ part, int n_part, float* __restrict__ d_w) {
   __shared__ float red[8][32];
-  const int x = threadIdx.x & 31, j = threadIdx.x >> 5, i = blockIdx.x * 32 + x;
-  const float* p = part + i;
-  float s = 0.f;
-#pragma unroll 4
-  for (int c = j; c < n_part; c += 8) s += p[(size_t)c * kWmMat];
-  red[j][x] = s;
-  __syncthreads();
-  if (j != 0) return;
-  d_w[i] = ((((((red[0][x] + red[1][x]) + red[2][x]) + red[3][x]) + red[4][x]) + red[5][x]) + red[6][x]) + red[7][x];
+  const int x = threadIdx.x & 31, i = blockIdx.x * 32 + x;
+  float v;
+  if (fold_slabs(part + i, n_part, kWmMat, red, &v)) d_w[i] = v;
 }
 
 // d_ctx[m][lane] = sum_r g[m][r][lane], r ascending
@@ -274,14 +166,10 @@ __global__ __launch_bounds__(256) void k_wm_dctx(const float* __restrict__ grad,
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------
-static int wm_groups(long T, int chunk) {
-  const long c = (T + chunk - 1) / chunk;
-  return (int)(c < kWmMaxGroups ? c : kWmMaxGroups);
-}
 // what the workspace query knows of a call: the batch, the grid, the list and the window
 static bool wm_sizes_ok(int N, int h_c, int w_c, int m_max, int W) { return N > 0 && h_c > 0 && w_c > 0 && m_max >= 0 && W > 0; }
 static bool wm_route(int N, int h_c, int w_c, int m_max, int W) {
-  return (W == 5 || W == 7) && (long)m_max * W * W <= kWmMaxT && (long)N * h_c * w_c < (1L << 31) - 1;
+  return (W == 5 || W == 7) && (long)m_max * W * W <= kTileMaxT && (long)N * h_c * w_c < (1L << 31) - 1;
 }
 // Workspace of either call: the fragments of Ww, then of Ww^T | one slab per workgroup of the backward | g Ww
 // [m_max, WW, 64] | the crop backward's own workspace (its CSR)
@@ -291,7 +179,7 @@ static WmWs wm_layout(int N, int h_c, int w_c, int m_max, int W) {
   Carver c;
   const size_t T = (size_t)m_max * W * W;
   c.take(w.frag, 2 * kWmMat);
-  c.take(w.part, (size_t)wm_groups((long)T, kWmBwdChunk) * kWmMat);
+  c.take(w.part, (size_t)token_groups((long)T, kTileBwdChunk) * kWmMat);
   c.take(w.gw, T * 64);
   w.crop_bytes = fm_gather_windows_backward_workspace_bytes(N, h_c, w_c, m_max);
   c.take(w.crop, w.crop_bytes);
@@ -331,14 +219,14 @@ static int wm_launch(const WmCall& c, const WmWs& w, const WmMap& map, int T, hi
     static unsigned long long lds_fwd = 0;
     const hipError_t e = ensure_dynamic_lds(k_wm_fwd<W>, kWmFwdLds, &lds_fwd);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(k_wm_fwd<W>, dim3(wm_groups(T, kWmFwdChunk)), dim3(kWmFwdWaves * 64), kWmFwdLds, st, map,
+    hipLaunchKernelGGL(k_wm_fwd<W>, dim3(token_groups(T, kTileFwdChunk)), dim3(kTileFwdWaves * 64), kWmFwdLds, st, map,
                        (const float*)frag, c.ctx, T, c.out);
     return (int)hipGetLastError();
   }
-  const int groups = wm_groups(T, kWmBwdChunk);
+  const int groups = token_groups(T, kTileBwdChunk);
   float* part = w.part.in(c.workspace);
   float* gw = w.gw.in(c.workspace);
-  const dim3 grid(groups), block(kWmBwdWaves * 64);
+  const dim3 grid(groups), block(kTileBwdWaves * 64);
   if (c.d_w_win) {
     static unsigned long long lds_data = 0, lds_only = 0;
     const hipError_t e = c.d_feat ? ensure_dynamic_lds(k_wm_bwd<W, true, true>, kWmBwdLds, &lds_data)
@@ -353,7 +241,7 @@ static int wm_launch(const WmCall& c, const WmWs& w, const WmMap& map, int T, hi
     hipLaunchKernelGGL((k_wm_bwd<W, false, true>), grid, block, 0, st, map, (const float*)frag, c.g, T, gw, part);
   }
   const int rows = (c.m_max + 3) / 4;
-  hipLaunchKernelGGL(k_wm_dctx, dim3(rows < kWmMaxGroups ? rows : kWmMaxGroups), dim3(256), 0, st, c.g, c.m_max, W * W,
+  hipLaunchKernelGGL(k_wm_dctx, dim3(rows < kTileMaxGroups ? rows : kTileMaxGroups), dim3(256), 0, st, c.g, c.m_max, W * W,
                      c.d_ctx);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess || !c.d_feat) return (int)e;

@@ -142,8 +142,8 @@ __global__ __launch_bounds__(256) void k_closs_entries(const float* __restrict__
 }
 
 // The tiled sweep (fm_sweep_device.h; grid (ceil(R / 32), N, Z)) with g computed from conf.
-//   kSums : per entry gc = g conf with g the dense part of G; row sums into v_out, column sums into u_out (float atomics in
-//           arrival order, as kDsmStats), l_neg(c) into a per-thread sum (double), one partial per workgroup into loss_part in a
+//   kSums : per entry gc = g conf with g the dense part of G; row sums and column sums as partials folded in index order
+//           (as kDsmStats: no atomics), l_neg(c) into a per-thread sum (double), one partial per workgroup into loss_part in a
 //           fixed order.  Side 0 only.
 //   kGrad : D = 2 gc - A w_y - B w_x accumulated into the rows' gradient, partials per z into `part`.
 template <int KIND>
@@ -287,7 +287,9 @@ static int closs_sweep(int mode, int side, const DsmCall& c, const DsmProblem& p
   double* loss_part = q.w.loss_part.in(c.workspace);
   auto launch = [&](auto cc, auto mm, auto kk) {
     constexpr int CC = decltype(cc)::value, MM = decltype(mm)::value, KK = decltype(kk)::value;
-    return launch_sweep<&k_closs_sweep<CC, MM, KK>>(o, sweep_lds_bytes(CC, false), c.st(), q.lp, p.part, p.v, p.u, loss_part);
+    const bool sums = MM == kSums;               // (side 0: its sums go out as partials, folded into v and u below)
+    return launch_sweep<&k_closs_sweep<CC, MM, KK>>(o, sweep_lds_bytes(CC, false), c.st(), q.lp, p.part, sums ? p.vpart : p.v,
+                                                    sums ? p.upart : p.u, loss_part);
   };
   const hipError_t e = with_padded_channels(p.C, [&](auto cc) {
     return with_kind(q.kind, [&](auto kk) {
@@ -295,7 +297,9 @@ static int closs_sweep(int mode, int side, const DsmCall& c, const DsmProblem& p
     });
   });
   if (e != hipSuccess) return (int)e;
-  if (mode != kSums) return (int)launch_sweep_combine(o, grid.z, c.d_loss, side ? c.d_feat1 : c.d_feat0, c.st());
+  if (mode != kSums) return (int)launch_sweep_combine(o, grid.z, c.d_loss, side ? c.d_feat1 : c.d_feat0, true, c.st());
+  const hipError_t ef = launch_sweep_fold_sums(p, c.st());
+  if (ef != hipSuccess) return (int)ef;
   hipLaunchKernelGGL(k_closs_finish, dim3(1), dim3(256), 0, c.st(), loss_part, (long)grid.x * grid.y * grid.z,
                      q.w.l_pos.in(c.workspace), q.w.l_neg.in(c.workspace), q.w.Ke, q.inv_pos, q.inv_neg, q.pos_weight,
                      q.neg_weight, q.stand_in ? 0 : 1, c.loss_out);
@@ -356,13 +360,11 @@ extern "C" int fm_coarse_loss_backward(const float* feat0, const float* feat1, i
   if (r != FM_OK) return r;
   const DsmProblem p = dsm_carve(c);          // (v and u are the forward call's)
   ClossCall q = closs_begin(c);
-  for (int side = 0; side < 2; ++side) {
-    r = closs_sweep(kGrad, side, c, p, q);
-    if (r != FM_OK) return r;
-  }
   float* gcs = q.w.gcs.in(workspace);
   hipLaunchKernelGGL(k_closs_scale, dim3((q.e.K + 255) / 256), dim3(256), 0, c.st(), q.w.gc.in(workspace), q.e.K, d_loss,
                      gcs);
   q.e.gc = gcs;
-  return (int)launch_dsm_entries(p, q.e, d_feat0, d_feat1, c.st());
+  r = (int)launch_dsm_entries(p, q.e, d_feat0, d_feat1, c.st());      // (first: the sweeps' combine adds on top)
+  for (int side = 0; side < 2 && r == FM_OK; ++side) r = closs_sweep(kGrad, side, c, p, q);
+  return r;
 }

@@ -63,8 +63,8 @@ __global__ __launch_bounds__(256) void k_conf_at(const float* __restrict__ f0, c
   }
 }
 
-// u_l and v_k of the supervised entries (float atomics: entries that share a row or a column are rare, and the order
-// in which two of them are added is the only thing that is not fixed)
+// u_l and v_k of the supervised entries (float atomics: entries that share a row or a column are rare; two of them commute,
+// so the order of three or more in one row or column - here and in k_dsm_entries - is all in this file that is not fixed)
 __global__ __launch_bounds__(256) void k_dsm_uv(const int64_t* __restrict__ b_ids, const int64_t* __restrict__ i_ids,
                                                 const int64_t* __restrict__ j_ids, const float* __restrict__ gc, int K,
                                                 int L, int S, float* __restrict__ v, float* __restrict__ u) {
@@ -83,11 +83,10 @@ __global__ __launch_bounds__(256) void k_dsm_uv(const int64_t* __restrict__ b_id
 // 62-65 - without any [N, L, S] temporary):
 //   kDsmSparse : as above (G lives in w_x / w_y and the entries' own kernel).
 //   kDsmStats  : v_k = sum_l G_kl conf_kl and u_l = sum_k G_kl conf_kl with conf recomputed tile by tile from exact float32
-//                dot products (conf = A B); no gradient phase.  Launched on side 0 only; v and u by float atomics: a row's
-//                v takes one add per z slice (<= 4), a COLUMN's u one add per 32-row tile of the owner image (150 at
-//                640x480) in arrival order - the dense backward's gradients are therefore reproducible to float32
-//                rounding of those sums (~1e-7 relative), not bit for bit; every other reduction of this file is
-//                order-fixed (k_sweep_combine).
+//                dot products (conf = A B); no gradient phase.  Launched on side 0 only; no atomics: a row's v is
+//                one partial per z slice (<= 4), a COLUMN's u one partial per 32-row tile of the owner image (150 at
+//                640x480), each stored by its one workgroup and added up in index order by k_sweep_fold_sums - the
+//                dense backward's gradients are the same bits on every run.
 //   kDsmDense  : D_kl = 2 G_kl conf_kl - A_kl u_l - B_kl v_k, the whole of dL/dsim, accumulated into the rows' gradient.
 // G is read through a transposing LDS tile when the owner image is image 1 (g_t: element (owner row, other row) lives at
 // G[other][owner]): both sides read 128-byte row segments of G.  G is read three times in all (92 MB per 640x480 pair
@@ -154,7 +153,8 @@ __global__ __launch_bounds__(256) void k_dsm_bwd(const float* __restrict__ X, co
 
 // out = scale * sum_z part[z]   (fixed order), D_LOSS: scale * d_loss * sum_z part[z] with d_loss [1] on the device, the
 // upstream gradient of the coarse loss's scalar
-template <bool D_LOSS>
+// ADD: on top of what `out` holds (the entries' own terms, added before the sweeps)
+template <bool D_LOSS, bool ADD>
 __global__ __launch_bounds__(256) void k_sweep_combine(const float4* __restrict__ part, long n4, int Z, float scale,
                                                        const float* __restrict__ d_loss, float4* __restrict__ out) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
@@ -165,11 +165,41 @@ __global__ __launch_bounds__(256) void k_sweep_combine(const float4* __restrict_
     const float4 v = part[(long)z * n4 + i];
     s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
   }
-  out[i] = make_float4(s.x * f, s.y * f, s.z * f, s.w * f);
+  float4 r = make_float4(s.x * f, s.y * f, s.z * f, s.w * f);
+  if (ADD) { const float4 e = out[i]; r.x += e.x; r.y += e.y; r.z += e.z; r.w += e.w; }
+  out[i] = r;
+}
+
+// v += sum over the z slices' partials, u += sum over the row tiles' partials of a statistics sweep, each in index order
+// (vpart [Z][n_v], upart [G][n_u]; one thread per element)
+__global__ __launch_bounds__(256) void k_sweep_fold_sums(const float* __restrict__ vpart, long n_v, int Z,
+                                                         const float* __restrict__ upart, long n_u, int G,
+                                                         float* __restrict__ v, float* __restrict__ u) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i < n_v) {
+    float s = vpart[i];
+    for (int z = 1; z < Z; ++z) s += vpart[(long)z * n_v + i];
+    v[i] += s;
+  } else if (i - n_v < n_u) {
+    const long k = i - n_v;
+    float s = upart[k];
+    int g = 1;
+    for (; g + 8 <= G; g += 8) {                          // eight loads in flight; the additions stay in index order
+      float x[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) x[j] = upart[(long)(g + j) * n_u + k];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) s += x[j];
+    }
+    for (; g < G; ++g) s += upart[(long)g * n_u + k];
+    u[k] += s;
+  }
 }
 
 // the supervised entries' own term: d0[b, i, :] += 2 g c / (C T) f1[b, j, :],  d1[b, j, :] += 2 g c / (C T) f0[b, i, :]
-// (one wave per entry; float atomics - see k_dsm_uv)
+// (one wave per entry; float atomics).  Launched FIRST, onto zeroed gradients (launch_dsm_entries clears them), and the
+// combine of the sweeps' partials adds its sum on top: the first term lands on 0 exactly and two terms commute, so a row
+// or column with up to two entries is the same bits in any arrival order - as k_dsm_uv's sums.  Cost: K C atomics.
 __global__ __launch_bounds__(256) void k_dsm_entries(const float* __restrict__ f0, const float* __restrict__ f1, int L, int S,
                                                      int c_in, const int64_t* __restrict__ b_ids,
                                                      const int64_t* __restrict__ i_ids, const int64_t* __restrict__ j_ids,
@@ -197,6 +227,9 @@ hipError_t launch_dsm_uv(const DsmEntries& e, int L, int S, float* v, float* u, 
 }
 
 hipError_t launch_dsm_entries(const DsmProblem& p, const DsmEntries& e, float* d_feat0, float* d_feat1, hipStream_t st) {
+  hipError_t z = hipMemsetAsync(d_feat0, 0, (size_t)p.N * p.L * p.C * sizeof(float), st);
+  if (z == hipSuccess) z = hipMemsetAsync(d_feat1, 0, (size_t)p.N * p.S * p.C * sizeof(float), st);
+  if (z != hipSuccess) return z;
   hipLaunchKernelGGL(k_dsm_entries, dim3((e.K + 3) / 4), dim3(256), 0, st, p.feat0, p.feat1, p.L, p.S, p.C, e.b_ids, e.i_ids,
                      e.j_ids, e.gc, e.K, 2.0f * p.inv_ct, d_feat0, d_feat1);
   return hipGetLastError();
@@ -226,7 +259,7 @@ DsmProblem dsm_carve(const DsmCall& c) {
   const float inv_ct = inv_ct_of(c.C, c.temperature);
   const DsmBwdWs w = dsm_bwd_layout(c.N, c.L, c.S, c.C);
   return {c.feat0, c.feat1, c.N, c.L, c.S, c.C, k2_of(inv_ct), inv_ct, w.v.in(c.workspace), w.u.in(c.workspace),
-          w.part.in(c.workspace)};
+          w.part.in(c.workspace), w.vpart.in(c.workspace), w.upart.in(c.workspace)};
 }
 
 int dsm_begin(const DsmCall& c, DsmProblem* p) {
@@ -235,11 +268,19 @@ int dsm_begin(const DsmCall& c, DsmProblem* p) {
   return (int)hipMemsetAsync(sums.in(c.workspace), 0, sums.bytes, c.st());
 }
 
-hipError_t launch_sweep_combine(const DsmSide& o, int Z, const float* d_loss, float* d_out, hipStream_t st) {
+hipError_t launch_sweep_combine(const DsmSide& o, int Z, const float* d_loss, float* d_out, bool add, hipStream_t st) {
   const long n4 = (long)o.p.N * o.p.L * o.p.C / 4;
   const dim3 grid((unsigned)((n4 + 255) / 256));
-  auto* combine = d_loss ? k_sweep_combine<true> : k_sweep_combine<false>;
+  auto* combine = d_loss ? (add ? k_sweep_combine<true, true> : k_sweep_combine<true, false>)
+                         : (add ? k_sweep_combine<false, true> : k_sweep_combine<false, false>);
   hipLaunchKernelGGL(combine, grid, dim3(256), 0, st, (const float4*)o.p.part, n4, Z, o.p.inv_ct, d_loss, (float4*)d_out);
+  return hipGetLastError();
+}
+
+hipError_t launch_sweep_fold_sums(const DsmProblem& p, hipStream_t st) {
+  const long n_v = (long)p.N * p.L, n_u = (long)p.N * p.S;
+  hipLaunchKernelGGL(k_sweep_fold_sums, dim3((unsigned)((n_v + n_u + 255) / 256)), dim3(256), 0, st, p.vpart, n_v,
+                     dsm_zsplit(p.N, p.L), p.upart, n_u, (p.L + 31) / 32, p.v, p.u);
   return hipGetLastError();
 }
 
@@ -248,15 +289,19 @@ static int dsm_sweep(int mode, int side, const DsmProblem& p, const DsmCall& c) 
   const DsmSide o = dsm_side(p, c.s, side);
   auto launch = [&](auto cc, auto mm) {
     constexpr int CC = decltype(cc)::value, MM = decltype(mm)::value;
-    return launch_sweep<&k_dsm_bwd<CC, MM>>(o, sweep_lds_bytes(CC, true), c.st(), p.part, c.G, side, p.v, p.u);
+    const bool stats = MM == kDsmStats;          // (side 0: its sums go out as partials, folded into v and u below)
+    return launch_sweep<&k_dsm_bwd<CC, MM>>(o, sweep_lds_bytes(CC, true), c.st(), p.part, c.G, side, stats ? p.vpart : p.v,
+                                            stats ? p.upart : p.u);
   };
   const hipError_t e = with_padded_channels(p.C, [&](auto cc) {
     if (mode == kDsmSparse) return launch(cc, int_c<kDsmSparse>{});
     return mode == kDsmStats ? launch(cc, int_c<kDsmStats>{}) : launch(cc, int_c<kDsmDense>{});
   });
   if (e != hipSuccess) return (int)e;
-  if (mode != kDsmStats) return (int)launch_sweep_combine(o, dsm_sweep_grid(o).z, nullptr, side ? c.d_feat1 : c.d_feat0, c.st());
-  return (int)hipGetLastError();
+  if (mode != kDsmStats)      // (a sparse call's entries have put their own terms into the gradients already)
+    return (int)launch_sweep_combine(o, dsm_sweep_grid(o).z, nullptr, side ? c.d_feat1 : c.d_feat0,
+                                     mode == kDsmSparse && c.e.K > 0, c.st());
+  return (int)launch_sweep_fold_sums(p, c.st());
 }
 
 }  // namespace fm
@@ -315,8 +360,8 @@ extern "C" int fm_dual_softmax_backward(const float* feat0, const float* feat1, 
   int r = dsm_status(c);
   if (r == FM_OK) r = dsm_begin(c, &p);
   if (r == FM_OK && K > 0) r = (int)launch_dsm_uv(c.e, L, S, p.v, p.u, c.st());
+  if (r == FM_OK && K > 0) r = (int)launch_dsm_entries(p, c.e, d_feat0, d_feat1, c.st());
   if (r == FM_OK) r = dsm_sweep(kDsmSparse, 0, p, c);
   if (r == FM_OK) r = dsm_sweep(kDsmSparse, 1, p, c);
-  if (r == FM_OK) r = K > 0 ? (int)launch_dsm_entries(p, c.e, d_feat0, d_feat1, c.st()) : (int)hipGetLastError();
   return r;
 }

@@ -283,15 +283,24 @@ struct DsmCall {
 };
 
 // Workspace of the backward entry points: v [N][L] row sums and u [N][S] column sums of g conf, one behind the other
-// (sums: the two, zeroed per call) | part, 256-byte aligned: up to 4 (dsm_zsplit) partial gradients [N][max(L, S)][C]
-struct DsmBwdWs { Region<float> v, u, part; Span sums; size_t total; };
+// (sums: the two, zeroed per call) | part, 256-byte aligned: up to 4 (dsm_zsplit) partial gradients [N][max(L, S)][C].
+// A statistics sweep (side 0) has no gradient and borrows `part` for the partial sums that k_sweep_fold_sums adds up in
+// index order, every element written by exactly one workgroup: vpart [4 (z)][N][L], then upart [ceil(L / 32) (row tile of
+// image 0)][N][S] from the next 256-byte boundary; `part` is as large as the larger of its two uses (the sums' only for
+// fewer channels than about a 128th of the grid).
+struct DsmBwdWs { Region<float> v, u, part, vpart, upart; Span sums; size_t total; };
 inline DsmBwdWs dsm_bwd_layout(int N, int L, int S, int C) {
   DsmBwdWs w;
   Carver c;
   c.take(w.v, (size_t)N * L);
   c.take(w.u, (size_t)N * S, sizeof(float));
   w.sums = c.since(w.v.at);                   // v and u
-  c.take(w.part, (size_t)4 * N * (size_t)(L > S ? L : S) * C);
+  const size_t grads = (size_t)4 * N * (size_t)(L > S ? L : S) * C;
+  const size_t vpart = align256((size_t)4 * N * L * sizeof(float)) / sizeof(float);
+  const size_t upart = (size_t)((L + 31) / 32) * N * S;
+  c.take(w.part, grads > vpart + upart ? grads : vpart + upart);
+  w.vpart.at = w.part.at;
+  w.upart.at = w.part.at + vpart * sizeof(float);
   w.total = c.o;
   return w;
 }
@@ -320,7 +329,7 @@ inline ClossWs closs_layout(int N, int L, int S, int C, int K) {
 
 int dsm_status(const DsmCall& c);   // the ONLY copy of the five entry points' argument checks (the table: DESIGN.md 6g)
 // one call past its status: the descriptors, the shape, the temperature terms and the carved workspace
-struct DsmProblem { const float *feat0, *feat1; int N, L, S, C; float k2, inv_ct; float *v, *u, *part; };
+struct DsmProblem { const float *feat0, *feat1; int N, L, S, C; float k2, inv_ct; float *v, *u, *part, *vpart, *upart; };
 // dsm_carve: a pure function of a call (with a workspace) that passed dsm_status; dsm_begin: the same, and v and u zeroed
 // on the call's stream (the coarse loss's backward takes v and u from its forward call).  Neither checks anything.
 DsmProblem dsm_carve(const DsmCall& c);
@@ -342,8 +351,12 @@ inline hipError_t with_padded_channels(int C, F&& f) {
   return Cp == 64 ? f(int_c<64>{}) : Cp == 128 ? f(int_c<128>{}) : f(int_c<256>{});
 }
 // d_out [N][o.p.L][C] = inv_ct (* d_loss[0], if given: on the device) * sum over the Z partials of a gradient sweep
-hipError_t launch_sweep_combine(const DsmSide& o, int Z, const float* d_loss, float* d_out, hipStream_t st);
-// v / u contributions and own term 2 g c of the listed entries (k_dsm_uv, k_dsm_entries)
+// (add: + what d_out holds)
+hipError_t launch_sweep_combine(const DsmSide& o, int Z, const float* d_loss, float* d_out, bool add, hipStream_t st);
+// behind a statistics sweep of side 0: v += the z slices' row sums, u += the row tiles' column sums, each in index order
+hipError_t launch_sweep_fold_sums(const DsmProblem& p, hipStream_t st);
+// v / u contributions and own term 2 g c of the listed entries (k_dsm_uv, k_dsm_entries; the latter clears d_feat0 /
+// d_feat1 first and goes BEFORE the gradient sweeps, whose combine adds to it)
 hipError_t launch_dsm_uv(const DsmEntries& e, int L, int S, float* v, float* u, hipStream_t st);
 hipError_t launch_dsm_entries(const DsmProblem& p, const DsmEntries& e, float* d_feat0, float* d_feat1, hipStream_t st);
 

@@ -4,9 +4,10 @@
 //
 // A workgroup of 256 threads owns 32 rows of the "owner" image (X, R rows) and sweeps the z-th share of the other image
 // (Y, T rows) in tiles of 32 descriptors; grid (ceil(R / 32), N, Z).  Per tile it recomputes the 32 x 32 dot products in
-// float32, turns each into one value (written transposed into Dt) and either adds the tile's column sums to u_out and
-// goes on (kDsmStats) or accumulates Dt . Ys into its rows' gradient (kDsmSparse, kDsmDense).  It ends with the row
-// sums into v_out (kDsmStats) or its partial gradient into part[z][b][row][c_in].
+// float32 and turns each into one value (written transposed into Dt).  kDsmStats: it stores the tile's column sums as its
+// row tile's partial of u and goes on; v_out / u_out are then the partial arrays, and it ends with the row sums into its z
+// slice's partial of v.  kDsmSparse, kDsmDense: it accumulates Dt . Ys into its rows' gradient and ends with its partial
+// gradient into part[z][b][row][c_in].
 //   kDsmSparse : D = -(A w_y + B w_x), the weights w / sum folded into one factor per row / column
 //   kDsmStats  : gc = g conf, conf = A B                          (no gradient phase)
 //   kDsmDense  : D = 2 gc - A w_y - B w_x                         (1 / sum and w kept apart)
@@ -76,20 +77,22 @@ __device__ __forceinline__ void sweep_accumulate(const float* Ys, const float* D
   }
 }
 
-// column sums of this tile's g conf: 32 threads add the 32 owner rows of their column in a fixed order; a column's u takes
-// one add per 32-row tile of the owner image, in arrival order
-__device__ __forceinline__ void sweep_column_sums(const float* Dt, int b, int l0, int T, float* u_out) {
+// column sums of this tile's g conf: 32 threads add the 32 owner rows of their column in a fixed order and store the sum
+// as the partial of this workgroup's row tile, u_part[blockIdx.x][b][T] - a tile of columns belongs to one z slice, so
+// every element has one writer; k_sweep_fold_sums adds the row tiles up in index order (no atomics)
+__device__ __forceinline__ void sweep_column_sums(const float* Dt, int b, int l0, int T, float* u_part) {
   const int tid = threadIdx.x;
   if (tid < 32 && l0 + tid < T) {
     float cs = 0.f;
 #pragma unroll 8
     for (int rr = 0; rr < 32; ++rr) cs += Dt[tid * kSweepDtPitch + rr];
-    atomicAdd(&u_out[(long)b * T + l0 + tid], cs);
+    u_part[((long)blockIdx.x * gridDim.y + b) * T + l0 + tid] = cs;
   }
 }
 
-// row sums: the 32 columns a row's partial sums sit in are the 32 lanes of a half wave; one add per z slice
-__device__ __forceinline__ void sweep_row_sums(const float (&vacc)[4], int b, int k0, int R, float* v_out) {
+// row sums: the 32 columns a row's partial sums sit in are the 32 lanes of a half wave; one partial per z slice,
+// v_part[z][b][R] (a slice without a tile stores 0), folded in index order by k_sweep_fold_sums
+__device__ __forceinline__ void sweep_row_sums(const float (&vacc)[4], int b, int k0, int R, float* v_part) {
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
@@ -97,7 +100,7 @@ __device__ __forceinline__ void sweep_row_sums(const float (&vacc)[4], int b, in
 #pragma unroll
     for (int m = 16; m >= 1; m >>= 1) t += __shfl_xor(t, m);
     const int k = k0 + ty + 8 * q;
-    if (tx == 0 && k < R) atomicAdd(&v_out[(long)b * R + k], t);
+    if (tx == 0 && k < R) v_part[((long)blockIdx.z * gridDim.y + b) * R + k] = t;
   }
 }
 

@@ -574,8 +574,11 @@ int fm_epipolar_errors(const float* mkpts0, const float* mkpts1, int kpt_stride,
  *                                 dL/dsim_kl = 2 g c [kl supervised] - A_kl u_l - B_kl v_k,  u / v = column / row sums of g c
  *                               (A, B recomputed tile by tile from the statistics; float32 arithmetic).  workspace:
  *                               fm_dual_softmax_backward_workspace_bytes bytes [dev], 256-byte aligned.  feat0 / feat1
- *                               float32.  Entries sharing a row or a column are added with float atomics (the order of
- *                               their additions is the only non-deterministic part).
+ *                               float32.  The listed entries' gc is added into the zeroed u and v, and their own terms
+ *                               into the zeroed gradients (before the sweeps' sums are added on top), with float atomics:
+ *                               K and K C of them, linear in K whatever K is (K <= N L S is not required; a triple listed
+ *                               twice counts twice).  THREE or more entries in one row or one column are the only sums
+ *                               whose order is not fixed: the first lands on 0 exactly and two commute.
  * What tests/test_gpu_dsm_grad.py establishes about these calls and the coarse loss below, with statistics made by the caller:
  *   - pitch_r >= L and pitch_c >= S may be any such value, the two independently; positions L .. pitch_r - 1 and S ..
  *     pitch_c - 1 of a row of the statistics are never read (they may hold NaN).  A smaller pitch is FM_E_SHAPE.
@@ -583,7 +586,8 @@ int fm_epipolar_errors(const float* mkpts0, const float* mkpts1, int kpt_stride,
  *     and a relative error delta of the denominators reaches the gradients as at most ~4 delta of the summed terms'
  *     magnitude (not of the gradient: on saturated problems the gradient is the small residue of those terms).
  *   - fm_dual_softmax_backward adds a triple once per time it is listed (three times the same (b, i, j, gc) = once with
- *     3 gc); entries with distinct rows and columns give the same bits on every call.  The coarse loss wants DISTINCT triples.
+ *     3 gc); lists with at most two entries per row and per column give the same bits on every call.  The coarse loss wants
+ *     DISTINCT triples.
  *   - K = 0: fm_dual_softmax_conf_at returns FM_OK and writes nothing; fm_dual_softmax_backward writes exact zeros to all
  *     of d_feat0 / d_feat1 and does not look at the id and gc pointers.  A sample of the batch without an entry gets
  *     exact zeros; so does every call of fm_dual_softmax_backward_dense with G = 0.
@@ -604,7 +608,9 @@ int fm_dual_softmax_backward(const float* feat0, const float* feat1, int N, int 
 /* The same for a DENSE dL/dconf: G [dev] float32 [N, L, S] (the reference's loss terms over ALL negatives, losses/loss.py:
  * 44-50, 62-65, hand back a gradient for every entry).  conf is recomputed tile by tile from exact float32 dot products
  * and the statistics; three tiled sweeps (the row / column sums of G conf, then the two gradients) read G three times and
- * write nothing of its size: same workspace as fm_dual_softmax_backward, no [N, L, S] temporary. */
+ * write nothing of its size: same workspace as fm_dual_softmax_backward, no [N, L, S] temporary.  No atomics: the row and
+ * column sums are partials with one writer each (in the part of the workspace the gradient sweeps use afterwards), added up
+ * in index order - the same bits on every run. */
 int fm_dual_softmax_backward_dense(const float* feat0, const float* feat1, int N, int L, int S, int C, float temperature,
                                    const float* nm_r, const float* sum_r, int pitch_r, const float* nm_c, const float* sum_c,
                                    int pitch_c, const float* G, void* workspace, size_t workspace_bytes, float* d_feat0,
@@ -624,7 +630,8 @@ int fm_dual_softmax_backward_dense(const float* feat0, const float* feat1, int N
  *                             The loss is the same bits on every run (its sums are taken in a fixed order).  One sweep.
  *   fm_coarse_loss_backward : d_feat0 [N,L,C], d_feat1 [N,S,C] = d_loss[0] * dloss/dfeat; d_loss [dev] float32 [1] is read
  *                             on the device.  Same problem arguments as the forward call and ITS workspace, untouched
- *                             since.  Two sweeps; reproducible to float32 rounding as fm_dual_softmax_backward_dense.
+ *                             since.  Two sweeps; the same bits on every run, as fm_dual_softmax_backward_dense (with at
+ *                             most two supervised entries per row and per column: see fm_dual_softmax_backward).
  * workspace: fm_coarse_loss_workspace_bytes bytes [dev], 256-byte aligned (0 for an invalid shape).  No host
  * synchronisation in either call.  K = 0 (the id pointers may be NULL) and K = N L S are the reference's degenerate cases
  * (loss.py:37-42): entry (0, 0, 0) stands in as the one positive with pos_weight 0 and, as in the reference, stays among

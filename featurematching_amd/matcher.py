@@ -89,9 +89,7 @@ class Matcher(nn.Module):
         super().train(mode)
         on = bool(mode) and self.hip_train
         for tf in (self.coarse, self.fine):
-            tf.hip_attention = tf.hip_tail = tf.hip_proj = on
-            for layer in tf.layers:
-                layer.hip_attention = layer.hip_tail = layer.hip_proj = on
+            tf.hip_attention = tf.hip_tail = tf.hip_proj = on      # (each writes through to the transformer's layers)
         self.fine_preprocess.hip_merge = on
         self.coarse_matching.loss_stats = bool(mode) and self.train_coarse == 'stats'
         self.coarse_matching.conf_matrix = bool(mode) and self.train_coarse == 'matrix'

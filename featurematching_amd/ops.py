@@ -61,6 +61,33 @@ def _aligned_workspace(nbytes: int, device):
     return ws, _aligned(ws)
 
 
+def _workspace(query: str, device, *dims, empty_ok: bool = False):
+    """(buffer, 256-byte aligned address, bytes) of the workspace the size query `query` asks for at `dims`; with
+    empty_ok a query that answers 0 gives (None, None, 0) - the call is then handed NULL"""
+    need = int(getattr(_lib.load(), query)(*dims))
+    if empty_ok and not need:
+        return None, None, 0
+    return (*_aligned_workspace(need, device), need)
+
+
+def _call(name: str, *args, dev, head=()) -> None:
+    """the C call `name`(*head, *args, the current stream of `dev`); a status raises under that name"""
+    _lib.check(getattr(_lib.load(), name)(*head, *args, _stream(dev)), name)
+
+
+def _rows64(t: torch.Tensor) -> torch.Tensor:
+    """[..., 64] as the token-wise kernels read it: [T, 64], contiguous (the results are viewed back to the shape)"""
+    return t.reshape(-1, 64).contiguous()
+
+
+def _param_grads(params, wanted):
+    """Parameter gradients are computed all or none: (what the backward call is handed - an uninitialised tensor per
+    parameter when any is wanted, else None for each and the kernels skip that work; what autograd gets back - those
+    tensors where wanted, None elsewhere)"""
+    full = [torch.empty_like(p) for p in params] if any(wanted) else [None] * len(params)
+    return full, [d if want else None for d, want in zip(full, wanted)]
+
+
 @functools.lru_cache(maxsize=256)
 def _workspace_bytes(query: str, *args) -> int:
     """fm_coarse_workspace_bytes_mode / _auto: a pure function of its arguments, asked once per distinct call"""
@@ -396,15 +423,12 @@ class _DualSoftmax:
 
     ids = staticmethod(lambda *lists: [_i64c(t) for t in lists])        # the id lists as the library reads them
 
-    def workspace(self, query: str, *more):                              # (buffer, aligned address, bytes) of what `query` asks for
-        need = int(getattr(_lib.load(), query)(*self.shape, *more))
-        return (*_aligned_workspace(need, self.dev), need)
-
     def grads(self):                                                     # (d_feat0, d_feat1), uninitialised
         return torch.empty_like(self.x0), torch.empty_like(self.x1)
 
-    def run(self, name: str, *args) -> None:                             # `name`(*head, *args, current stream); a status raises
-        _lib.check(getattr(_lib.load(), name)(*self.head, *args, _stream(self.dev)), name)
+    @functools.cached_property
+    def run(self):                                                       # run(name, *args): `name`(*head, *args, current stream)
+        return functools.partial(_call, dev=self.dev, head=self.head)
 
     def finish(self, d0, d1, *keep):
         """The gradients in the callers' element types.  The kernels run on the current stream and torch's caching
@@ -419,7 +443,8 @@ def _dsm_backward(f0, f1, temperature, buffers, b_ids, i_ids, j_ids, gc):
     """(dL/df0, dL/df1) of sum_e g_e conf_e from gc = g * conf at the entries (fm_dual_softmax_backward): two launches of
     one tiled kernel that recomputes the similarities tile by tile - no [N, L, S] array."""
     p = _DualSoftmax(f0, f1, temperature, buffers)
-    _, (ws, wsp, need) = p.head, p.workspace("fm_dual_softmax_backward_workspace_bytes")      # (statistics first, as ever)
+    p.head                                                               # (statistics first, as ever)
+    ws, wsp, need = _workspace("fm_dual_softmax_backward_workspace_bytes", p.dev, *p.shape)
     d0, d1 = p.grads()
     bb, ii, jj = p.ids(b_ids, i_ids, j_ids)
     g = _f32c(gc, "gc")
@@ -459,7 +484,8 @@ def _dsm_backward_dense(f0, f1, temperature, buffers, grad):
     exact float32 dot products and the forward call's softmax statistics - no [N, L, S] temporary."""
     p = _DualSoftmax(f0, f1, temperature, buffers)
     g = _f32c(grad, "grad")
-    _, (ws, wsp, need) = p.head, p.workspace("fm_dual_softmax_backward_workspace_bytes")      # (statistics first, as ever)
+    p.head                                                               # (statistics first, as ever)
+    ws, wsp, need = _workspace("fm_dual_softmax_backward_workspace_bytes", p.dev, *p.shape)
     d0, d1 = p.grads()
     p.run("fm_dual_softmax_backward_dense", _ptr(g), wsp, need, _ptr(d0), _ptr(d1))
     return p.finish(d0, d1, ws, g)
@@ -552,7 +578,7 @@ class _CoarseLoss(torch.autograd.Function):
     def forward(ctx, feat_c0, feat_c1, bb, ii, jj, buffers, kind, alpha, gamma, pos_weight, neg_weight):
         p = _DualSoftmax(feat_c0, feat_c1, buffers._temperature, buffers)
         k = int(bb.shape[0])
-        ws, wsp, need = p.workspace("fm_coarse_loss_workspace_bytes", k)
+        ws, wsp, need = _workspace("fm_coarse_loss_workspace_bytes", p.dev, *p.shape, k)
         out = torch.empty(3, dtype=torch.float32, device=p.dev)
         ids = (_ptr(bb), _ptr(ii), _ptr(jj)) if k else (None, None, None)
         ctx.problem = (kind, float(alpha), float(gamma), float(pos_weight), float(neg_weight), *ids, k, wsp, need)
@@ -615,23 +641,20 @@ def supervise_matches(kp0: torch.Tensor, kp1: torch.Tensor, hw0_c, hw1_c, cell: 
     dev = kp0.device
     k = int(kp0.shape[0])
     cap = max(0, min(k, h1c * w1c))
-    need = int(lib.fm_supervise_workspace_bytes(h0c, w0c, h1c, w1c))
+    ws, wsp, need = _workspace("fm_supervise_workspace_bytes", dev, h0c, w0c, h1c, w1c, empty_ok=True)
     if need == 0:
         raise ValueError(f"coarse grids {hw0_c} / {hw1_c}: positive, at most 2^24 cells each")
-    ws, wsp = _aligned_workspace(need, dev)
     ids = torch.empty(2, cap, dtype=torch.int64, device=dev)
     pts = torch.empty(4, cap, 2, dtype=torch.float32, device=dev)
     lists = torch.empty(2, cap, dtype=torch.float32, device=dev)
     mtx0 = torch.empty(h0c * w0c, 2, dtype=torch.float32, device=dev)
     mtx1 = torch.empty(h1c * w1c, 2, dtype=torch.float32, device=dev)
     count = torch.empty(2, dtype=torch.int32, device=dev)
-    stream = _stream(dev)
-    _lib.check(lib.fm_supervise_matches(_ptr(kp0), _ptr(kp1), k, h0c, w0c, h1c, w1c, float(cell), wsp, need, _ptr(ids[0]),
-                                        _ptr(ids[1]), _ptr(pts[0]), _ptr(pts[1]), _ptr(pts[2]), _ptr(pts[3]),
-                                        _ptr(lists[0]), _ptr(lists[1]), _ptr(mtx0), _ptr(mtx1), cap, _ptr(count), stream),
-               "fm_supervise_matches")
+    _call("fm_supervise_matches", _ptr(kp0), _ptr(kp1), k, h0c, w0c, h1c, w1c, float(cell), wsp, need, _ptr(ids[0]),
+          _ptr(ids[1]), _ptr(pts[0]), _ptr(pts[1]), _ptr(pts[2]), _ptr(pts[3]), _ptr(lists[0]), _ptr(lists[1]), _ptr(mtx0),
+          _ptr(mtx1), cap, _ptr(count), dev=dev)
     m = C.c_int32(0)
-    _lib.check(lib.fm_read_count(_ptr(count), cap, C.byref(m), stream), "fm_supervise_matches")
+    _lib.check(lib.fm_read_count(_ptr(count), cap, C.byref(m), _stream(dev)), "fm_supervise_matches")
     n = m.value
     return {'i_ids': ids[0, :n], 'j_ids': ids[1, :n], 'coarse_kp0': pts[0, :n], 'coarse_kp1': pts[1, :n],
             'fine_kp0': pts[2, :n], 'fine_kp1': pts[3, :n], 'lists_f0': lists[0, :n], 'lists_f1': lists[1, :n],
@@ -644,15 +667,13 @@ class _FineLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, expec0, expec1, gt0, gt1, count):
-        lib = _lib.load()
         e0, e1 = _f32c(expec0, "expec0"), _f32c(expec1, "expec1")
         g0, g1 = _f32c(gt0, "gt0"), _f32c(gt1, "gt1")
         m_max, dev = int(e0.shape[0]), e0.device
-        need = int(lib.fm_fine_loss_workspace_bytes(m_max))
-        ws, wsp = _aligned_workspace(need, dev)
+        ws, wsp, need = _workspace("fm_fine_loss_workspace_bytes", dev, m_max)
         out = torch.empty(3, dtype=torch.float32, device=dev)
-        _lib.check(lib.fm_fine_loss_forward(_ptr(e0), _ptr(e1), 3, _ptr(g0), _ptr(g1), m_max, _ptr(count), wsp, need,
-                                            _ptr(out), _stream(dev)), "fm_fine_loss_forward")
+        _call("fm_fine_loss_forward", _ptr(e0), _ptr(e1), 3, _ptr(g0), _ptr(g1), m_max, _ptr(count), wsp, need, _ptr(out),
+              dev=dev)
         ctx.problem, ctx.keep = (_ptr(e0), _ptr(e1), 3, _ptr(g0), _ptr(g1), m_max, wsp, need), (e0, e1, g0, g1, ws, count)
         ctx.dtypes = (expec0.dtype, expec1.dtype)
         ctx.mark_non_differentiable(out)
@@ -660,12 +681,10 @@ class _FineLoss(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad, _):
-        lib = _lib.load()
         e0 = ctx.keep[0]
         d_loss = _d_loss(grad)
         d0, d1 = torch.empty_like(e0), torch.empty_like(e0)
-        _lib.check(lib.fm_fine_loss_backward(*ctx.problem, _ptr(d_loss), _ptr(d0), _ptr(d1), _stream(e0.device)),
-                   "fm_fine_loss_backward")
+        _call("fm_fine_loss_backward", *ctx.problem, _ptr(d_loss), _ptr(d0), _ptr(d1), dev=e0.device)
         d0._keep = (ctx.keep, d_loss)
         return d0.to(ctx.dtypes[0]), d1.to(ctx.dtypes[1]), None, None, None
 
@@ -755,10 +774,7 @@ class _Windows:
             if tuple(t.shape) != want:
                 raise ValueError(f"ctx{i} must be {list(want)}, got {tuple(t.shape)}")
             self.ctx.append(t)
-
-    def run(self, name: str, *args) -> None:
-        """the C call `name` on the maps' stream (its last argument); a status raises"""
-        _lib.check(getattr(_lib.load(), name)(*args, _stream(self.dev)), name)
+        self.run = functools.partial(_call, dev=self.dev)     # run(name, *args): the C call on the maps' stream
 
     def merge_nhwc(self, w, stride, pad, packed_w, b_ids, ids, count) -> None:
         """fm_gather_merge_windows_nhwc on the call's one or two channels-last maps (list order; image 1 absent: NULL / 0)"""
@@ -796,12 +812,11 @@ def gather_windows(feat_f: torch.Tensor, b_ids: torch.Tensor, ids: torch.Tensor,
 
 def pack_merge_weights(merge_w: torch.Tensor) -> torch.Tensor:
     """merge_feat.weight [64, 128] -> the 16 KiB MFMA fragment buffer fm_gather_merge_windows reads."""
-    lib = _lib.load()
     w = _f32c(merge_w, "merge_w")
     if tuple(w.shape) != (64, 128):
         raise ValueError(f"merge_feat.weight must be [64, 128], got {tuple(w.shape)}")
     packed = torch.empty(16384, dtype=torch.uint8, device=w.device)
-    _lib.check(lib.fm_merge_pack_weights(_ptr(w), 64, _ptr(packed), _stream(w.device)), "fm_merge_pack_weights")
+    _call("fm_merge_pack_weights", _ptr(w), 64, _ptr(packed), dev=w.device)
     return packed
 
 
@@ -852,7 +867,6 @@ def fine_match(win0: torch.Tensor, win1: torch.Tensor, mix0: torch.Tensor, mix1:
                count: Optional[torch.Tensor] = None):
     """Fine stage (fine_matching_new.py:50-79).  mix0/mix1 = float32 [WW+1] (weight, bias).
     Returns (mkpts0_f, mkpts1_f), each [M,3] = (x, y, std)."""
-    lib = _lib.load()
     win0 = _f32c(win0, "win0")
     win1 = _f32c(win1, "win1")
     m_max, ww, cf = win0.shape
@@ -863,10 +877,8 @@ def fine_match(win0: torch.Tensor, win1: torch.Tensor, mix0: torch.Tensor, mix1:
         return out0, out1
     k0 = _f32c(mkpts0_c, "mkpts0_c")
     k1 = _f32c(mkpts1_c, "mkpts1_c")
-    st = lib.fm_fine_match(_ptr(win0), _ptr(win1), m_max, _ptr(count), ww, cf, _ptr(_f32c(mix0, "mix0")),
-                           _ptr(_f32c(mix1, "mix1")), _ptr(k0), _ptr(k1), float(scale_f), _ptr(out0), _ptr(out1),
-                           _stream(dev))
-    _lib.check(st, "fm_fine_match")
+    _call("fm_fine_match", _ptr(win0), _ptr(win1), m_max, _ptr(count), ww, cf, _ptr(_f32c(mix0, "mix0")),
+          _ptr(_f32c(mix1, "mix1")), _ptr(k0), _ptr(k1), float(scale_f), _ptr(out0), _ptr(out1), dev=dev)
     return out0, out1
 
 
@@ -884,7 +896,6 @@ class _FineMatch(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g0, g1):
         w0, w1, m0, m1 = ctx.saved_tensors
-        lib = _lib.load()
         m_max, ww, cf = w0.shape
         dev = w0.device
         g0 = torch.zeros(m_max, 3, dtype=torch.float32, device=dev) if g0 is None else _f32c(g0, "grad")
@@ -892,11 +903,9 @@ class _FineMatch(torch.autograd.Function):
         d_w0, d_w1 = torch.zeros_like(w0), torch.zeros_like(w1)
         d_m0, d_m1 = torch.zeros_like(m0), torch.zeros_like(m1)
         if m_max > 0:
-            need = int(lib.fm_fine_match_backward_workspace_bytes(m_max, ww))
-            ws, wsp = _aligned_workspace(need, dev)
-            _lib.check(lib.fm_fine_match_backward(_ptr(w0), _ptr(w1), m_max, None, ww, cf, _ptr(m0), _ptr(m1), ctx.scale_f,
-                                                  _ptr(g0), _ptr(g1), wsp, need, _ptr(d_w0), _ptr(d_w1), _ptr(d_m0),
-                                                  _ptr(d_m1), _stream(dev)), "fm_fine_match_backward")
+            ws, wsp, need = _workspace("fm_fine_match_backward_workspace_bytes", dev, m_max, ww)
+            _call("fm_fine_match_backward", _ptr(w0), _ptr(w1), m_max, None, ww, cf, _ptr(m0), _ptr(m1), ctx.scale_f,
+                  _ptr(g0), _ptr(g1), wsp, need, _ptr(d_w0), _ptr(d_w1), _ptr(d_m0), _ptr(d_m1), dev=dev)
             d_w0._keep = (ws, g0, g1)
         t0, t1, t2, t3 = ctx.dtypes
         return d_w0.to(t0), d_w1.to(t1), d_m0.to(t2), d_m1.to(t3), g0[:, :2], g1[:, :2], None
@@ -917,7 +926,6 @@ def gather_windows_backward(d_win: torch.Tensor, b_ids: torch.Tensor, ids: torch
     (stored channels-last for layout 1), the sum of d_win over every (match, window position) that read each pixel, in
     a fixed order (bitwise reproducible).  count = the coarse stage's device-side int32 count: rows at or beyond
     min(count[0], M) contribute nothing (no host sync)."""
-    lib = _lib.load()
     n, cf, hf, wf = shape
     dev = d_win.device
     mf = torch.channels_last if layout == 1 else torch.contiguous_format
@@ -927,11 +935,9 @@ def gather_windows_backward(d_win: torch.Tensor, b_ids: torch.Tensor, ids: torch
         return d_feat.zero_()
     g = _f32c(d_win, "d_win")
     bb, ii = _i64c(b_ids), _i64c(ids)
-    need = int(lib.fm_gather_windows_backward_workspace_bytes(n, int(h_c), int(w_c), m_max))
-    ws, wsp = _aligned_workspace(need, dev)
-    _lib.check(lib.fm_gather_windows_backward(_ptr(g), _ptr(bb), _ptr(ii), _ptr(count), m_max, n, cf, hf, wf, layout, w,
-                                              stride, pad, int(h_c), int(w_c), wsp, need, _ptr(d_feat), _stream(dev)),
-               "fm_gather_windows_backward")
+    ws, wsp, need = _workspace("fm_gather_windows_backward_workspace_bytes", dev, n, int(h_c), int(w_c), m_max)
+    _call("fm_gather_windows_backward", _ptr(g), _ptr(bb), _ptr(ii), _ptr(count), m_max, n, cf, hf, wf, layout, w, stride,
+          pad, int(h_c), int(w_c), wsp, need, _ptr(d_feat), dev=dev)
     d_feat._keep = (ws, g, bb, ii, count)
     return d_feat
 
@@ -988,35 +994,31 @@ class _LinearAttention(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, q, k, v, q_mask, kv_mask, eps):
-        lib = _lib.load()
         qc, kc, vc = _f32c(q, "q"), _f32c(k, "k"), _f32c(v, "v")
         n, l, h, d = qc.shape
         s, dev = kc.shape[1], qc.device
         qm, km = _mask_bytes(q_mask, n, l, "q_mask"), _mask_bytes(kv_mask, n, s, "kv_mask")
         dims = (n, l, s, h, d)
-        state_bytes = int(lib.fm_linear_attention_state_bytes(*dims))
-        need = int(lib.fm_linear_attention_workspace_bytes(*dims))
+        state_bytes = int(_lib.load().fm_linear_attention_state_bytes(*dims))
         state = torch.empty(state_bytes // 4, dtype=torch.float32, device=dev) if state_bytes else None
-        ws, wsp = _aligned_workspace(need, dev) if need else (None, None)
+        ws, wsp, need = _workspace("fm_linear_attention_workspace_bytes", dev, *dims, empty_ok=True)
         out = torch.empty_like(qc)
-        _lib.check(lib.fm_linear_attention_forward(_ptr(qc), _ptr(kc), _ptr(vc), _ptr(qm), _ptr(km), *dims, float(eps), wsp,
-                                                   need, _ptr(state), _ptr(out), _stream(dev)), "fm_linear_attention_forward")
+        _call("fm_linear_attention_forward", _ptr(qc), _ptr(kc), _ptr(vc), _ptr(qm), _ptr(km), *dims, float(eps), wsp, need,
+              _ptr(state), _ptr(out), dev=dev)
         ctx.save_for_backward(qc, kc, vc, qm, km, state)
         ctx.call = (dims, float(eps), need, (q.dtype, k.dtype, v.dtype))
         return out.to(q.dtype)
 
     @staticmethod
     def backward(ctx, grad):
-        lib = _lib.load()
         qc, kc, vc, qm, km, state = ctx.saved_tensors
         dims, eps, need, dtypes = ctx.call
         dev = qc.device
         g = _f32c(grad, "grad")
         ws, wsp = _aligned_workspace(need, dev) if need else (None, None)
         d_q, d_k, d_v = torch.empty_like(qc), torch.empty_like(kc), torch.empty_like(vc)
-        _lib.check(lib.fm_linear_attention_backward(_ptr(qc), _ptr(kc), _ptr(vc), _ptr(qm), _ptr(km), _ptr(g), _ptr(state),
-                                                    *dims, eps, wsp, need, _ptr(d_q), _ptr(d_k), _ptr(d_v), _stream(dev)),
-                   "fm_linear_attention_backward")
+        _call("fm_linear_attention_backward", _ptr(qc), _ptr(kc), _ptr(vc), _ptr(qm), _ptr(km), _ptr(g), _ptr(state), *dims,
+              eps, wsp, need, _ptr(d_q), _ptr(d_k), _ptr(d_v), dev=dev)
         return d_q.to(dtypes[0]), d_k.to(dtypes[1]), d_v.to(dtypes[2]), None, None, None
 
 
@@ -1045,37 +1047,31 @@ class _EncoderTail(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, a, eps1, eps2, *params):
-        lib = _lib.load()
-        xc, ac = x.reshape(-1, 64).contiguous(), a.reshape(-1, 64).contiguous()
+        xc, ac = _rows64(x), _rows64(a)
         pc = [_f32c(p.detach(), "parameter") for p in params]
         t, dev = xc.shape[0], xc.device
-        state_bytes = int(lib.fm_encoder_tail_state_bytes(t, 64))
-        need = int(lib.fm_encoder_tail_workspace_bytes(t, 64))
+        state_bytes = int(_lib.load().fm_encoder_tail_state_bytes(t, 64))
         state = torch.empty(state_bytes // 4, dtype=torch.float32, device=dev) if state_bytes else None
-        ws, wsp = _aligned_workspace(need, dev)
+        ws, wsp, need = _workspace("fm_encoder_tail_workspace_bytes", dev, t, 64)
         y = torch.empty_like(xc)
-        _lib.check(lib.fm_encoder_tail_forward(_ptr(xc), _ptr(ac), *[_ptr(p) for p in pc], t, 64, float(eps1), float(eps2), wsp,
-                                               need, _ptr(state), _ptr(y), _stream(dev)), "fm_encoder_tail_forward")
+        _call("fm_encoder_tail_forward", _ptr(xc), _ptr(ac), *map(_ptr, pc), t, 64, float(eps1), float(eps2), wsp, need,
+              _ptr(state), _ptr(y), dev=dev)
         ctx.save_for_backward(xc, ac, state, *pc)
         ctx.call = (t, float(eps1), float(eps2), need, x.shape)
         return y.view(x.shape)
 
     @staticmethod
     def backward(ctx, grad):
-        lib = _lib.load()
         xc, ac, state, *pc = ctx.saved_tensors
         t, eps1, eps2, need, shape = ctx.call
         dev = xc.device
-        g = _f32c(grad, "grad").reshape(-1, 64).contiguous()
+        g = _rows64(_f32c(grad, "grad"))
         ws, wsp = _aligned_workspace(need, dev)
         d_x, d_a = torch.empty_like(xc), torch.empty_like(ac)
-        # parameter gradients: all seven or none (the kernels then skip that work)
-        d_p = [torch.empty_like(p) for p in pc] if any(ctx.needs_input_grad[4:]) else [None] * 7
-        _lib.check(lib.fm_encoder_tail_backward(_ptr(xc), _ptr(ac), *[_ptr(p) for p in pc], _ptr(g), _ptr(state), t, 64, eps1,
-                                                eps2, wsp, need, _ptr(d_x), _ptr(d_a), *[_ptr(p) for p in d_p],
-                                                _stream(dev)), "fm_encoder_tail_backward")
-        d_p = [d if want else None for d, want in zip(d_p, ctx.needs_input_grad[4:])]
-        return (d_x.view(shape), d_a.view(shape), None, None, *d_p)
+        d_p, d_p_back = _param_grads(pc, ctx.needs_input_grad[4:])       # all seven or none
+        _call("fm_encoder_tail_backward", _ptr(xc), _ptr(ac), *map(_ptr, pc), _ptr(g), _ptr(state), t, 64, eps1, eps2, wsp,
+              need, _ptr(d_x), _ptr(d_a), *map(_ptr, d_p), dev=dev)
+        return (d_x.view(shape), d_a.view(shape), None, None, *d_p_back)
 
 
 def encoder_tail(x: torch.Tensor, a: torch.Tensor, merge_w: torch.Tensor, ln1_w: torch.Tensor, ln1_b: torch.Tensor,
@@ -1122,17 +1118,15 @@ class _QkvProjection(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, source, wq, wk, wv):
-        lib = _lib.load()
         self_mode = source is None
-        xc = x.reshape(-1, 64).contiguous()
-        sc = xc if self_mode else source.reshape(-1, 64).contiguous()
+        xc = _rows64(x)
+        sc = xc if self_mode else _rows64(source)
         wc = [_f32c(w.detach(), "weight") for w in (wq, wk, wv)]
         tx, ts, dev = xc.shape[0], sc.shape[0], xc.device
-        need = int(lib.fm_qkv_projection_workspace_bytes(tx, ts, 64))
-        ws, wsp = _aligned_workspace(need, dev)
+        ws, wsp, need = _workspace("fm_qkv_projection_workspace_bytes", dev, tx, ts, 64)
         q, k, v = torch.empty_like(xc), torch.empty_like(sc), torch.empty_like(sc)
-        _lib.check(lib.fm_qkv_projection_forward(_ptr(xc), _ptr(sc), *[_ptr(w) for w in wc], tx, ts, 64, wsp, need, _ptr(q),
-                                                 _ptr(k), _ptr(v), _stream(dev)), "fm_qkv_projection_forward")
+        _call("fm_qkv_projection_forward", _ptr(xc), _ptr(sc), *map(_ptr, wc), tx, ts, 64, wsp, need, _ptr(q), _ptr(k),
+              _ptr(v), dev=dev)
         if self_mode:
             ctx.save_for_backward(xc, *wc)
         else:
@@ -1143,7 +1137,6 @@ class _QkvProjection(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gq, gk, gv):
-        lib = _lib.load()
         self_mode, need, x_shape, s_shape = ctx.call
         if self_mode:
             xc, *wc = ctx.saved_tensors
@@ -1151,17 +1144,14 @@ class _QkvProjection(torch.autograd.Function):
         else:
             xc, sc, *wc = ctx.saved_tensors
         tx, ts, dev = xc.shape[0], sc.shape[0], xc.device
-        g = [_f32c(t, "grad").reshape(-1, 64).contiguous() for t in (gq, gk, gv)]
+        g = [_rows64(_f32c(t, "grad")) for t in (gq, gk, gv)]
         ws, wsp = _aligned_workspace(need, dev)
         d_x = torch.empty_like(xc)
         d_src = None if self_mode else torch.empty_like(sc)
-        # weight gradients: all three or none (the kernels then skip that work)
-        d_w = [torch.empty_like(w) for w in wc] if any(ctx.needs_input_grad[2:]) else [None] * 3
-        _lib.check(lib.fm_qkv_projection_backward(_ptr(xc), _ptr(sc), *[_ptr(w) for w in wc], *[_ptr(t) for t in g], tx, ts,
-                                                  64, wsp, need, _ptr(d_x), _ptr(d_src), *[_ptr(w) for w in d_w],
-                                                  _stream(dev)), "fm_qkv_projection_backward")
-        d_w = [d if want else None for d, want in zip(d_w, ctx.needs_input_grad[2:])]
-        return (d_x.view(x_shape), None if self_mode else d_src.view(s_shape), *d_w)
+        d_w, d_w_back = _param_grads(wc, ctx.needs_input_grad[2:])         # all three or none
+        _call("fm_qkv_projection_backward", _ptr(xc), _ptr(sc), *map(_ptr, wc), *map(_ptr, g), tx, ts, 64, wsp, need,
+              _ptr(d_x), _ptr(d_src), *map(_ptr, d_w), dev=dev)
+        return (d_x.view(x_shape), None if self_mode else d_src.view(s_shape), *d_w_back)
 
 
 def qkv_projection(x: torch.Tensor, source: torch.Tensor, wq: torch.Tensor, wk: torch.Tensor, wv: torch.Tensor):
@@ -1195,25 +1185,22 @@ class _WindowMerge(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, feat_f, w_win, ctx_rows, b_ids, ids, w, stride, h_c, w_c, pad):
-        lib = _lib.load()
         layout = _stored_layout(feat_f)
         n, _, hf, wf = feat_f.shape
         dev, m_max = feat_f.device, int(b_ids.shape[0])
         wc, cc = _f32c(w_win.detach(), "w_win"), _f32c(ctx_rows.detach(), "ctx_rows")
         bb, ii = _i64c(b_ids), _i64c(ids)
         geom = (n, 64, hf, wf, layout, w, stride, pad, int(h_c), int(w_c))
-        need = int(lib.fm_window_merge_workspace_bytes(n, int(h_c), int(w_c), m_max, w))
-        ws, wsp = _aligned_workspace(need, dev)
+        ws, wsp, need = _workspace("fm_window_merge_workspace_bytes", dev, n, int(h_c), int(w_c), m_max, w)
         out = torch.empty(m_max, w * w, 64, dtype=torch.float32, device=dev)
-        _lib.check(lib.fm_window_merge_forward(_ptr(feat_f), *geom, _ptr(wc), _ptr(cc), _ptr(bb), _ptr(ii), m_max, wsp, need,
-                                               _ptr(out), _stream(dev)), "fm_window_merge_forward")
+        _call("fm_window_merge_forward", _ptr(feat_f), *geom, _ptr(wc), _ptr(cc), _ptr(bb), _ptr(ii), m_max, wsp, need,
+              _ptr(out), dev=dev)
         ctx.save_for_backward(feat_f, wc, cc, bb, ii)
         ctx.call = (geom, need, m_max)
         return out
 
     @staticmethod
     def backward(ctx, grad):
-        lib = _lib.load()
         feat_f, wc, cc, bb, ii = ctx.saved_tensors
         geom, need, m_max = ctx.call
         dev = feat_f.device
@@ -1225,9 +1212,8 @@ class _WindowMerge(torch.autograd.Function):
         if m_max == 0:
             d_feat = None if d_feat is None else d_feat.zero_()
             d_w = None if d_w is None else d_w.zero_()
-        _lib.check(lib.fm_window_merge_backward(_ptr(feat_f), *geom, _ptr(wc), _ptr(cc), _ptr(bb), _ptr(ii), m_max, _ptr(g),
-                                                wsp, need, _ptr(d_feat), _ptr(d_w), _ptr(d_ctx), _stream(dev)),
-                   "fm_window_merge_backward")
+        _call("fm_window_merge_backward", _ptr(feat_f), *geom, _ptr(wc), _ptr(cc), _ptr(bb), _ptr(ii), m_max, _ptr(g), wsp,
+              need, _ptr(d_feat), _ptr(d_w), _ptr(d_ctx), dev=dev)
         return (d_feat, d_w, d_ctx if ctx.needs_input_grad[2] else None,
                 None, None, None, None, None, None, None)
 
@@ -1316,8 +1302,7 @@ def pack_coarse_transformer(state_dict: dict, n_layers: int, device) -> torch.Te
     if nbytes == 0:
         raise ValueError(f"fm_coarse_transformer: unsupported layer count {n_layers}")
     packed = torch.empty(nbytes, dtype=torch.uint8, device=device)
-    _lib.check(lib.fm_coarse_tf_pack_weights(C.cast(table, C.c_void_p), n_layers, _ptr(packed), _stream(packed.device)),
-               "fm_coarse_tf_pack_weights")
+    _call("fm_coarse_tf_pack_weights", C.cast(table, C.c_void_p), n_layers, _ptr(packed), dev=packed.device)
     torch.cuda.current_stream(packed.device).synchronize()       # the sources in `keep` may be freed after this
     return packed
 
@@ -1348,9 +1333,8 @@ def coarse_transformer(feat0: torch.Tensor, feat1: torch.Tensor, packed: torch.T
             raise ValueError(f"{name} must be [{n}, {length}], got {tuple(m.shape)}")
         return (m != 0).to(device=feat0.device, dtype=torch.uint8).contiguous()
     m0, m1 = as_bytes(mask0, l, "mask0"), as_bytes(mask1, s, "mask1")
-    _lib.check(lib.fm_coarse_transformer_masked(_ptr(feat0), _ptr(feat1), _ptr(m0), _ptr(m1), n, l, s, c, nhead, kinds,
-                                                len(layer_names), _ptr(packed), _ptr(workspace), workspace.numel(),
-                                                _ptr(out0), _ptr(out1), _stream(feat0.device)), "fm_coarse_transformer_masked")
+    _call("fm_coarse_transformer_masked", _ptr(feat0), _ptr(feat1), _ptr(m0), _ptr(m1), n, l, s, c, nhead, kinds,
+          len(layer_names), _ptr(packed), _ptr(workspace), workspace.numel(), _ptr(out0), _ptr(out1), dev=feat0.device)
     out0._keep = (m0, m1)
     return out0, out1
 
@@ -1361,7 +1345,7 @@ def pack_fine_transformer(state_dict: dict, device) -> torch.Tensor:
     lib = _lib.load()
     keep, arrs = _tf_pointer_tables(state_dict, 2, device, "fine", 64)
     packed = torch.empty(int(lib.fm_fine_tf_packed_bytes()), dtype=torch.uint8, device=device)
-    _lib.check(lib.fm_fine_tf_pack_weights(arrs[0], arrs[1], _ptr(packed), _stream(packed.device)), "fm_fine_tf_pack_weights")
+    _call("fm_fine_tf_pack_weights", arrs[0], arrs[1], _ptr(packed), dev=packed.device)
     torch.cuda.current_stream(packed.device).synchronize()       # the sources in `keep` may be freed after this
     return packed
 

@@ -12,7 +12,6 @@ the records `dist.pack_records` produces and `dist.gather_match_lists` exchanges
 """
 from __future__ import annotations
 
-import ctypes as C
 import struct
 from collections import namedtuple
 from typing import Optional
@@ -22,6 +21,7 @@ import torch
 
 from . import _lib
 from .dist import RECORD, pack_records, unpack_records
+from .ops import _call, _ptr
 
 MAGIC = b"FMT1"
 VERSION = 1
@@ -33,7 +33,6 @@ def epipolar_errors(mkpts0: torch.Tensor, mkpts1: torch.Tensor, m_bids: torch.Te
     `count`: a tensor holding the number of rows, on any device and of any integer type (converted as estimate_poses
     converts it; a negative count is none).  A row behind the count, like a row whose id lies outside [0, N) - tested in
     64 bits, as estimate_poses tests it - reads NaN and not-inlier and is counted in no pair."""
-    lib = _lib.load()
     if not mkpts0.is_cuda:
         raise RuntimeError("mkpts0 must live on the GPU: the HIP path has no CPU fallback")
     dev = mkpts0.device
@@ -48,11 +47,8 @@ def epipolar_errors(mkpts0: torch.Tensor, mkpts1: torch.Tensor, m_bids: torch.Te
     inl = torch.zeros(m, dtype=torch.uint8, device=dev)
     per = torch.zeros(n, 2, dtype=torch.int32, device=dev)
     if m:
-        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        st = lib.fm_epipolar_errors(p(k0), p(k1), stride, p(m_bids.to(dev).long().contiguous()), p(count), m, n, p(T),
-                                    p(a0), p(a1), float(inlier_thr), p(epi), p(inl), p(per),
-                                    C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        _lib.check(st, "fm_epipolar_errors")
+        _call("fm_epipolar_errors", _ptr(k0), _ptr(k1), stride, _ptr(m_bids.to(dev).long().contiguous()), _ptr(count), m, n,
+              _ptr(T), _ptr(a0), _ptr(a1), float(inlier_thr), _ptr(epi), _ptr(inl), _ptr(per), dev=dev)
     return epi, inl.bool(), per
 
 
@@ -101,13 +97,11 @@ def estimate_poses(mkpts0: torch.Tensor, mkpts1: torch.Tensor, m_bids: torch.Ten
     E = torch.zeros(n, 3, 3, dtype=torch.float64, device=dev)
     inl = torch.zeros(m, dtype=torch.uint8, device=dev)
     per = torch.zeros(n, 4, dtype=torch.int32, device=dev)
-    p = lambda x: None if x is None else C.c_void_p(x.data_ptr())
     if m == 0:                                            # nothing to estimate from (and an empty tensor has no address)
         return Poses(R, t, E, inl.bool(), per, per[:, 3] != 0)
-    st = lib.fm_estimate_pose(p(k0), p(k1), stride, p(bids), p(count), m, n, p(a0), p(a1), float(pixel_thr), int(samples),
-                              int(seed) & 0xFFFFFFFFFFFFFFFF, p(ws), need, p(R), p(t), p(E), p(inl), p(per),
-                              C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    _lib.check(st, "fm_estimate_pose")
+    _call("fm_estimate_pose", _ptr(k0), _ptr(k1), stride, _ptr(bids), _ptr(count), m, n, _ptr(a0), _ptr(a1),
+          float(pixel_thr), int(samples), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(ws), need, _ptr(R), _ptr(t), _ptr(E),
+          _ptr(inl), _ptr(per), dev=dev)
     if order is not None:
         inl = torch.zeros_like(inl).index_copy_(0, order, inl)
     return Poses(R, t, E, inl.bool(), per, per[:, 3] != 0)

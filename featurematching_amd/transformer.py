@@ -81,24 +81,20 @@ class EncoderLayer(nn.Module):
         self.norm2 = nn.LayerNorm(d_model)
 
     def forward(self, x: torch.Tensor, source: torch.Tensor, x_mask=None, source_mask=None) -> torch.Tensor:
+        from . import ops
         n, l, _ = x.shape
         heads = lambda t: t.view(n, -1, self.nhead, self.dim)
         attn = linear_attention if self.attention == 'linear' else full_attention
         qkv = None
-        if self.hip_proj:
-            from . import ops
-            if ops.qkv_projection_supported(x, source):
-                qkv = ops.qkv_projection(x, source, self.q_proj.weight, self.k_proj.weight, self.v_proj.weight)
+        if self.hip_proj and ops.qkv_projection_supported(x, source):
+            qkv = ops.qkv_projection(x, source, self.q_proj.weight, self.k_proj.weight, self.v_proj.weight)
         if qkv is None:
             qkv = self.q_proj(x), self.k_proj(source), self.v_proj(source)
         q, k, v = heads(qkv[0]), heads(qkv[1]), heads(qkv[2])
-        if self.hip_attention and self.attention == 'linear':
-            from . import ops
-            if ops.linear_attention_supported(q, k):
-                attn = ops.linear_attention
+        if self.hip_attention and self.attention == 'linear' and ops.linear_attention_supported(q, k):
+            attn = ops.linear_attention
         msg = attn(q, k, v, q_mask=x_mask, kv_mask=source_mask)
         if self.hip_tail:
-            from . import ops
             msg = msg.reshape(n, l, -1)
             if ops.encoder_tail_supported(x, msg):
                 return ops.encoder_tail(x, msg, self.merge.weight, self.norm1.weight, self.norm1.bias, self.mlp[0].weight,
@@ -106,6 +102,18 @@ class EncoderLayer(nn.Module):
         msg = self.norm1(self.merge(msg.reshape(n, l, -1)))
         msg = self.norm2(self.mlp(torch.cat([x, msg], dim=2)))
         return x + msg
+
+
+def _layer_switch(name: str) -> property:
+    """A training switch of LocalFeatureTransformer.  It lives on the EncoderLayers, which are the ones that read it:
+    assigning it writes through to every layer, reading it says whether any layer has it on."""
+    def get(self):
+        return any(getattr(layer, name) for layer in self.layers)
+
+    def put(self, on):
+        for layer in self.layers:
+            setattr(layer, name, on)
+    return property(get, put)
 
 
 class LocalFeatureTransformer(nn.Module):
@@ -126,15 +134,16 @@ class LocalFeatureTransformer(nn.Module):
     fine level - the HIP attention core with its HIP backward (EncoderLayer); the eval-mode kernels are not affected.
     hip_tail=True (default False) gives them the fused HIP tail with its HIP backward (EncoderLayer; d_model 64 only).
     hip_proj=True (default False) gives them the fused q / k / v projections with their HIP backward (EncoderLayer;
-    d_model 64 only): with all three switches a training-mode fine layer is three HIP ops each way."""
+    d_model 64 only): with all three switches a training-mode fine layer is three HIP ops each way.  The three are
+    attributes too: `tf.hip_tail = True` after construction switches every layer."""
 
     _warned_detached = False
+    hip_attention, hip_tail, hip_proj = (_layer_switch(k) for k in ("hip_attention", "hip_tail", "hip_proj"))
 
     def __init__(self, config, use_hip: bool = True, check_range: bool = True, inference_only: bool = True,
                  hip_attention: bool = False, hip_tail: bool = False, hip_proj: bool = False):
         super().__init__()
         self.use_hip, self.check_range, self.inference_only = use_hip, check_range, inference_only
-        self.hip_attention, self.hip_tail, self.hip_proj = hip_attention, hip_tail, hip_proj
         self.range_fallbacks = 0
         self.last_status = None
         self.attention = config.get('attention', 'linear')

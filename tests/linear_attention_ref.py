@@ -6,6 +6,8 @@ import torch
 
 from featurematching_amd import synth
 
+from train_layers_yardstick import rel_err  # noqa: F401  (the error measure of the GPU tests)
+
 # the fixture's cases: name -> ((N, L, S, H, D), masked)
 GOLDEN_CASES = {
     "window": ((3, 25, 49, 8, 8), False),
@@ -49,10 +51,3 @@ def autograd(fn, q, k, v, g, q_mask=None, kv_mask=None):
     out = fn(q, k, v, q_mask=q_mask, kv_mask=kv_mask)
     out.backward(g)
     return out.detach(), q.grad, k.grad, v.grad
-
-
-def rel_err(x, ref):
-    """max|x - ref| / max|ref| (0 for an all-zero reference that is met exactly)"""
-    top = ref.abs().max().item()
-    err = (x.double() - ref).abs().max().item()
-    return err / top if top > 0 else err

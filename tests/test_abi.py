@@ -57,6 +57,58 @@ def test_header_symbols_are_exported():
         assert hasattr(lib, s), f"{s} declared in fm_debug.h but not exported"
 
 
+def declared_prototypes(path=("include", "fmatch.h")):
+    """[(name, return type, [argument types])] of every `fm_*` prototype of a header, the types as C spells them without
+    `const` and parameter names ("int", "float*", "void**"): comments and preprocessor lines stripped first"""
+    text = open(os.path.join(ROOT, *path)).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = re.sub(r"//[^\n]*|^\s*#[^\n]*", "", text, flags=re.M)
+
+    def spelled(decl, named):
+        decl = re.sub(r"\s*\*\s*", "* ", re.sub(r"\bconst\b", " ", decl))
+        words = decl.split()
+        if named and len(words) > 1 and not words[-1].endswith("*"):
+            words = words[:-1]                                       # the parameter's name
+        return " ".join(words).replace("* ", "*").replace(" *", "*")
+
+    protos = []
+    for ret, name, args in re.findall(r"([A-Za-z_][\w\s\*]*?)\b(fm_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", text):
+        args = [] if args.strip() in ("", "void") else [spelled(a, True) for a in args.split(",")]
+        protos.append((name, spelled(ret, False), args))
+    return protos
+
+
+C_SCALARS = {"int": C.c_int, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t, "uint64_t": C.c_uint64,
+             "int32_t": C.c_int32, "int64_t": C.c_int64, "unsigned char": C.c_ubyte}
+
+
+def _same_kind(decl, ctype):
+    """a scalar is its ctypes type; any pointer is c_void_p, or POINTER of a type its pointee is the same kind as"""
+    if not decl.endswith("*"):
+        return decl in C_SCALARS and ctype == C_SCALARS[decl]
+    if ctype == C.c_void_p:
+        return True
+    return isinstance(ctype, type) and issubclass(ctype, C._Pointer) and _same_kind(decl[:-1], ctype._type_)
+
+
+def test_signature_table_matches_the_header_prototypes():
+    """Every row of _lib.ALL_SIGNATURES against the prototype it stands for, in include/fmatch.h or csrc/fm_debug.h: the
+    argument count, the return type and every argument's kind.  (_lib.load() assigns the table to the loaded functions,
+    so a wrong row is what ctypes converts the arguments by: a pointer declared `int` reaches the kernel truncated.)"""
+    protos = declared_prototypes() + declared_prototypes(("featurematching_amd", "csrc", "fm_debug.h"))
+    assert len(protos) >= 81                                         # (the parser reads: 69 + 12 when this was written)
+    names = [name for name, _, _ in protos]
+    assert len(set(names)) == len(names) and set(names) == set(_lib.ALL_SIGNATURES)
+    assert ("fm_strerror", "char*", ["int"]) in protos and ("fm_fine_tf_packed_bytes", "size_t", []) in protos
+    for name, ret, args in protos:
+        restype, argtypes = _lib.ALL_SIGNATURES[name]
+        assert len(argtypes) == len(args), f"{name}: {len(args)} arguments declared, {len(argtypes)} in _lib"
+        want = C.c_char_p if ret == "char*" else C_SCALARS.get(ret)      # a string or a scalar: nothing else is returned
+        assert want is not None and restype == want, f"{name}: returns {ret}, _lib says {restype}"
+        for k, (decl, ctype) in enumerate(zip(args, argtypes)):
+            assert _same_kind(decl, ctype), f"{name}: argument {k} is {decl}, _lib says {ctype}"
+
+
 def test_version_and_messages():
     lib = _lib.load()
     assert lib.fm_version() == 100

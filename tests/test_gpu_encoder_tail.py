@@ -18,9 +18,10 @@ slice from 9 workgroups = 1025 tokens).  T is not chunked on the host."""
 import pytest
 import torch
 
-from featurematching_amd import _lib, ops, synth, transformer
+from featurematching_amd import _lib, ops, synth
 
 import encoder_tail_ref as tref
+import train_layers_yardstick as yard
 
 pytestmark = pytest.mark.gpu
 
@@ -50,17 +51,8 @@ def _three(x, a, gy, params, **kw):
 
 
 def _hold(tag, hip, ref32, ref64, names=tref.NAMES):
-    """print every figure, then hold every tensor to the bar"""
-    rows = []
-    for name, h, r32, r64 in zip(names, hip, ref32, ref64):
-        assert h.shape == r64.shape and h.dtype == torch.float32, (tag, name)
-        finite = bool(torch.isfinite(h).all())
-        e_hip, e_ref = tref.rel_err(h, r64), tref.rel_err(r32, r64)
-        print(f"ACC  {tag:34s} {name:22s} max|ref64| {r64.abs().max().item():.3e}  e_ref {e_ref:.3e}  e_hip {e_hip:.3e}")
-        rows.append((name, finite, e_hip, e_ref))
-    for name, finite, e_hip, e_ref in rows:
-        assert finite, (tag, name)
-        assert e_hip <= 4 * e_ref + FLOOR, (tag, name, e_hip, e_ref)
+    """print every figure, then hold every tensor to the bar, at this file's floor"""
+    yard.hold(tag, names, hip, ref32, ref64, FLOOR)
 
 
 def _check(tag, seed, shape, **kw):
@@ -152,29 +144,7 @@ def test_same_bits_on_every_call():
 
 
 # ---- the modules ---------------------------------------------------------------------------------------------------
-def _module(cfg, dtype=torch.float32, **kw):
-    m = transformer.LocalFeatureTransformer(cfg, **kw)
-    m.load_state_dict({k: torch.as_tensor(v) for k, v in
-                       synth.transformer_weights(7, cfg['d_model'], len(cfg['layer_names'])).items()})
-    return m.to(device=DEV, dtype=dtype).train()
-
-
-def _module_run(m, x0, x1, g0, g1, dtype, **kw):
-    a, b = (t.detach().to(dtype, copy=True).requires_grad_(True) for t in (x0, x1))
-    o0, o1 = m(a, b, **kw)
-    assert o0.grad_fn is not None and o1.grad_fn is not None
-    torch.autograd.backward([o0, o1], [g0.to(dtype), g1.to(dtype)])
-    grads = {k: p.grad for k, p in m.named_parameters()}
-    assert all(p is not None for p in grads.values()), [k for k, p in grads.items() if p is None]
-    keys = sorted(grads)
-    return ["out0", "out1", "d_feat0", "d_feat1"] + keys, [o0.detach(), o1.detach(), a.grad, b.grad] + [grads[k] for k in keys]
-
-
-def _count_calls(monkeypatch):
-    calls = []
-    real = ops.encoder_tail
-    monkeypatch.setattr(ops, "encoder_tail", lambda *a, **kw: (calls.append(1), real(*a, **kw))[1])
-    return calls
+_module, _module_run = yard.module, yard.module_run
 
 
 @pytest.mark.parametrize("masked", [False, True])
@@ -189,43 +159,29 @@ def test_module_training_step(monkeypatch, masked):
         for b in range(130):
             mask0[b, :max(1, 49 - (3 * b + 4) % 49)] = True
         kw = {'mask0': mask0}
-    calls = _count_calls(monkeypatch)
+    calls = yard.count_calls(monkeypatch, "encoder_tail")
     names, hip = _module_run(_module(FINE, hip_attention=True, hip_tail=True), x0, x1, g0, g1, torch.float32, **kw)
-    assert len(calls) == 4                                           # self x 2, cross x 2: every layer call took the HIP tail
+    assert calls == {"encoder_tail": 4}                              # self x 2, cross x 2: every layer call took the HIP tail
     _, ref32 = _module_run(_module(FINE, hip_attention=True), x0, x1, g0, g1, torch.float32, **kw)
-    assert len(calls) == 4
+    assert calls == {"encoder_tail": 4}
     _, ref64 = _module_run(_module(FINE, dtype=torch.float64, hip_attention=True, hip_tail=True), x0, x1, g0, g1,
                            torch.float64, **kw)
-    assert len(calls) == 4                                           # float64 tensors: the torch lines
+    assert calls == {"encoder_tail": 4}                              # float64 tensors: the torch lines
     _hold("module fine" + (" masked" if masked else ""), hip, ref32, ref64, names)
 
 
 def test_module_d256_takes_the_torch_lines(monkeypatch):
     cfg = {'d_model': 256, 'nhead': 8, 'layer_names': ['self', 'cross']}
     x0, x1 = (torch.as_tensor(synth.normal(910, i, (2, 60, 256)), device=DEV) for i in (1, 2))
-    calls = _count_calls(monkeypatch)
+    calls = yard.count_calls(monkeypatch, "encoder_tail")
     _, on = _module_run(_module(cfg, hip_tail=True), x0, x1, x1, x0, torch.float32)
     _, off = _module_run(_module(cfg), x0, x1, x1, x0, torch.float32)
-    assert not calls
+    assert calls == {"encoder_tail": 0}
     for u, v in zip(on, off):
         assert torch.equal(u, v)
 
 
 # ---- memory --------------------------------------------------------------------------------------------------------
-def _peak_above_inputs(fn, x, a, gy, params):
-    x, a = (t.detach().requires_grad_(True) for t in (x, a))
-    params = [p.detach().requires_grad_(True) for p in params]
-    torch.cuda.synchronize()
-    torch.cuda.reset_peak_memory_stats()
-    base = torch.cuda.memory_allocated()
-    y = fn(x, a, *params)
-    grads = torch.autograd.grad(y, [x, a] + params, gy)
-    torch.cuda.synchronize()
-    peak = torch.cuda.max_memory_allocated() - base
-    del y, grads
-    return peak
-
-
 def test_peak_memory():
     """forward + backward at [2000 * 49, 64] allocate y, dx, da, the seven parameter gradients, the state and one workspace,
     and nothing of the tensors' size besides: none of the six tensors torch's autograd keeps per call"""
@@ -242,8 +198,8 @@ def test_peak_memory():
     state, ws = lib.fm_encoder_tail_state_bytes(T, 64), lib.fm_encoder_tail_workspace_bytes(T, 64)
     assert state <= 16 * T and 0 < ws <= 64 << 20
     allowed = 3 * T * 64 * 4 + sum(p.numel() * 4 for p in params) + state + ws + (1 << 20)
-    peak_hip = _peak_above_inputs(_hip, x, a, gy, params)
-    peak_torch = _peak_above_inputs(tref.tail, x, a, gy, params)
+    peak_hip = yard.peak_above_inputs(_hip, [x, a] + params, gy)
+    peak_torch = yard.peak_above_inputs(tref.tail, [x, a] + params, gy)
     print(f"MEM  tail T{T}  hip {peak_hip} B  allowed {allowed} B  torch {peak_torch} B  ({peak_torch / max(peak_hip, 1):.2f} x)")
     assert peak_hip <= allowed, (peak_hip, allowed)
 

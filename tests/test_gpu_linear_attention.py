@@ -20,6 +20,7 @@ import torch
 from featurematching_amd import _lib, ops, synth, transformer
 
 import linear_attention_ref as lref
+import train_layers_yardstick as yard
 
 pytestmark = pytest.mark.gpu
 
@@ -53,17 +54,8 @@ def _three(case):
 
 
 def _hold(tag, hip, ref32, ref64, names=NAMES):
-    """print every figure, then hold every tensor to the bar"""
-    rows = []
-    for name, h, r32, r64 in zip(names, hip, ref32, ref64):
-        assert h.shape == r64.shape and h.dtype == torch.float32, (tag, name)
-        finite = bool(torch.isfinite(h).all())
-        e_hip, e_ref = lref.rel_err(h, r64), lref.rel_err(r32, r64)
-        print(f"ACC  {tag:34s} {name:22s} max|ref64| {r64.abs().max().item():.3e}  e_ref {e_ref:.3e}  e_hip {e_hip:.3e}")
-        rows.append((name, finite, e_hip, e_ref))
-    for name, finite, e_hip, e_ref in rows:
-        assert finite, (tag, name)
-        assert e_hip <= 4 * e_ref + FLOOR, (tag, name, e_hip, e_ref)
+    """print every figure, then hold every tensor to the bar, at this file's floor"""
+    yard.hold(tag, names, hip, ref32, ref64, FLOOR)
 
 
 def _check(tag, dims, seed, **kw):
@@ -183,29 +175,7 @@ def test_supported_mirrors_the_route_table():
 
 
 # ---- the modules ---------------------------------------------------------------------------------------------------
-def _module(cfg, dtype=torch.float32, **kw):
-    m = transformer.LocalFeatureTransformer(cfg, **kw)
-    m.load_state_dict({k: torch.as_tensor(v) for k, v in
-                       synth.transformer_weights(7, cfg['d_model'], len(cfg['layer_names'])).items()})
-    return m.to(device=DEV, dtype=dtype).train()
-
-
-def _module_run(m, x0, x1, g0, g1, dtype):
-    a, b = (t.detach().to(dtype, copy=True).requires_grad_(True) for t in (x0, x1))
-    o0, o1 = m(a, b)
-    assert o0.grad_fn is not None and o1.grad_fn is not None
-    torch.autograd.backward([o0, o1], [g0.to(dtype), g1.to(dtype)])
-    grads = {k: p.grad for k, p in m.named_parameters()}
-    assert all(p is not None for p in grads.values()), [k for k, p in grads.items() if p is None]
-    keys = sorted(grads)
-    return ["out0", "out1", "d_feat0", "d_feat1"] + keys, [o0.detach(), o1.detach(), a.grad, b.grad] + [grads[k] for k in keys]
-
-
-def _count_calls(monkeypatch):
-    calls = []
-    real = ops.linear_attention
-    monkeypatch.setattr(ops, "linear_attention", lambda *a, **kw: (calls.append(1), real(*a, **kw))[1])
-    return calls
+_module, _module_run = yard.module, yard.module_run
 
 
 @pytest.mark.parametrize("name,d_model,shape0,shape1", [("fine", 64, (130, 49), (130, 49)), ("coarse", 256, (2, 300), (2, 200))])
@@ -215,13 +185,13 @@ def test_module_training_step(monkeypatch, name, d_model, shape0, shape1):
     cfg = {'d_model': d_model, 'nhead': 8, 'layer_names': ['self', 'cross']}
     x0, x1 = (torch.as_tensor(synth.normal(900, i, (*s, d_model)), device=DEV) for i, s in ((1, shape0), (2, shape1)))
     g0, g1 = (torch.as_tensor(synth.normal(900, i, (*s, d_model)), device=DEV) for i, s in ((3, shape0), (4, shape1)))
-    calls = _count_calls(monkeypatch)
+    calls = yard.count_calls(monkeypatch, "linear_attention")
     names, hip = _module_run(_module(cfg, hip_attention=True), x0, x1, g0, g1, torch.float32)
-    assert len(calls) == 4                                           # self x 2, cross x 2: every layer call took the HIP op
+    assert calls == {"linear_attention": 4}                          # self x 2, cross x 2: every layer call took the HIP op
     _, ref32 = _module_run(_module(cfg), x0, x1, g0, g1, torch.float32)
-    assert len(calls) == 4
+    assert calls == {"linear_attention": 4}
     _, ref64 = _module_run(_module(cfg, dtype=torch.float64, hip_attention=True), x0, x1, g0, g1, torch.float64)
-    assert len(calls) == 4                                           # float64 tensors: the torch function
+    assert calls == {"linear_attention": 4}                          # float64 tensors: the torch function
     _hold(f"module {name}", hip, ref32, ref64, names)
 
 
@@ -230,28 +200,15 @@ def test_module_takes_the_torch_function_for_unsupported_shapes(monkeypatch, d_m
     """D = 16, and 65 tokens at D = 8: hip_attention=True computes what hip_attention=False computes, bit for bit"""
     cfg = {'d_model': d_model, 'nhead': 8, 'layer_names': ['self', 'cross']}
     x0, x1 = (torch.as_tensor(synth.normal(910, i, (3, tokens, d_model)), device=DEV) for i in (1, 2))
-    calls = _count_calls(monkeypatch)
+    calls = yard.count_calls(monkeypatch, "linear_attention")
     _, on = _module_run(_module(cfg, hip_attention=True), x0, x1, x1, x0, torch.float32)
     _, off = _module_run(_module(cfg), x0, x1, x1, x0, torch.float32)
-    assert not calls
+    assert calls == {"linear_attention": 0}
     for a, b in zip(on[:4], off[:4]):
         assert torch.equal(a, b)
 
 
 # ---- memory --------------------------------------------------------------------------------------------------------
-def _peak_above_inputs(fn, q, k, v, g):
-    q, k, v = (t.detach().requires_grad_(True) for t in (q, k, v))
-    torch.cuda.synchronize()
-    torch.cuda.reset_peak_memory_stats()
-    base = torch.cuda.memory_allocated()
-    out = fn(q, k, v)
-    grads = torch.autograd.grad(out, (q, k, v), g)
-    torch.cuda.synchronize()
-    peak = torch.cuda.max_memory_allocated() - base
-    del out, grads
-    return peak
-
-
 def test_window_route_memory():
     """forward + backward at M = 2000, WW = 49 allocate the four results and nothing of their size besides"""
     dims = (2000, 49, 49, 8, 8)
@@ -265,8 +222,8 @@ def test_window_route_memory():
     state, ws = lib.fm_linear_attention_state_bytes(*dims), lib.fm_linear_attention_workspace_bytes(*dims)
     assert state == 0 and ws == 0
     allowed = q.numel() * 4 + q.numel() * 4 + 2 * k.numel() * 4 + state + ws + 4 * 512     # out, dq, dk, dv
-    peak_hip = _peak_above_inputs(_hip, q, k, v, g)
-    peak_torch = _peak_above_inputs(transformer.linear_attention, q, k, v, g)
+    peak_hip = yard.peak_above_inputs(_hip, (q, k, v), g)
+    peak_torch = yard.peak_above_inputs(transformer.linear_attention, (q, k, v), g)
     print(f"MEM  window M2000 WW49  hip {peak_hip} B  allowed {allowed} B  torch {peak_torch} B  "
           f"({peak_torch / max(peak_hip, 1):.2f} x)")
     assert peak_hip <= allowed, (peak_hip, allowed)

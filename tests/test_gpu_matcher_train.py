@@ -6,12 +6,13 @@ Images 1 x 3 x 96 x 128 (coarse grid 12 x 16, fine maps 48 x 64, W = 7) with 300
 import pytest
 import torch
 
-from featurematching_amd import modules, ops, supervision, synth
+from featurematching_amd import modules, supervision, synth
 from featurematching_amd.matcher import Matcher
 from featurematching_amd.transformer import LocalFeatureTransformer
 
 import matcher_train_ref as mref
 import supervision_ref as sref
+from train_layers_yardstick import count_calls
 
 pytestmark = pytest.mark.gpu
 HC, WC, HF, WF, DEV = mref.HC, mref.WC, mref.HF, mref.WF, mref.DEV
@@ -26,16 +27,6 @@ def deterministic_torch():
     torch.use_deterministic_algorithms(True, warn_only=True)
     yield
     torch.use_deterministic_algorithms(before[0], warn_only=before[1])
-
-
-def _count_calls(monkeypatch):
-    calls = {k: 0 for k in OPS}
-    for name in OPS:
-        def counted(*a, _real=getattr(ops, name), _name=name, **kw):
-            calls[_name] += 1
-            return _real(*a, **kw)
-        monkeypatch.setattr(ops, name, counted)
-    return calls
 
 
 # ---- (a) -------------------------------------------------------------------------------------------------------------
@@ -136,7 +127,7 @@ def test_hip_train_on_against_off(monkeypatch, deterministic_torch):
     off = _matcher(hip_train=False, patches=True, fixture_merge=True)
     on = _matcher(hip_train=True, patches=True, fixture_merge=True)
     on.load_state_dict(off.state_dict())
-    calls = _count_calls(monkeypatch)
+    calls = count_calls(monkeypatch, *OPS)
     loss_off, g_off = _step(off, _data(62, grad=True))
     assert calls == {k: 0 for k in OPS}
     loss_on, g_on = _step(on, _data(62, grad=True))

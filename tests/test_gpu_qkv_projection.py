@@ -18,9 +18,10 @@ mode).  The token counts are not chunked on the host."""
 import pytest
 import torch
 
-from featurematching_amd import _lib, ops, synth, transformer
+from featurematching_amd import _lib, ops, synth
 
 import qkv_projection_ref as qref
+import train_layers_yardstick as yard
 
 pytestmark = pytest.mark.gpu
 
@@ -49,18 +50,8 @@ def _names(src):
 
 
 def _hold(tag, hip, ref32, ref64, names):
-    """print every figure, then hold every tensor to the bar"""
-    assert len(hip) == len(ref32) == len(ref64) and len(hip) <= len(names), tag
-    rows = []
-    for name, h, r32, r64 in zip(names, hip, ref32, ref64):
-        assert h.shape == r64.shape and h.dtype == torch.float32, (tag, name)
-        finite = bool(torch.isfinite(h).all())
-        e_hip, e_ref = qref.rel_err(h, r64), qref.rel_err(r32, r64)
-        print(f"ACC  {tag:34s} {name:22s} max|ref64| {r64.abs().max().item():.3e}  e_ref {e_ref:.3e}  e_hip {e_hip:.3e}")
-        rows.append((name, finite, e_hip, e_ref))
-    for name, finite, e_hip, e_ref in rows:
-        assert finite, (tag, name)
-        assert e_hip <= 4 * e_ref + FLOOR, (tag, name, e_hip, e_ref)
+    """print every figure, then hold every tensor to the bar, at this file's floor"""
+    yard.hold(tag, names, hip, ref32, ref64, FLOOR)
 
 
 def _check(tag, seed, x_shape, s_shape=None, **kw):
@@ -192,8 +183,8 @@ def test_self_mode_is_the_sum_of_cross_mode():
     summed = cross[:3] + (cross[3] + cross[4],) + cross[5:]
     _hold("regular self T6370", self_, ref32, ref64, qref.NAMES_SELF)
     _hold("regular self = cross dx + dsrc", summed, ref32, ref64, qref.NAMES_SELF)
-    apart = qref.rel_err(self_[3], summed[3].double())               # and the two against each other, at the same bar
-    assert apart <= 4 * qref.rel_err(ref32[3], ref64[3]) + FLOOR, apart
+    apart = yard.rel_err(self_[3], summed[3].double())               # and the two against each other, at the same bar
+    assert apart <= 4 * yard.rel_err(ref32[3], ref64[3]) + FLOOR, apart
     for u, v in zip(self_[:3], cross[:3]):                           # q, k, v: the same k-ordered chains in either mode
         assert torch.equal(u, v)
     xg = x.detach().clone().requires_grad_(True)
@@ -216,29 +207,7 @@ def test_same_bits_on_every_call(cross):
 
 
 # ---- the modules ---------------------------------------------------------------------------------------------------
-def _module(cfg, dtype=torch.float32, **kw):
-    m = transformer.LocalFeatureTransformer(cfg, **kw)
-    m.load_state_dict({k: torch.as_tensor(v) for k, v in
-                       synth.transformer_weights(7, cfg['d_model'], len(cfg['layer_names'])).items()})
-    return m.to(device=DEV, dtype=dtype).train()
-
-
-def _module_run(m, x0, x1, g0, g1, dtype, **kw):
-    a, b = (t.detach().to(dtype, copy=True).requires_grad_(True) for t in (x0, x1))
-    o0, o1 = m(a, b, **kw)
-    assert o0.grad_fn is not None and o1.grad_fn is not None
-    torch.autograd.backward([o0, o1], [g0.to(dtype), g1.to(dtype)])
-    grads = {k: p.grad for k, p in m.named_parameters()}
-    assert all(p is not None for p in grads.values()), [k for k, p in grads.items() if p is None]
-    keys = sorted(grads)
-    return ["out0", "out1", "d_feat0", "d_feat1"] + keys, [o0.detach(), o1.detach(), a.grad, b.grad] + [grads[k] for k in keys]
-
-
-def _count_calls(monkeypatch):
-    calls = []
-    real = ops.qkv_projection
-    monkeypatch.setattr(ops, "qkv_projection", lambda *a, **kw: (calls.append(1), real(*a, **kw))[1])
-    return calls
+_module, _module_run = yard.module, yard.module_run
 
 
 @pytest.mark.parametrize("masked", [False, True])
@@ -253,43 +222,29 @@ def test_module_training_step(monkeypatch, masked):
         for b in range(130):
             mask0[b, :max(1, 49 - (3 * b + 4) % 49)] = True
         kw = {'mask0': mask0}
-    calls = _count_calls(monkeypatch)
+    calls = yard.count_calls(monkeypatch, "qkv_projection")
     switches = dict(hip_attention=True, hip_tail=True)
     names, hip = _module_run(_module(FINE, hip_proj=True, **switches), x0, x1, g0, g1, torch.float32, **kw)
-    assert len(calls) == 4                                           # self x 2, cross x 2: every layer call took the HIP op
+    assert calls == {"qkv_projection": 4}                            # self x 2, cross x 2: every layer call took the HIP op
     _, ref32 = _module_run(_module(FINE, **switches), x0, x1, g0, g1, torch.float32, **kw)
-    assert len(calls) == 4
+    assert calls == {"qkv_projection": 4}
     _, ref64 = _module_run(_module(FINE, dtype=torch.float64, hip_proj=True, **switches), x0, x1, g0, g1, torch.float64, **kw)
-    assert len(calls) == 4                                           # float64 tensors: the torch lines
+    assert calls == {"qkv_projection": 4}                            # float64 tensors: the torch lines
     _hold("module fine" + (" masked" if masked else ""), hip, ref32, ref64, names)
 
 
 def test_module_d256_takes_the_torch_lines(monkeypatch):
     cfg = {'d_model': 256, 'nhead': 8, 'layer_names': ['self', 'cross']}
     x0, x1 = (torch.as_tensor(synth.normal(910, i, (2, 60, 256)), device=DEV) for i in (1, 2))
-    calls = _count_calls(monkeypatch)
+    calls = yard.count_calls(monkeypatch, "qkv_projection")
     _, on = _module_run(_module(cfg, hip_proj=True), x0, x1, x1, x0, torch.float32)
     _, off = _module_run(_module(cfg), x0, x1, x1, x0, torch.float32)
-    assert not calls
+    assert calls == {"qkv_projection": 0}
     for u, v in zip(on, off):
         assert torch.equal(u, v)
 
 
 # ---- memory --------------------------------------------------------------------------------------------------------
-def _peak_above_inputs(fn, x, g, weights):
-    x = x.detach().requires_grad_(True)
-    weights = [w.detach().requires_grad_(True) for w in weights]
-    torch.cuda.synchronize()
-    torch.cuda.reset_peak_memory_stats()
-    base = torch.cuda.memory_allocated()
-    out = fn(x, x, *weights)
-    grads = torch.autograd.grad(list(out), [x] + weights, list(g))
-    torch.cuda.synchronize()
-    peak = torch.cuda.max_memory_allocated() - base
-    del out, grads
-    return peak
-
-
 def test_peak_memory():
     """forward + backward in self mode at [2000 * 49, 64] allocate q, k, v, dx, the three weight gradients and one workspace
     per call, and nothing of the tensors' size besides (torch saves only the inputs here too: no ratio is asserted)"""
@@ -306,8 +261,9 @@ def test_peak_memory():
     assert 0 < ws <= 64 << 20
     # q, k, v and dx; the weight gradients; the forward's workspace is released before the backward takes its own
     allowed = 4 * T * 64 * 4 + 3 * 64 * 64 * 4 + ws + (1 << 20)
-    peak_hip = _peak_above_inputs(ops.qkv_projection, x, (gq, gk, gv), weights)
-    peak_torch = _peak_above_inputs(qref.proj, x, (gq, gk, gv), weights)
+    self_mode = lambda fn: lambda x, *w: fn(x, x, *w)
+    peak_hip = yard.peak_above_inputs(self_mode(ops.qkv_projection), [x] + weights, (gq, gk, gv))
+    peak_torch = yard.peak_above_inputs(self_mode(qref.proj), [x] + weights, (gq, gk, gv))
     print(f"MEM  qkv T{T}  hip {peak_hip} B  allowed {allowed} B  torch {peak_torch} B  ({peak_torch / max(peak_hip, 1):.2f} x)")
     assert peak_hip <= allowed, (peak_hip, allowed)
 

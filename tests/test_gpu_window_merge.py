@@ -20,6 +20,7 @@ import torch
 
 from featurematching_amd import _lib, modules, ops, synth
 
+import train_layers_yardstick as yard
 import window_merge_ref as wref
 from helpers import case_inputs, load_golden
 
@@ -47,18 +48,9 @@ def _three(case, w, stride, hc, wc, pad, layout, **kw):
 
 
 def _hold(tag, hip, ref32, ref64, names=wref.NAMES):
-    """print every figure, then hold every tensor to the bar"""
-    assert len(hip) == len(ref32) == len(ref64) == len(names), tag
-    rows = []
-    for name, h, r32, r64 in zip(names, hip, ref32, ref64):
-        assert h.shape == r64.shape and h.dtype == torch.float32, (tag, name)
-        finite = bool(torch.isfinite(h).all())
-        e_hip, e_ref = wref.rel_err(h, r64), wref.rel_err(r32, r64)
-        print(f"ACC  {tag:34s} {name:22s} max|ref64| {r64.abs().max().item():.3e}  e_ref {e_ref:.3e}  e_hip {e_hip:.3e}")
-        rows.append((name, finite, e_hip, e_ref))
-    for name, finite, e_hip, e_ref in rows:
-        assert finite, (tag, name)
-        assert e_hip <= 4 * e_ref + FLOOR, (tag, name, e_hip, e_ref)
+    """print every figure, then hold every tensor to the bar, at this file's floor; here every name has its tensor"""
+    assert len(hip) == len(names), tag
+    yard.hold(tag, names, hip, ref32, ref64, FLOOR)
 
 
 def _check(tag, seed, m, w, layout, stride=wref.STRIDE, pad=wref.PAD, **kw):
@@ -245,9 +237,9 @@ def test_module_forward_against_the_reference_fixture(monkeypatch):
     dev = lambda a: torch.as_tensor(a, device=DEV)
     data = {'hw0_f': c['hw_f'], 'hw0_c': c['hw_c'], 'hw1_c': c['hw_c'], 'b_ids': dev(g['b_ids'].astype(np.int64)),
             'i_ids': dev(g['i_ids'].astype(np.int64)), 'j_ids': dev(g['j_ids'].astype(np.int64))}
-    calls = _count_calls(monkeypatch)
+    calls = yard.count_calls(monkeypatch, "window_merge")
     got = fp(dev(c['ff0']), dev(c['ff1']), dev(c['f0']), dev(c['f1']), data)
-    assert len(calls) == 2 and all(t.grad_fn is not None for t in got)
+    assert calls == {"window_merge": 2} and all(t.grad_fn is not None for t in got)
     pos = torch.arange(1, w * w + 1, dtype=torch.float64).view(1, w * w, 1)
     ch = torch.arange(1, 65, dtype=torch.float64).view(1, 1, -1)
     for t, key in zip(got, ('merged0', 'merged1')):
@@ -258,13 +250,6 @@ def test_module_forward_against_the_reference_fixture(monkeypatch):
 
 
 # ---- the module ----------------------------------------------------------------------------------------------------
-def _count_calls(monkeypatch):
-    calls = []
-    real = ops.window_merge
-    monkeypatch.setattr(ops, "window_merge", lambda *a, **kw: (calls.append(1), real(*a, **kw))[1])
-    return calls
-
-
 def _module_run(fp, maps, descs, data, grads, dtype, memory_format=torch.contiguous_format):
     leaves = [t.detach().to(dtype, copy=True) for t in maps + descs]
     leaves = [t.contiguous(memory_format=memory_format) if t.dim() == 4 else t for t in leaves]
@@ -299,37 +284,24 @@ def test_module_training_step(monkeypatch, layout):
         torch.manual_seed(9)
         return modules.FinePreprocess(cfg, **kw).to(device=DEV, dtype=dtype).train()
 
-    calls = _count_calls(monkeypatch)
+    calls = yard.count_calls(monkeypatch, "window_merge")
     names, hip = _module_run(module(hip_merge=True), maps, descs, data, grads, torch.float32, LAYOUTS[layout])
-    assert len(calls) == 2                                           # once per image
+    assert calls == {"window_merge": 2}                              # once per image
     assert hip[2].is_contiguous(memory_format=LAYOUTS[layout]) and hip[3].is_contiguous(memory_format=LAYOUTS[layout])
     _, ref32 = _module_run(module(), maps, descs, data, grads, torch.float32)
-    assert len(calls) == 2
+    assert calls == {"window_merge": 2}
     monkeypatch.setattr(ops, "gather_windows_grad", lambda feat, b, ids, w, stride, w_c, h_c, pad=2, cells=None:
                         wref.crop(feat, b, ids, w, stride, h_c, w_c, pad))
     _, ref64 = _module_run(module(torch.float64, hip_merge=True), maps, descs, data, grads, torch.float64)
-    assert len(calls) == 2                                           # float64 tensors: the torch lines
+    assert calls == {"window_merge": 2}                              # float64 tensors: the torch lines
     _hold(f"module {layout}", hip, ref32, ref64, names)
     with torch.no_grad():                                            # a call that wants no gradient: the lines as they are
         fp = module(hip_merge=True)
         fp(maps[0], maps[1], descs[0], descs[1], dict(data))
-    assert len(calls) == 2
+    assert calls == {"window_merge": 2}
 
 
 # ---- memory --------------------------------------------------------------------------------------------------------
-def _peak_above_inputs(fn, feat, w_win, ctx, g, *args):
-    feat, w_win, ctx = (t.detach().requires_grad_(True) for t in (feat, w_win, ctx))
-    torch.cuda.synchronize()
-    torch.cuda.reset_peak_memory_stats()
-    base = torch.cuda.memory_allocated()
-    out = fn(feat, w_win, ctx, *args)
-    grads = torch.autograd.grad(out, [feat, w_win, ctx], g)
-    torch.cuda.synchronize()
-    peak = torch.cuda.max_memory_allocated() - base
-    del out, grads
-    return peak
-
-
 def test_peak_memory():
     """forward + backward above the inputs at M = 2000, W = 7 on one 640x480 map: out, the gradients and one workspace per
     call (g w_win is its bulk) - below what the torch lines hold, measured in the same test"""
@@ -340,7 +312,7 @@ def test_peak_memory():
     wref.autograd(ops.window_merge, *small[:4], *small[4:], 7, 4, wref.HC, wref.WC)      # (library loaded, attributes set)
     spare = torch.empty(768 << 20, dtype=torch.uint8, device=DEV)   # (one cached segment: tests/test_gpu_qkv_projection.py)
     del spare
-    peak_hip = _peak_above_inputs(ops.window_merge, feat, w_win, ctx, g, *args)
-    peak_torch = _peak_above_inputs(wref.lines, feat, w_win, ctx, g, *args)
+    peak_hip = yard.peak_above_inputs(ops.window_merge, (feat, w_win, ctx), g, *args)
+    peak_torch = yard.peak_above_inputs(wref.lines, (feat, w_win, ctx), g, *args)
     print(f"MEM  window_merge M{m} W7  hip {peak_hip} B  torch {peak_torch} B  ({peak_torch / max(peak_hip, 1):.2f} x)")
     assert peak_hip < peak_torch, (peak_hip, peak_torch)

@@ -9,6 +9,8 @@ import torch.nn.functional as F
 
 from featurematching_amd import synth
 
+from train_layers_yardstick import rel_err  # noqa: F401  (the error measure of the GPU tests)
+
 N, HF, WF, HC, WC, STRIDE, PAD = 2, 24, 32, 6, 8, 4, 2        # the shared small map: 2 x 64 x 24 x 32, coarse grid 6 x 8
 NAMES = ("out", "d_feat", "d_Ww", "d_ctx")
 
@@ -68,10 +70,3 @@ def autograd(fn, feat, w_win, ctx, g, *args, dtype=None, weight_grad=True, memor
         assert w_win.grad is None
         return out.detach(), feat.grad, ctx.grad
     return out.detach(), feat.grad, w_win.grad, ctx.grad
-
-
-def rel_err(x, ref):
-    """max|x - ref| / max|ref| (0 for an all-zero reference that is met exactly)"""
-    top = ref.abs().max().item()
-    err = (x.double() - ref.double()).abs().max().item()
-    return err / top if top > 0 else err

@@ -21,14 +21,9 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 from featurematching_amd import synth  # noqa: E402
 import matcher_train_ref as mref  # noqa: E402
+from timing import say, write_log  # noqa: E402
 
-LINES = []
 GROUPS = ("backbone", "coarse.", "fine_preprocess", "fine.", "fine_matching", "image")
-
-
-def say(text=""):
-    print(text, flush=True)
-    LINES.append(text)
 
 
 def apart(ga, gb):
@@ -114,9 +109,7 @@ def main():
         part_b(fixture)
         say()
     part_c()
-    if out:
-        with open(out, "w") as f:
-            f.write("\n".join(LINES) + "\n")
+    write_log(out)
 
 
 if __name__ == "__main__":

@@ -23,36 +23,12 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from featurematching_amd import ops, synth, transformer  # noqa: E402
+from timing import say, timeit, write_log  # noqa: E402
 
 HBM_BYTES_PER_S = 8.0e12
 FP32_FLOPS = 157.3e12
 SIZES = [196000, 100000]
 FWD_BYTES, BWD_BYTES, FWD_FLOP, BWD_FLOP = 768, 1280, 57344, 172032      # per token
-LINES = []
-
-
-def say(text=""):
-    print(text, flush=True)
-    LINES.append(text)
-
-
-def timeit(fn):
-    """ms per call by device events, over a window of about 0.3 s (5 to 1000 calls)"""
-    fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(3):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    n = int(min(1000, max(5, 300.0 / max(e0.elapsed_time(e1) / 3, 1e-3))))
-    e0.record()
-    for _ in range(n):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / n
 
 
 def torch_tail(layer):
@@ -160,9 +136,7 @@ def main():
     say()
     for T, ok in results:
         say(f"tail [{T}, 64]: the condition is {'met' if ok else 'NOT met'}")
-    if out:
-        with open(out, "w") as f:
-            f.write("\n".join(LINES) + "\n")
+    write_log(out)
 
 
 if __name__ == "__main__":

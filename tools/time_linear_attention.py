@@ -21,36 +21,12 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from featurematching_amd import ops, synth, transformer  # noqa: E402
+from timing import say, timeit, write_log  # noqa: E402
 
 HBM_BYTES_PER_S = 8.0e12
 FP32_FLOPS = 157.3e12
 SIZES = [("window", (4000, 49, 49, 8, 8)), ("window", (4000, 25, 25, 8, 8)), ("long", (1, 4800, 4800, 8, 32)),
          ("long", (4, 4800, 4800, 8, 32))]
-LINES = []
-
-
-def say(text=""):
-    print(text, flush=True)
-    LINES.append(text)
-
-
-def timeit(fn):
-    """ms per call by device events, over a window of about 0.3 s (5 to 1000 calls)"""
-    fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(3):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    n = int(min(1000, max(5, 300.0 / max(e0.elapsed_time(e1) / 3, 1e-3))))
-    e0.record()
-    for _ in range(n):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / n
 
 
 def needs(dims):
@@ -149,9 +125,7 @@ def main():
     for route in ("window", "long"):
         met = all(ok for r, _, ok in results if r == route)
         say(f"{route} route: the condition is {'met at every size' if met else 'NOT met at every size'}")
-    if out:
-        with open(out, "w") as f:
-            f.write("\n".join(LINES) + "\n")
+    write_log(out)
 
 
 if __name__ == "__main__":

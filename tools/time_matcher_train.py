@@ -16,18 +16,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from featurematching_amd import modules, synth  # noqa: E402
 from featurematching_amd.matcher import Matcher  # noqa: E402
+from timing import say, write_log  # noqa: E402
 
 H, W, K = 480, 640, 4000
 LOSS_CFG = {'fine_correct_thr': 1.0, 'pos_weight': 1.0, 'neg_weight': 1.0, 'pose_loss_cal_flag': False, 'coarse_type': 'focal',
             'focal_alpha': 0.25, 'focal_gamma': 2.0, 'coarse_weight': 1.0, 'fine_weight': 0.25}
 CONFIG = {'module': {'loss': LOSS_CFG, 'match_coarse': {'sparse_spvs': False}}}
 STAGES = ("backbone", "coarse", "coarse_matching", "fine_preprocess", "fine", "fine_matching")
-LINES = []
-
-
-def say(text=""):
-    print(text, flush=True)
-    LINES.append(text)
 
 
 def data(dev):
@@ -108,9 +103,7 @@ def main():
         step(m, loss, batch)()
         parts = split(m, loss, batch)
         say(f"hip_train {'on ' if flag else 'off'}  " + "   ".join(f"{k} {v:.2f}" for k, v in parts.items()))
-    if out:
-        with open(out, "w") as f:
-            f.write("\n".join(LINES) + "\n")
+    write_log(out)
 
 
 if __name__ == "__main__":

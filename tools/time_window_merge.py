@@ -25,35 +25,11 @@ import torch.nn.functional as F
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from featurematching_amd import modules, ops, synth  # noqa: E402
+from timing import say, timeit, write_log  # noqa: E402
 
 HBM_BYTES_PER_S = 8.0e12
 N, HF, WF, HC, WC, STRIDE, M = 1, 240, 320, 60, 80, 4, 4000
 LAYOUTS = {"NCHW": torch.contiguous_format, "channels-last": torch.channels_last}
-LINES = []
-
-
-def say(text=""):
-    print(text, flush=True)
-    LINES.append(text)
-
-
-def timeit(fn):
-    """ms per call by device events, over a window of about 0.3 s (5 to 1000 calls)"""
-    fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(3):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    n = int(min(1000, max(5, 300.0 / max(e0.elapsed_time(e1) / 3, 1e-3))))
-    e0.record()
-    for _ in range(n):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / n
 
 
 def ids(seed, dev):
@@ -155,9 +131,7 @@ def main():
     for w, layout, ok in results:
         say(f"window_merge W = {w} {layout}: the condition is {'met' if ok else 'NOT met'}")
     say(f"FinePreprocess: the condition is {'met' if module_ok else 'NOT met'}")
-    if out:
-        with open(out, "w") as f:
-            f.write("\n".join(LINES) + "\n")
+    write_log(out)
 
 
 if __name__ == "__main__":

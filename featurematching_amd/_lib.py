@@ -92,7 +92,11 @@ SIGNATURES = {
     "fm_encoder_tail_workspace_bytes": (C.c_size_t, [_i, _i]),
     "fm_encoder_tail_forward": (_i, [_p] * 9 + [_i, _i, _f, _f, _p, C.c_size_t, _p, _p, _p]),
     "fm_encoder_tail_backward": (_i, [_p] * 11 + [_i, _i, _f, _f, _p, C.c_size_t] + [_p] * 9 + [_p]),
-    "fm_qkv_projection_workspace_bytes": (C.c_size_t, [_i, _i, _i]),
+    "fm_coarse_tail_state_bytes": (C.c_size_t, [_i, _i]),
+    "fm_coarse_tail_workspace_bytes": (C.c_size_t, [_i, _i]),
+    "fm_coarse_tail_forward": (_i, [_p] * 9 + [_i, _i, _f, _f, _p, C.c_size_t, _p, _p, _p]),
+    "fm_coarse_tail_backward": (_i, [_p] * 11 + [_i, _i, _f, _f, _p, C.c_size_t] + [_p] * 9 + [_p]),
+    "fm_qkv_projection_workspace_bytes":(C.c_size_t, [_i, _i, _i]),
     "fm_qkv_projection_forward": (_i, [_p] * 5 + [_i, _i, _i, _p, C.c_size_t] + [_p] * 3 + [_p]),
     "fm_qkv_projection_backward": (_i, [_p] * 8 + [_i, _i, _i, _p, C.c_size_t] + [_p] * 5 + [_p]),
     "fm_window_merge_workspace_bytes": (C.c_size_t, [_i] * 5),

@@ -64,14 +64,15 @@ class Matcher(nn.Module):
     FineMatching with the reference's `data` dict protocol and sub-module names (network/net.py:24-32,51-92), so
     that a reference state dict addresses the same parameters."""
 
-    def __init__(self, config=None, backbone: nn.Module = None, hip_train: bool = True, train_coarse: str = 'stats'):
+    def __init__(self, config=None, backbone: nn.Module = None, hip_train: bool = True, train_coarse: str = 'stats',
+                 hip_train_coarse: bool = False):
         super().__init__()
         if train_coarse not in ('stats', 'matrix'):
             raise ValueError(f"train_coarse must be 'stats' or 'matrix', got {train_coarse!r}")
         cfg = dict(DEFAULT_CONFIG)
         cfg.update(config or {})
         self.config = cfg
-        self.hip_train, self.train_coarse = hip_train, train_coarse
+        self.hip_train, self.train_coarse, self.hip_train_coarse = hip_train, train_coarse, hip_train_coarse
         self.backbone = backbone or SmallFPN(3, cfg['coarse']['d_model'], cfg['fine']['d_model'])
         self.coarse = LocalFeatureTransformer(cfg['coarse'])
         self.coarse_matching = CoarseMatching(cfg['match_coarse'])
@@ -84,12 +85,13 @@ class Matcher(nn.Module):
         """Training mode switches on what only a training step uses, eval mode switches it off again - an eval-mode call
         is the same launches whatever `hip_train` is: the HIP training ops of the context layers (hip_attention, hip_tail,
         hip_proj; d_model 256 keeps the torch tail and projections by itself) and of FinePreprocess (hip_merge) with
-        hip_train, and the coarse stage's training output (loss_stats for train_coarse='stats', conf_matrix for
-        'matrix')."""
+        hip_train, the coarse layers' HIP tail (hip_coarse_tail) with hip_train and hip_train_coarse, and the coarse stage's
+        training output (loss_stats for train_coarse='stats', conf_matrix for 'matrix')."""
         super().train(mode)
         on = bool(mode) and self.hip_train
         for tf in (self.coarse, self.fine):
             tf.hip_attention = tf.hip_tail = tf.hip_proj = on      # (each writes through to the transformer's layers)
+        self.coarse.hip_coarse_tail = on and self.hip_train_coarse
         self.fine_preprocess.hip_merge = on
         self.coarse_matching.loss_stats = bool(mode) and self.train_coarse == 'stats'
         self.coarse_matching.conf_matrix = bool(mode) and self.train_coarse == 'matrix'

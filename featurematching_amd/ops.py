@@ -1094,6 +1094,73 @@ def encoder_tail(x: torch.Tensor, a: torch.Tensor, merge_w: torch.Tensor, ln1_w:
     return _EncoderTail.apply(x, a, eps1, eps2, *params)
 
 
+def coarse_tail_supported(x: torch.Tensor, a: torch.Tensor) -> bool:
+    """Whether coarse_tail serves x, a [..., 256]: float32 GPU tensors of equal shape, 256 channels, at least one token
+    (and at most 2^24) - ct_route of csrc/coarse_tail.hip."""
+    if not (x.is_cuda and a.is_cuda and x.dtype == torch.float32 and a.dtype == torch.float32 and x.dim() >= 1):
+        return False
+    return x.shape == a.shape and x.shape[-1] == 256 and 1 <= x.numel() // 256 <= 1 << 24
+
+
+def _rows256(t: torch.Tensor) -> torch.Tensor:
+    """[..., 256] as the coarse tail reads it: [T, 256], contiguous (the results are viewed back to the shape)"""
+    return t.reshape(-1, 256).contiguous()
+
+
+class _CoarseTail(torch.autograd.Function):
+    """fm_coarse_tail_forward / fm_coarse_tail_backward: x, a, the seven parameters and the forward call's state (none:
+    the backward recomputes) stay on ctx; each call has a workspace of its own, freed when the call has been enqueued."""
+
+    @staticmethod
+    def forward(ctx, x, a, eps1, eps2, *params):
+        xc, ac = _rows256(x), _rows256(a)
+        pc = [_f32c(p.detach(), "parameter") for p in params]
+        t, dev = xc.shape[0], xc.device
+        state_bytes = int(_lib.load().fm_coarse_tail_state_bytes(t, 256))
+        state = torch.empty(state_bytes // 4, dtype=torch.float32, device=dev) if state_bytes else None
+        ws, wsp, need = _workspace("fm_coarse_tail_workspace_bytes", dev, t, 256)
+        y = torch.empty_like(xc)
+        _call("fm_coarse_tail_forward", _ptr(xc), _ptr(ac), *map(_ptr, pc), t, 256, float(eps1), float(eps2), wsp, need,
+              _ptr(state), _ptr(y), dev=dev)
+        ctx.save_for_backward(xc, ac, state, *pc)
+        ctx.call = (t, float(eps1), float(eps2), need, x.shape)
+        return y.view(x.shape)
+
+    @staticmethod
+    def backward(ctx, grad):
+        xc, ac, state, *pc = ctx.saved_tensors
+        t, eps1, eps2, need, shape = ctx.call
+        dev = xc.device
+        g = _rows256(_f32c(grad, "grad"))
+        ws, wsp = _aligned_workspace(need, dev)
+        d_x, d_a = torch.empty_like(xc), torch.empty_like(ac)
+        d_p, d_p_back = _param_grads(pc, ctx.needs_input_grad[4:])       # all seven or none
+        _call("fm_coarse_tail_backward", _ptr(xc), _ptr(ac), *map(_ptr, pc), _ptr(g), _ptr(state), t, 256, eps1, eps2, wsp,
+              need, _ptr(d_x), _ptr(d_a), *map(_ptr, d_p), dev=dev)
+        return (d_x.view(shape), d_a.view(shape), None, None, *d_p_back)
+
+
+def coarse_tail(x: torch.Tensor, a: torch.Tensor, merge_w: torch.Tensor, ln1_w: torch.Tensor, ln1_b: torch.Tensor,
+                mlp0_w: torch.Tensor, mlp2_w: torch.Tensor, ln2_w: torch.Tensor, ln2_b: torch.Tensor, eps1: float = 1e-5,
+                eps2: float = 1e-5) -> torch.Tensor:
+    """encoder_tail at d_model 256, the coarse context layers' width (float32 on the exact-float32 matrix instructions,
+    forward and backward, both deterministic):
+        n1 = LayerNorm1(a merge_w^T);  y = x + LayerNorm2(relu([x, n1] mlp0_w^T) mlp2_w^T)
+    x (the layer's input), a (the attention's output) [..., 256] -> [..., 256].  The backward recomputes the chain from x
+    and a, chunk by chunk in a workspace whose size does not grow with the token count: only x, a and the parameters are
+    kept.  Inputs that coarse_tail_supported refuses raise; so do CPU tensors."""
+    _on_gpu(x, "x"), _on_gpu(a, "a")
+    if not coarse_tail_supported(x, a):
+        raise ValueError(f"coarse_tail serves float32 x, a of one shape [..., 256] with at least one token, got "
+                         f"{tuple(x.shape)} {x.dtype}, {tuple(a.shape)} {a.dtype}")
+    params = (merge_w, ln1_w, ln1_b, mlp0_w, mlp2_w, ln2_w, ln2_b)
+    want = ((256, 256), (256,), (256,), (512, 512), (256, 512), (256,), (256,))
+    for p, shape in zip(params, want):
+        if tuple(p.shape) != shape or p.dtype != torch.float32 or not p.is_cuda:
+            raise ValueError(f"coarse_tail parameters are float32 GPU tensors of shapes {want}, got {tuple(p.shape)} {p.dtype}")
+    return _CoarseTail.apply(x, a, eps1, eps2, *params)
+
+
 def qkv_projection_supported(x: torch.Tensor, source: torch.Tensor) -> bool:
     """Whether qkv_projection serves x, source: float32 GPU tensors [T, 64] (Tx, Ts independent) or [N, L, 64], [N, S, 64]
     with the same leading batch dimension, at least one token each (and at most 2^24) - qp_route of csrc/qkv_proj.hip."""

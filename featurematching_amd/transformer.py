@@ -63,13 +63,16 @@ class EncoderLayer(nn.Module):
     tensors, d_model 64; masked calls too: the tail is token-wise); every other call takes the torch lines as they are.
     hip_proj=True likewise sends the three projections in front of the attention through ops.qkv_projection - one HIP
     kernel forward, one backward - wherever ops.qkv_projection_supported accepts (x, source); every other call takes the
-    three nn.Linear lines as they are."""
+    three nn.Linear lines as they are.  hip_coarse_tail=True sends the tail's three lines through ops.coarse_tail - the same
+    op at d_model 256, HIP forward and a HIP backward that recomputes the chain chunk by chunk - wherever
+    ops.coarse_tail_supported accepts (float32 GPU tensors, d_model 256); every other call takes the torch lines as they
+    are."""
 
     def __init__(self, d_model: int, nhead: int, attention: str = 'linear', hip_attention: bool = False,
-                 hip_tail: bool = False, hip_proj: bool = False):
+                 hip_tail: bool = False, hip_proj: bool = False, hip_coarse_tail: bool = False):
         super().__init__()
         self.attention, self.hip_attention, self.hip_tail = attention, hip_attention, hip_tail
-        self.hip_proj = hip_proj
+        self.hip_proj, self.hip_coarse_tail = hip_proj, hip_coarse_tail
         self.nhead, self.dim = nhead, d_model // nhead
         self.q_proj = nn.Linear(d_model, d_model, bias=False)
         self.k_proj = nn.Linear(d_model, d_model, bias=False)
@@ -99,6 +102,11 @@ class EncoderLayer(nn.Module):
             if ops.encoder_tail_supported(x, msg):
                 return ops.encoder_tail(x, msg, self.merge.weight, self.norm1.weight, self.norm1.bias, self.mlp[0].weight,
                                         self.mlp[2].weight, self.norm2.weight, self.norm2.bias, self.norm1.eps, self.norm2.eps)
+        if self.hip_coarse_tail:
+            msg = msg.reshape(n, l, -1)
+            if ops.coarse_tail_supported(x, msg):
+                return ops.coarse_tail(x, msg, self.merge.weight, self.norm1.weight, self.norm1.bias, self.mlp[0].weight,
+                                       self.mlp[2].weight, self.norm2.weight, self.norm2.bias, self.norm1.eps, self.norm2.eps)
         msg = self.norm1(self.merge(msg.reshape(n, l, -1)))
         msg = self.norm2(self.mlp(torch.cat([x, msg], dim=2)))
         return x + msg
@@ -134,14 +142,17 @@ class LocalFeatureTransformer(nn.Module):
     fine level - the HIP attention core with its HIP backward (EncoderLayer); the eval-mode kernels are not affected.
     hip_tail=True (default False) gives them the fused HIP tail with its HIP backward (EncoderLayer; d_model 64 only).
     hip_proj=True (default False) gives them the fused q / k / v projections with their HIP backward (EncoderLayer;
-    d_model 64 only): with all three switches a training-mode fine layer is three HIP ops each way.  The three are
-    attributes too: `tf.hip_tail = True` after construction switches every layer."""
+    d_model 64 only): with all three switches a training-mode fine layer is three HIP ops each way.
+    hip_coarse_tail=True (default False) gives them the HIP tail of d_model 256 with its HIP backward (EncoderLayer; d_model
+    256 only).  The four are attributes too: `tf.hip_tail = True` after construction switches every layer."""
 
     _warned_detached = False
-    hip_attention, hip_tail, hip_proj = (_layer_switch(k) for k in ("hip_attention", "hip_tail", "hip_proj"))
+    hip_attention, hip_tail, hip_proj, hip_coarse_tail = (
+        _layer_switch(k) for k in ("hip_attention", "hip_tail", "hip_proj", "hip_coarse_tail"))
 
     def __init__(self, config, use_hip: bool = True, check_range: bool = True, inference_only: bool = True,
-                 hip_attention: bool = False, hip_tail: bool = False, hip_proj: bool = False):
+                 hip_attention: bool = False, hip_tail: bool = False, hip_proj: bool = False,
+                 hip_coarse_tail: bool = False):
         super().__init__()
         self.use_hip, self.check_range, self.inference_only = use_hip, check_range, inference_only
         self.range_fallbacks = 0
@@ -151,7 +162,7 @@ class LocalFeatureTransformer(nn.Module):
             raise ValueError(f"attention must be 'linear' or 'full' (transformer.py:22), got {self.attention!r}")
         self.d_model, self.layer_names = config['d_model'], list(config['layer_names'])
         self.layers = nn.ModuleList(EncoderLayer(config['d_model'], config['nhead'], self.attention, hip_attention,
-                                                 hip_tail, hip_proj)
+                                                 hip_tail, hip_proj, hip_coarse_tail)
                                     for _ in self.layer_names)
         for p in self.parameters():
             if p.dim() > 1:

@@ -775,6 +775,41 @@ int fm_encoder_tail_backward(const float* x, const float* a, const float* w_merg
                              void* stream);
 
 /*
+ * The same tail and its gradient at d = 256: the coarse level's training path.  Arguments, shapes (w_merge [256, 256],
+ * w_mlp0 [512, 512], w_mlp2 [256, 512], the LayerNorm vectors [256]), alignment and arithmetic are those of
+ * fm_encoder_tail_* above: float32 on the exact-float32 matrix instructions, one rounding per product, no reduced
+ * precision, no BLAS call.
+ *   fm_coarse_tail_forward  : y [dev] float32 [T, d].
+ *   fm_coarse_tail_backward : d_x, d_a [T, d] and the seven parameter gradients from d_y [T, d]; the forward chain is
+ *                             recomputed from x and a.  Every element is written.  The seven parameter-gradient pointers
+ *                             are all non-NULL or all NULL; all NULL = d_x and d_a only, and no parameter-gradient work.
+ * T is walked in chunks of at most 8192 tokens inside the call (5 launches per chunk forward, 14 backward, 9 without
+ * parameter gradients); a chunk's [tokens, 256] and [tokens, 512] intermediates live in the workspace.
+ * state: fm_coarse_tail_state_bytes answers 0 - nothing is kept between the calls - and `state` may be NULL.
+ * workspace: fm_coarse_tail_workspace_bytes(T, d) bytes [dev], 256-byte aligned: one chunk's intermediates, one slab of
+ * partial weight gradients per 512 tokens of a chunk and one row of partial LayerNorm gradients per 64.  It grows with T up
+ * to 8192 tokens and is the same from there on (under 96 MiB); the same size serves both calls and nothing is kept in it
+ * between them, nor is anything asked of its contents.  Supported: d = 256, 1 <= T <= 2^24.  Both byte queries answer 0
+ * for a shape that is not served.  No atomics, grids that depend on T alone: every output is the same bits on every run.
+ * No host synchronisation or allocation; everything goes to `stream` and can be captured in a graph.
+ * Statuses, checked in this order before anything is launched: FM_E_NULL (a required pointer; some but not all of the
+ * seven gradient pointers), FM_E_SHAPE (T <= 0 or d <= 0), FM_E_UNSUPPORTED (d != 256, an eps that is not > 0, T > 2^24),
+ * FM_E_WORKSPACE (NULL, too small or misaligned); then a hipError_t.
+ */
+size_t fm_coarse_tail_state_bytes(int T, int d);
+size_t fm_coarse_tail_workspace_bytes(int T, int d);
+int fm_coarse_tail_forward(const float* x, const float* a, const float* w_merge, const float* ln1_w, const float* ln1_b,
+                           const float* w_mlp0, const float* w_mlp2, const float* ln2_w, const float* ln2_b, int T, int d,
+                           float eps1, float eps2, void* workspace, size_t workspace_bytes, float* state, float* y,
+                           void* stream);
+int fm_coarse_tail_backward(const float* x, const float* a, const float* w_merge, const float* ln1_w, const float* ln1_b,
+                            const float* w_mlp0, const float* w_mlp2, const float* ln2_w, const float* ln2_b,
+                            const float* d_y, const float* state, int T, int d, float eps1, float eps2, void* workspace,
+                            size_t workspace_bytes, float* d_x, float* d_a, float* d_w_merge, float* d_ln1_w,
+                            float* d_ln1_b, float* d_w_mlp0, float* d_w_mlp2, float* d_ln2_w, float* d_ln2_b,
+                            void* stream);
+
+/*
  * The q / k / v projections of an encoder layer of the context transformer (the three bias-free linear maps in front of
  * the attention) and their gradient, fused: the fine level's training path, d = 64.  x [dev] float32 [Tx, d] (the layer's
  * input), src [dev] float32 [Ts, d] (the tokens it attends to), wq, wk, wv [d, d] (nn.Linear weights, [out, in]).  All

@@ -3,9 +3,10 @@
 correspondences, with the HIP training ops off (hip_train=False) and on, in ms by device events: the whole step, two
 alternating rounds, and one more step split per stage (an event at each stage's entry and exit; the backward as one
 piece).  The batch - images, correspondences - is built once, before anything is timed; every step gets a shallow copy
-of the dict.  Report only.
+of the dict.  --hip-train-coarse adds a third matcher to every round: hip_train on with hip_train_coarse (the coarse
+layers' tail through ops.coarse_tail).  Report only.
 
-    python tools/time_matcher_train.py [--out FILE]
+    python tools/time_matcher_train.py [--hip-train-coarse] [--out FILE]
 """
 import os
 import sys
@@ -86,23 +87,26 @@ def main():
     loss = modules.Loss(CONFIG).train()
     batch = data(dev)                                  # built once, outside every timed region
     torch.cuda.synchronize()
+    kinds = {"off": dict(hip_train=False), "on ": dict(hip_train=True)}
+    if "--hip-train-coarse" in sys.argv:
+        kinds["on, hip_train_coarse"] = dict(hip_train=True, hip_train_coarse=True)
     ms, runs = {}, {}
-    for flag in (False, True):
+    for kind, kw in kinds.items():
         torch.manual_seed(3)
-        runs[flag] = step(Matcher(hip_train=flag).to(dev).train(), loss, batch)
-        runs[flag](); runs[flag]()
-        ms[flag] = []
+        runs[kind] = step(Matcher(**kw).to(dev).train(), loss, batch)
+        runs[kind](); runs[kind]()
+        ms[kind] = []
     for _ in range(2):
-        for flag in (False, True):
-            ms[flag].append(ms_of(runs[flag]))
-    for flag in (False, True):
-        say(f"hip_train {'on ' if flag else 'off'}  whole step {ms[flag][0]:8.2f} / {ms[flag][1]:8.2f} ms (round 1 / round 2)")
-    for flag in (False, True):
+        for kind in kinds:
+            ms[kind].append(ms_of(runs[kind]))
+    for kind in kinds:
+        say(f"hip_train {kind}  whole step {ms[kind][0]:8.2f} / {ms[kind][1]:8.2f} ms (round 1 / round 2)")
+    for kind, kw in kinds.items():
         torch.manual_seed(3)
-        m = Matcher(hip_train=flag).to(dev).train()
+        m = Matcher(**kw).to(dev).train()
         step(m, loss, batch)()
         parts = split(m, loss, batch)
-        say(f"hip_train {'on ' if flag else 'off'}  " + "   ".join(f"{k} {v:.2f}" for k, v in parts.items()))
+        say(f"hip_train {kind}  " + "   ".join(f"{k} {v:.2f}" for k, v in parts.items()))
     write_log(out)
 
 

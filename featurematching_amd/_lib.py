@@ -88,6 +88,10 @@ SIGNATURES = {
     "fm_linear_attention_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i]),
     "fm_linear_attention_forward": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p, C.c_size_t, _p, _p, _p]),
     "fm_linear_attention_backward": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p, C.c_size_t, _p, _p, _p, _p]),
+    "fm_full_attention_state_bytes": (C.c_size_t, [_i, _i, _i, _i, _i]),
+    "fm_full_attention_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i]),
+    "fm_full_attention_forward": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, C.c_size_t, _p, _p, _p]),
+    "fm_full_attention_backward": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, C.c_size_t, _p, _p, _p, _p]),
     "fm_encoder_tail_state_bytes": (C.c_size_t, [_i, _i]),
     "fm_encoder_tail_workspace_bytes": (C.c_size_t, [_i, _i]),
     "fm_encoder_tail_forward": (_i, [_p] * 9 + [_i, _i, _f, _f, _p, C.c_size_t, _p, _p, _p]),

@@ -1033,6 +1033,68 @@ def linear_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, q_mask: 
     return _LinearAttention.apply(q, k, v, q_mask, kv_mask, eps)
 
 
+def full_attention_supported(q: torch.Tensor, k: torch.Tensor) -> bool:
+    """Whether full_attention serves q [N,L,H,D] / k [N,S,H,D]: float32 GPU tensors of 8 heads of 8 or 32 channels, any
+    L, S >= 1, N * max(L, S) * H * D < 2^31 - fa_supported of csrc/full_attn.hip."""
+    if not (q.is_cuda and k.is_cuda and q.dtype == torch.float32 and k.dtype == torch.float32 and q.dim() == 4
+            and k.dim() == 4):
+        return False
+    n, l, h, d = q.shape
+    s = k.shape[1]
+    if k.shape[0] != n or tuple(k.shape[2:]) != (h, d) or min(n, l, s) < 1 or h != 8 or d not in (8, 32):
+        return False
+    return n * max(l, s) * h * d < 1 << 31
+
+
+class _FullAttention(torch.autograd.Function):
+    """fm_full_attention_forward / fm_full_attention_backward: q, k, v, out and the forward call's state (one
+    log-sum-exp per query and head) stay on ctx; each call has a workspace of its own.  A call that nothing will
+    differentiate hands a NULL state and saves nothing."""
+
+    @staticmethod
+    def forward(ctx, q, k, v):
+        qc, kc, vc = _f32c(q, "q"), _f32c(k, "k"), _f32c(v, "v")
+        n, l, h, d = qc.shape
+        s, dev = kc.shape[1], qc.device
+        dims = (n, l, s, h, d)
+        wants = any(ctx.needs_input_grad)
+        state_bytes = int(_lib.load().fm_full_attention_state_bytes(*dims)) if wants else 0
+        state = torch.empty(state_bytes // 4, dtype=torch.float32, device=dev) if state_bytes else None
+        ws, wsp, need = _workspace("fm_full_attention_workspace_bytes", dev, *dims, empty_ok=True)
+        out = torch.empty_like(qc)
+        _call("fm_full_attention_forward", _ptr(qc), _ptr(kc), _ptr(vc), *dims, wsp, need, _ptr(state), _ptr(out), dev=dev)
+        if wants:
+            ctx.save_for_backward(qc, kc, vc, out, state)
+            ctx.call = (dims, need, (q.dtype, k.dtype, v.dtype))
+        return out.to(q.dtype)
+
+    @staticmethod
+    def backward(ctx, grad):
+        qc, kc, vc, out, state = ctx.saved_tensors
+        dims, need, dtypes = ctx.call
+        dev = qc.device
+        g = _f32c(grad, "grad")
+        ws, wsp = _aligned_workspace(need, dev)
+        d_q, d_k, d_v = torch.empty_like(qc), torch.empty_like(kc), torch.empty_like(vc)
+        _call("fm_full_attention_backward", _ptr(qc), _ptr(kc), _ptr(vc), _ptr(out), _ptr(g), _ptr(state), *dims, wsp, need,
+              _ptr(d_q), _ptr(d_k), _ptr(d_v), dev=dev)
+        return d_q.to(dtypes[0]), d_k.to(dtypes[1]), d_v.to(dtypes[2])
+
+
+def full_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, q_mask: Optional[torch.Tensor] = None,
+                   kv_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """transformer.full_attention (the reference's FullAttention, attentions.py:48-79, no dropout) as a differentiable
+    HIP op that never stores the [L, S] scores: q [N,L,H,D], k / v [N,S,H,D] -> [N,L,H,D].  Forward
+    fm_full_attention_forward, backward fm_full_attention_backward, both deterministic.  Padding masks are not served
+    (ValueError: masked calls keep the torch function); shapes that full_attention_supported refuses raise
+    (FM_E_UNSUPPORTED); so do CPU tensors."""
+    if q_mask is not None or kv_mask is not None:
+        raise ValueError("ops.full_attention takes no padding masks: use transformer.full_attention")
+    if q.dim() != 4 or k.dim() != 4 or k.shape != v.shape or k.shape[0] != q.shape[0] or k.shape[2:] != q.shape[2:]:
+        raise ValueError(f"q [N,L,H,D] and k, v [N,S,H,D] expected, got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}")
+    return _FullAttention.apply(q, k, v)
+
+
 def encoder_tail_supported(x: torch.Tensor, a: torch.Tensor) -> bool:
     """Whether encoder_tail serves x, a [..., 64]: float32 GPU tensors of equal shape, 64 channels, at least one token (and
     at most 2^24) - et_route of csrc/encoder_tail.hip."""

@@ -8,8 +8,10 @@ match - and the COARSE layers (d_model 256, 8 heads, any self / cross sequence, 
 as fm_coarse_transformer - three launches per encoder layer, hi/lo-split float16 products on the matrix cores (22
 significant bits).  That holds under the reference's own inference call, `matcher.eval()(data)` with grad mode on
 (demo/demo.py:105-108).  The torch ops below are the trainable definition: training mode, inputs that require grad,
-other configurations (the reference's 'full' attention among them), padding masks, CPU tensors.  Parameter names and shapes equal the reference's, so a reference state dict
-loads unchanged:
+other configurations (the reference's 'full' attention among them), padding masks, CPU tensors.  With attention='full'
+the layers stay torch modules in every mode, and their attention core is ops.full_attention - HIP forward and backward,
+the [L, S] scores never stored - wherever it serves the call (EncoderLayer).  Parameter names and shapes equal the
+reference's, so a reference state dict loads unchanged:
 
     layers.<k>.{q_proj,k_proj,v_proj,merge}.weight [d,d]   layers.<k>.mlp.{0,2}.weight [2d,2d] / [d,2d]
     layers.<k>.{norm1,norm2}.{weight,bias} [d]
@@ -44,7 +46,8 @@ def full_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, q_mask=Non
     """Scaled dot-product attention, the reference's other option (attentions.py:54-79, no dropout: its default).
     q [N,L,H,D], k,v [N,S,H,D] -> [N,L,H,D]: softmax over the source positions of q.k / sqrt(D); with a kv_mask the
     pairs outside q_mask x kv_mask are filled with -inf first (:71-72: a fully padded query row comes out as NaN there
-    too).  Materialises the [N,L,S,H] scores as the reference does: an option for short sequences."""
+    too).  Materialises the [N,L,S,H] scores as the reference does: the definition, and what masked, CPU and float64
+    calls run; ops.full_attention is the same function without the stored scores."""
     qk = torch.einsum("nlhd,nshd->nlsh", q, k)
     if kv_mask is not None:
         qm = torch.ones(q.shape[:2], dtype=torch.bool, device=q.device) if q_mask is None else q_mask.bool()
@@ -57,7 +60,11 @@ class EncoderLayer(nn.Module):
     """x <- x + LN2(MLP([x, LN1(merge(attn(q(x), k(src), v(src))))]))   (transformer.py:34-57); attention = 'linear'
     (the default) or 'full' (:22).  hip_attention=True sends the 'linear' attention of shapes that
     ops.linear_attention_supported accepts through ops.linear_attention (HIP forward and backward) instead of the torch
-    function above; every other call is the torch function, as with hip_attention=False.  hip_tail=True likewise sends
+    function above; every other call is the torch function, as with hip_attention=False.  With attention = 'full' it sends
+    the unmasked calls that ops.full_attention_supported accepts (float32 GPU tensors, 8 heads of 8 or 32 channels)
+    through ops.full_attention - HIP forward and backward, no stored scores - and so does, in eval mode, the owning
+    transformer's use_hip (forward's hip_core); masked, CPU and float64 calls, other head sizes and use_hip=False in eval
+    mode keep full_attention above.  hip_tail=True likewise sends
     the three lines behind the attention (merge, norm1, mlp, norm2, the residual) through ops.encoder_tail - one fused HIP
     kernel forward, one backward that recomputes the chain - wherever ops.encoder_tail_supported accepts (float32 GPU
     tensors, d_model 64; masked calls too: the tail is token-wise); every other call takes the torch lines as they are.
@@ -83,7 +90,9 @@ class EncoderLayer(nn.Module):
         self.norm1 = nn.LayerNorm(d_model)
         self.norm2 = nn.LayerNorm(d_model)
 
-    def forward(self, x: torch.Tensor, source: torch.Tensor, x_mask=None, source_mask=None) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, source: torch.Tensor, x_mask=None, source_mask=None,
+                hip_core: bool = False) -> torch.Tensor:
+        """hip_core: the owning LocalFeatureTransformer's use_hip ("HIP where there is a kernel"); it counts in eval mode."""
         from . import ops
         n, l, _ = x.shape
         heads = lambda t: t.view(n, -1, self.nhead, self.dim)
@@ -96,6 +105,9 @@ class EncoderLayer(nn.Module):
         q, k, v = heads(qkv[0]), heads(qkv[1]), heads(qkv[2])
         if self.hip_attention and self.attention == 'linear' and ops.linear_attention_supported(q, k):
             attn = ops.linear_attention
+        if self.attention == 'full' and x_mask is None and source_mask is None \
+                and (self.hip_attention or (hip_core and not self.training)) and ops.full_attention_supported(q, k):
+            attn = ops.full_attention
         msg = attn(q, k, v, q_mask=x_mask, kv_mask=source_mask)
         if self.hip_tail:
             msg = msg.reshape(n, l, -1)
@@ -140,6 +152,7 @@ class LocalFeatureTransformer(nn.Module):
     the torch layers, as a fine-tuning run that freezes batch norm with .eval() needs.
     hip_attention=True (default False) gives the torch layers - training mode, inputs that require grad, masks at the
     fine level - the HIP attention core with its HIP backward (EncoderLayer); the eval-mode kernels are not affected.
+    With attention='full' that core is ops.full_attention, and an eval-mode call takes it too while use_hip is on.
     hip_tail=True (default False) gives them the fused HIP tail with its HIP backward (EncoderLayer; d_model 64 only).
     hip_proj=True (default False) gives them the fused q / k / v projections with their HIP backward (EncoderLayer;
     d_model 64 only): with all three switches a training-mode fine layer is three HIP ops each way.
@@ -185,8 +198,8 @@ class LocalFeatureTransformer(nn.Module):
                 import warnings
                 warnings.warn("LocalFeatureTransformer: eval-mode HIP kernels return tensors without a graph through the "
                               "layers' parameters; pass inference_only=False (or call .train()) to fine-tune them")
-        if self.attention != 'linear':               # 'full' attention (attentions.py:54-79): the torch layers
-            return None
+        if self.attention != 'linear':               # 'full' attention (attentions.py:54-79): the torch layers, whose
+            return None                              # attention core is ops.full_attention where it serves (EncoderLayer)
         if not self.use_hip or self.training or wants_grad or not feat0.is_cuda or feat0.dtype != torch.float32 \
                 or feat1.dtype != torch.float32 or self.layers[0].nhead != 8 or feat0.shape[0] != feat1.shape[0]:
             return None
@@ -271,12 +284,13 @@ class LocalFeatureTransformer(nn.Module):
     def _torch_layers(self, feat0, feat1, mask0=None, mask1=None):
         m0 = None if mask0 is None else mask0.to(feat0.dtype)
         m1 = None if mask1 is None else mask1.to(feat1.dtype)
+        hip = self.use_hip
         for layer, name in zip(self.layers, self.layer_names):
             if name == 'self':
-                feat0, feat1 = layer(feat0, feat0, m0, m0), layer(feat1, feat1, m1, m1)
+                feat0, feat1 = layer(feat0, feat0, m0, m0, hip), layer(feat1, feat1, m1, m1, hip)
             elif name == 'cross':
-                feat0 = layer(feat0, feat1, m0, m1)
-                feat1 = layer(feat1, feat0, m1, m0)  # sees the UPDATED feat0, as in the reference (:93-94)
+                feat0 = layer(feat0, feat1, m0, m1, hip)
+                feat1 = layer(feat1, feat0, m1, m0, hip)  # sees the UPDATED feat0, as in the reference (:93-94)
             else:
                 raise KeyError(name)
         return feat0, feat1

@@ -740,6 +740,40 @@ int fm_linear_attention_backward(const float* q, const float* k, const float* v,
                                  float* d_k, float* d_v, void* stream);
 
 /*
+ * Full softmax attention (the reference's FullAttention, network/module/attentions.py:48-79, without mask and dropout:
+ * what its EncoderLayer constructs) and its gradient: the attention core of the context layers of attention = 'full'.
+ * q, out, d_out, d_q [dev] float32 [N, L, H*D], k, v, d_k, d_v [dev] float32 [N, S, H*D], head h in channels
+ * [h*D, (h+1)*D), all (and state) 16-byte aligned.  Per sample and head:
+ *     out[l] = sum_s softmax_s(q_l . k_s / sqrt(D)) v_s
+ * float32 arithmetic on the exact-float32 matrix instructions; the [L, S] scores of a head are never stored, forward
+ * or backward.  Served: H = 8, D = 8 or 32, any L, S >= 1 (L != S: a cross layer between images of different size),
+ * any N >= 1 while N * max(L, S) * H * D < 2^31 (N is not bounded by a grid dimension).
+ *   fm_full_attention_forward  : out; online softmax over tiles of 32 keys (running maximum and sum).  `state` [dev], if
+ *                                not NULL, receives fm_full_attention_state_bytes bytes: the log-sum-exp of the scaled
+ *                                scores of every (n, h, l), float32 [N, H, L].  NULL is the inference call and writes
+ *                                nothing.  One launch.
+ *   fm_full_attention_backward : d_q, d_k, d_v from d_out, the forward call's `out` and the `state` it wrote (required).
+ *                                The probabilities are recomputed from q, k and the state.  Three launches: delta =
+ *                                rowsum(d_out * out) into the workspace, then d_k and d_v (a wave owns 32 keys and walks
+ *                                the queries), then d_q (a wave owns 32 queries and walks the keys).
+ * Every output element is written.  state: N*L*H floats rounded up to 256 bytes.  workspace:
+ * fm_full_attention_workspace_bytes bytes [dev], 256-byte aligned (the same N*L*H floats: delta); both calls check it, the
+ * backward call writes all of it before reading it and nothing is kept in it between calls.  Both byte queries answer 0
+ * for an invalid or unserved shape.  No atomics and no sum across workgroups - every output is the same bits on every
+ * call - and no host synchronisation or allocation.  Statuses, in this order and before anything is launched: FM_E_NULL
+ * (q, k, v, out; backward: also d_out, state, d_q, d_k, d_v; the workspace when its byte query is non-zero), FM_E_SHAPE
+ * (a non-positive size), FM_E_UNSUPPORTED (H != 8, D not 8 or 32, the element bound), FM_E_WORKSPACE (too small /
+ * misaligned), a hipError_t.
+ */
+size_t fm_full_attention_state_bytes(int N, int L, int S, int H, int D);
+size_t fm_full_attention_workspace_bytes(int N, int L, int S, int H, int D);
+int fm_full_attention_forward(const float* q, const float* k, const float* v, int N, int L, int S, int H, int D,
+                              void* workspace, size_t workspace_bytes, float* state, float* out, void* stream);
+int fm_full_attention_backward(const float* q, const float* k, const float* v, const float* out, const float* d_out,
+                               const float* state, int N, int L, int S, int H, int D, void* workspace,
+                               size_t workspace_bytes, float* d_q, float* d_k, float* d_v, void* stream);
+
+/*
  * The tail of an encoder layer of the context transformer (everything behind the attention) and its gradient, fused:
  * the fine level's training path, d = 64.  x, a [dev] float32 [T, d] (the layer's input and the attention's output, T
  * tokens, no token needs another); w_merge [d, d], w_mlp0 [2d, 2d], w_mlp2 [d, 2d] (nn.Linear weights, [out, in]);
